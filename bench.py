@@ -3,20 +3,26 @@
 batch 8 per GPU, 128-frame x 256-bin clips, dropout 0.1, on N MI355X GPUs (BASELINE.json configs[2]/[3]).
 
 A "step" = forward + fused loss + backward + (gradient all-reduce when N > 1) + fused Adam over one synthetic batch that
-is already resident in HBM.  One JSON line on rank 0 (see the driver contract in the task statement), with two extra
-objects: "roofline" (dominant kernel; per-launch HIP events in a profiling pass of its own AFTER the timed region, which itself runs
-without any instrumentation) and "cpu_baseline" (the CPU oracle = a port of the reference algorithm, timed on the host cores, rank 0 at
-N=1 only); plus "roofline_ffn" (the fused feed-forward block hftt_ffn_res_ln_fwd on the inference plan, against the MFMA roofline),
-"inference_clips_per_s", "bf16_mode" / "fp32_mfma_mode" (throughput of the other two precision modes and the output differences between
-them and the benchmarked one), "compat_path_clips_per_s" (the reference's training loop unchanged: torch.optim.Adam + nn criteria +
-loss.backward()) and, under N > 1, "collective" (backend, ranks and the all-gathered device list the all-reduce really saw).
+is already resident in HBM.  One JSON line on rank 0: "metric" / "value" / "unit" / "higher_is_better" / "dtype" and "ms_per_step" (the
+wall time of one timed step), the per-step HIP-event spread, and under N > 1 "collective" (backend, ranks and the all-gathered device list
+the all-reduce really saw).  A plain run does only that: set-up, `--warmup` steps, `--steps` timed steps, the line.
+
+--dump-outputs DIR: after the timed steps, what the last of them computed goes to DIR/<name>.npy (float32; see dump_outputs).
+
+--full adds everything beyond the headline figure, after the timed region: "roofline" (dominant kernel; per-launch HIP events in a
+profiling pass of its own, with the counters of rocprofv3 --pmc child passes of this command) and "cpu_baseline" (the CPU oracle = a port
+of the reference algorithm, timed on the host cores, rank 0 at N=1 only); plus "roofline_ffn" (the fused feed-forward block
+hftt_ffn_res_ln_fwd on the inference plan, against the MFMA roofline), "inference_clips_per_s", "bf16_mode" / "fp32_mfma_mode" (throughput
+of the other two precision modes and the output differences between them and the benchmarked one), "front_end", "compat_path_clips_per_s"
+(the reference's training loop unchanged: torch.optim.Adam + nn criteria + loss.backward()), the whole-step HBM bytes and, under N > 1,
+the gradient buckets' overlap with the backward.  The --no-* switches leave single parts of --full out.
 
 Precision modes.  The benchmarked default is "x3": every product in three bf16-rate MFMA passes on split operands
 (fp16 hi + lo forward, bf16 hi + lo where a gradient is an operand), fp32 tensors in HBM -- the mode whose outputs meet north_star's 1e-3
 against the reference (measured 1.2e-4 on the reference-generated paper-size fixture).  "bf16" is the single-pass throughput mode (outputs
 3e-2 off), "parity" the exact-fp32-MFMA mode of round 1.
 
-Launch: python bench.py --gpus 1 --steps 20 --warmup 5
+Launch: python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -77,6 +83,34 @@ def synthetic_batch(cfg, B, seed, dev):
     velocity = torch.randint(1, cfg.n_velocity, shp, generator=g) * active
     return spec.to(dev), (onset.to(dev).contiguous(), offset.to(dev).contiguous(), active.float().to(dev).contiguous(),
                           velocity.to(torch.int64).to(dev).contiguous())
+
+
+# the nine forward outputs in the order the engine (and the reference's Model_SPEC2MIDI.forward) returns them
+OUTPUT_NAMES = ('onset_A', 'offset_A', 'mpe_A', 'velocity_A', 'attention', 'onset_B', 'offset_B', 'mpe_B', 'velocity_B')
+DUMP_CAP = 1 << 20          # elements per dumped array (4 MB as float32); a larger array is written as a fixed sample of this many
+
+
+def dump_outputs(path, ts, B, loss):
+    """--dump-outputs DIR: what the timed path computed in its LAST step, one DIR/<name>.npy (float32) per array a caller of TrainStep
+    receives -- `loss` (the [9] vector the step returns: total + 8 terms), `out_<name>` (the nine forward outputs, attention map included),
+    `grads` (the flat gradient of that step) and `params` (the flat parameters after its Adam update).  An array of more than DUMP_CAP
+    elements is written flattened, as the elements at DUMP_CAP sorted indices that numpy's default_rng(0) draws without replacement from its
+    length: the same sample in every run and every build.  Paper size, batch 8: ~23 MB in all."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    eng = ts.engine
+    arrays = ([('loss', loss)] + [('out_' + n, t) for n, t in zip(OUTPUT_NAMES, eng._ws[B]['outs'])]
+              + [('grads', eng.flat_grads), ('params', eng.flat_params)])
+    total = 0
+    for name, t in arrays:
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_CAP, replace=False))
+            t = t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device))
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'), a)
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20, total
 
 
 def host_cpu():
@@ -460,13 +494,20 @@ def main():
     ap.add_argument('--dropout', type=float, default=0.1)
     ap.add_argument('--data', default='synthetic', choices=['synthetic', 'store'],
                     help="'store': every step gathers its clips from a device-resident MAESTRO-format store (the gather is inside the step)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-profile', action='store_true', help='skip the per-launch HIP-event pass (roofline objects become null)')
-    ap.add_argument('--no-extras', action='store_true', help='skip the inference / parity-mode / compatibility-path legs')
-    ap.add_argument('--no-pmc', action='store_true', help='skip the rocprofv3 --pmc child passes (HBM traffic and MFMA-busy of this run; N = 1 only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32; see dump_outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also run the profiling pass, the rocprofv3 --pmc child passes, the inference / other-precision / '
+                         'front-end / compatibility-path legs, the CPU baseline and (N > 1) the bucket-overlap steps; off by default')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(with --full) skip the CPU baseline')
+    ap.add_argument('--no-profile', action='store_true', help='(with --full) skip the per-launch HIP-event pass (roofline objects become null)')
+    ap.add_argument('--no-extras', action='store_true', help='(with --full) skip the inference / parity-mode / compatibility-path legs')
+    ap.add_argument('--no-pmc', action='store_true', help='(with --full) skip the rocprofv3 --pmc child passes (HBM traffic and MFMA-busy of this run; N = 1 only)')
     ap.add_argument('--inference-only', action='store_true',
                     help='(the command measure_pmc wraps for the inference plan) three eval forwards in the x3 mode, then three in the bf16 mode; no JSON line')
     args = ap.parse_args()
+    if not args.full:               # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_cpu_baseline = args.no_profile = args.no_extras = args.no_pmc = True
 
     import gc
     from hftt_hip.trainer import TrainStep
@@ -587,6 +628,8 @@ def main():
             t = t.cpu()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ts, B, loss)
 
     def timed(fn, n, warm=1):
         for _ in range(warm):
@@ -613,7 +656,7 @@ def main():
         sync()
 
     overlap = None
-    if grad_sync is not None and dev.type == 'cuda':
+    if args.full and grad_sync is not None and dev.type == 'cuda':
         # two more steps with an event behind every bucket's all-reduce and one at the end of the backward: did the early buckets (time
         # decoder, frequency decoder) finish under the encoder's backward, as the design says?  (every rank runs them: they all-reduce)
         grad_sync.timing = True
@@ -808,7 +851,7 @@ def main():
             'kernels': kernels,
             'collective': collective,
         }
-        step_bytes, step_src = pmc_step_bytes()
+        step_bytes, step_src = pmc_step_bytes() if args.full else (None, None)
         if _LIVE_PMC is not None and _LIVE_PMC.get('bytes_per_step'):
             step_bytes, step_src = _LIVE_PMC['bytes_per_step'], _LIVE_PMC['source']
             result['hbm_bytes_outside_the_steps'] = _LIVE_PMC.get('bytes_outside_the_steps')

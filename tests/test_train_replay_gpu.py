@@ -456,7 +456,7 @@ def test_one_rank_rccl_rehearsal_of_the_bench_ddp_branch(dev, config):
     import sys
     env = dict(os.environ, HFTT_BENCH_FORCE_DDP='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(39500 + (os.getpid() % 2000) + (7 if config == 'paper' else 0)))
     r = subprocess.run([sys.executable, os.path.join(util.ROOT, 'bench.py'), '--config', config, '--steps', '3', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-extras', '--no-profile'], env=env, capture_output=True, text=True, timeout=600)
+                        '--full', '--no-cpu-baseline', '--no-extras', '--no-profile'], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
     assert line['value'] > 0 and line['n_gpus'] == 1
@@ -490,7 +490,7 @@ def test_two_rank_bench_on_one_gpu(dev, config):
     port = str(41000 + (os.getpid() % 2000) + (7 if config == 'paper' else 0))
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port', port,
                         os.path.join(util.ROOT, 'bench.py'), '--gpus', '2', '--config', config, '--steps', '3', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-extras', '--no-profile'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline', '--no-extras', '--no-profile'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, lines                      # rank 0 alone prints

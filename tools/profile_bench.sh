@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: the default bench line + rocprofv3 kernel stats + PMC passes around bench.py; outputs under gpurun_out/<tag>_*.
+# GPU box: the full bench line (--full) + rocprofv3 kernel stats + PMC passes around bench.py; outputs as <tag>_* in the folder $O below.
 #   pass 1  --kernel-trace --stats                      per-kernel durations (same command as the bench's timed leg, no event instrumentation)
 #   pass 2  --pmc FETCH_SIZE      pass 3  --pmc WRITE_SIZE       HBM traffic (MI355X_MICROARCH.md: separate passes, FETCH_SIZE x2 on gfx950)
 #   pass 4  --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE      pass 5  --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES (utilisation)
@@ -13,7 +13,7 @@ O=$R/gpurun_out
 B="python3 $R/bench.py $BENCH_ARGS"
 run() { name=$1; shift; echo "== $name"; timeout -k 10 300 "$@" > $O/${TAG}_$name.log 2>&1; rc=$?; if [ $rc -ne 0 ]; then echo "$name rc=$rc"; tail -n 5 $O/${TAG}_$name.log; fi; if [ $rc -eq 124 ] || [ $rc -ge 128 ]; then exit $rc; fi; }
 if [ "$2" != "quick" ]; then
-  echo "== bench"; timeout -k 10 420 $B > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; rc=$?; if [ $rc -eq 124 ] || [ $rc -ge 128 ]; then exit $rc; fi
+  echo "== bench"; timeout -k 10 420 $B --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; rc=$?; if [ $rc -eq 124 ] || [ $rc -ge 128 ]; then exit $rc; fi
 fi
 S="--no-cpu-baseline --no-profile --no-extras"
 run stats rocprofv3 --kernel-trace --stats -d $O/${TAG}_stats -o bench --output-format csv -- $B --steps 10 --warmup 3 $S
