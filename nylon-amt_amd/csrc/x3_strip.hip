@@ -1212,6 +1212,8 @@ static int x3_debug() { static const int v = [] { const char* e = getenv("HFTT_X
 int hftt_x3_strip_linear(const hftt_strip_desc& d0, hipStream_t st) {
   hftt_strip_desc d = d0;
   d.pad = x3_debug();
+  // the tile stores form each lane's row offset with __umul24 (tile_store_rows*): a stride beyond 24 bits would wrap silently
+  HFTT_REQUIRE(d.ldc >= 0 && d.ldc < (1 << 24), "x3_strip_linear: ldc=%lld must be below 2^24 (24-bit row offsets)", (long long)d.ldc);
   if (d.K <= 192 && d.N <= 192) {                     // the small-width family (weights resident in LDS, compact pack): x3s_strip.h
     HFTT_REQUIRE(d.K % 32 == 0 && d.N % 32 == 0 && d.M % 32 == 0 && d.K > 0 && d.N > 0, "x3s_strip_linear: needs K %% 32 == 0, N %% 32 == 0, M %% 32 == 0 (M=%d N=%d K=%d)", d.M, d.N, d.K);
     HFTT_REQUIRE(d.gate == nullptr && !(d.flags & (HFTT_SL_X_BF16 | HFTT_SL_C_BF16 | HFTT_SL_RES_BF16 | HFTT_SL_X3_GRAD_HI | HFTT_SL_C_F16PAIR)),
@@ -1246,6 +1248,8 @@ int hftt_x3_strip_linear(const hftt_strip_desc& d0, hipStream_t st) {
 int hftt_x3_strip_mlp(const hftt_ffn_desc& d0, hipStream_t st) {
   hftt_ffn_desc d = d0;
   d.pad = x3_debug();
+  HFTT_REQUIRE(d.ldh >= 0 && d.ldh < (1 << 24) && d.ldy >= 0 && d.ldy < (1 << 24),
+               "x3_strip_mlp: ldh=%lld / ldy=%lld must be below 2^24 (24-bit row offsets)", (long long)d.ldh, (long long)d.ldy);
   if (d.d == 64 && d.p == 128) {                      // the reference's default width: x3s_strip.h
     HFTT_REQUIRE(d.M % 32 == 0, "x3s_strip_mlp: needs M %% 32 == 0 (M=%d)", d.M);
     HFTT_REQUIRE(!(d.flags & (HFTT_SL_X_BF16 | HFTT_SL_C_BF16 | HFTT_SL_RES_BF16 | HFTT_SL_X3_GRAD_HI)), "x3s_strip_mlp: fp32 tensors, no gradient-rounding form");
@@ -1285,6 +1289,8 @@ int hftt_x3_strip_mlp(const hftt_ffn_desc& d0, hipStream_t st) {
 // hftt_attn_out_ffn_fwd: the fc_o + LayerNorm descriptor and the FFN descriptor of the two launches it replaces, unchanged, with o.C (the
 // LayerNorm-1 output) optional and the two weight streams adjacent (fc_o's 16 slots, then the FFN's 64)
 int hftt_x3_attn_out_ffn(const hftt_strip_desc& o, const hftt_ffn_desc& d, hipStream_t st) {
+  HFTT_REQUIRE(o.ldc >= 0 && o.ldc < (1 << 24) && d.ldh >= 0 && d.ldh < (1 << 24) && d.ldy >= 0 && d.ldy < (1 << 24),
+               "attn_out_ffn_fwd: ldc=%lld / ldh=%lld / ldy=%lld must be below 2^24 (24-bit row offsets)", (long long)o.ldc, (long long)d.ldh, (long long)d.ldy);
   HFTT_REQUIRE(o.M == d.M && o.M > 0 && o.M % 32 == 0 && o.N == 256 && o.K == 256 && d.d == 256 && d.p == 512 && d.mode == 0,
                "attn_out_ffn_fwd: needs M %% 32 == 0, fc_o 256 -> 256, FFN d = 256, p = 512, mode 0 (M=%d/%d N=%d K=%d d=%d p=%d mode=%d)", o.M, d.M, o.N, o.K, d.d, d.p, d.mode);
   HFTT_REQUIRE((o.flags & HFTT_SL_X3_F16) && (d.flags & HFTT_SL_X3_F16) && !((o.flags | d.flags) & (HFTT_SL_X3_BF16 | HFTT_SL_X_BF16 | HFTT_SL_C_BF16 | HFTT_SL_RES_BF16 | HFTT_SL_RELU | HFTT_SL_C_F16PAIR | HFTT_SL_X_DROP | HFTT_SL_X3_GRAD_HI)),

@@ -78,6 +78,29 @@ def test_argument_validation_without_gpu(lib):
     td.seg_dw[0], td.seg_rows[0] = 0x1000, 256
     rc = lib.hftt_gemm_tn(C.byref(td), None)
     assert rc != 0 and b'32-bit quads' in lib.hftt_last_error(), lib.hftt_last_error()
+    # only the npass 4 kernel without HFTT_TN_DY_HI applies the mask while it loads dY: every other form used to run the product unmasked
+    td.M = 1024
+    td.ws_bytes = lib.hftt_gemm_tn_ws_bytes(td.M, td.N, td.K)
+    for npass, flags in ((1, 8), (4, 8 | 4)):                               # HFTT_TN_DY_DROP alone at npass 1; with HFTT_TN_DY_HI at npass 4
+        td.npass, td.io_flags = npass, flags
+        rc = lib.hftt_gemm_tn(C.byref(td), None)
+        assert rc != 0 and b'DY_DROP goes with npass == 4 and without' in lib.hftt_last_error(), (npass, flags, lib.hftt_last_error())
+    # the x3 strip kernels form row offsets with 24-bit multiplies: a store stride of 2^24 or more is refused, not wrapped
+    xs = _capi.StripDesc()
+    xs.M, xs.N, xs.K, xs.flags = 32, 256, 256, 16                           # HFTT_SL_X3_F16
+    xs.x = xs.w = xs.C = 0x1000
+    xs.ldx, xs.ldc = 256, 1 << 24
+    assert lib.hftt_strip_linear(C.byref(xs), None) != 0
+    assert b'ldc=16777216 must be below 2^24' in lib.hftt_last_error(), lib.hftt_last_error()
+    xf = _capi.FfnDesc()
+    xf.M, xf.d, xf.p, xf.mode, xf.flags = 32, 256, 512, 0, 16
+    xf.x = xf.w = xf.y = xf.h_out = xf.ln_gamma = xf.ln_beta = 0x1000
+    xf.ldx, xf.ldy, xf.ldh = 256, 256, 1 << 24
+    assert lib.hftt_ffn_res_ln_fwd(C.byref(xf), None) != 0
+    assert b'ldh=16777216 / ldy=256 must be below 2^24' in lib.hftt_last_error(), lib.hftt_last_error()
+    xf.ldh, xs.ldc = 1024, 1 << 25
+    assert lib.hftt_attn_out_ffn_fwd(C.byref(xs), C.byref(xf), None) != 0
+    assert b'ldc=33554432 / ldh=1024 / ldy=256 must be below 2^24' in lib.hftt_last_error(), lib.hftt_last_error()
     with pytest.raises(_capi.HfttError):
         _capi.check(1, 'x')
 
