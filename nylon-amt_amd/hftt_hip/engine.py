@@ -42,6 +42,13 @@ def keep_scale(p):
     return float(np.float32(256.0) / np.float32(thr)) if thr > 0 else 0.0
 
 
+def attn_fwd8_takes(npass, hb, dh, Lq, Lk, probs):
+    """Does hftt_attn_fwd launch attn_fwd8_kernel for this shape (csrc/attn_fwd8.hip: hftt_attn_fwd8_try)?  hb: q, k, v and out all bf16;
+    probs: the attention map is an output.  HFTT_ATTN_FWD8 is read once per process on the C side."""
+    return (hb and dh == 64 and npass == 1 and 128 < Lk <= 256 and 128 < Lq <= 256 and not probs
+            and os.environ.get('HFTT_ATTN_FWD8', '1')[:1] != '0')
+
+
 def _align(x, a):
     return (x + a - 1) // a * a
 
@@ -750,8 +757,7 @@ class HfttEngine:
                     + 8.0 * n_seq * H * Lq, 'shape': (n_seq, H, Lq, Lk, dh)}
         else:
             hb = 'true' if (flags & 7) == 7 else 'false'
-            long_rows = (hb == 'true' and dh == 64 and self.npass == 1 and 128 < Lk <= 256 and 128 < Lq <= 256 and not probs
-                         and os.environ.get('HFTT_ATTN_FWD8', '1')[:1] != '0')                   # csrc/attn_fwd8.hip: hftt_attn_fwd8_try
+            long_rows = attn_fwd8_takes(self.npass, hb == 'true', dh, Lq, Lk, bool(probs))
             x3name = ('x3p_attn_fwd_kernel<%d, %d, %s, %d>' % (kt, 8 if (kt == 8 and Lq > 128) else 4, 'true' if (probs or map_out) else 'false', dm)) if planes else \
                 ('x3_attn_fwd_kernel<%d, %d, %d, %s>' % (kt, dh, 8 if kt == 8 else 4, 'true' if (probs or map_out) else 'false'))
             meta = {'kernel': 'attn_fwd8_kernel' if long_rows else (x3name if self.npass == 2 else
