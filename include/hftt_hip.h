@@ -40,9 +40,10 @@ int hftt_build_options(void);
 const char* hftt_last_error(void);
 /* ONE PROCESS DRIVES ONE DEVICE (one process per GPU, as torch.distributed launches them): the launchers keep per-kernel state -- dynamic-LDS
  * attributes, the CU count, the resident-workgroup grids of the persistent kernels -- in process-wide caches made for the device of the
- * first launch.  A launch from the same process with another device current returns 3 with a message instead of running with the first
- * device's cached state.  Every entry point may be called from any host thread; launches go to the stream that is passed in. */
-/* number of compute units of the current device (for workspace sizing on the host side) */
+ * first launch.  A launch from the same process with another device current is refused before anything is enqueued: it returns 3 with a
+ * message instead of running with the first device's cached state.  Every entry point may be called from any host thread; launches go to the stream that is passed in. */
+/* number of compute units of the process's device (for workspace sizing on the host side).  Counts as the process's first use of the current
+ * device, as a launch does; -1 (with a message) from another device, or when the device query fails. */
 int hftt_device_cus(void);
 
 /* ---------------------------------------------------------------------------------------------

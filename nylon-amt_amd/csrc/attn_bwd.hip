@@ -10,7 +10,7 @@
 //   * Q and dO blocks (32 rows) are staged per iteration; their transposes are again tr reads of the same image.
 #include <type_traits>
 #include "hftt_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "x3_internal.h"
 #include "../../include/hftt_hip.h"
 #include <math.h>
@@ -515,16 +515,7 @@ __global__ __launch_bounds__(KT * 64, HFTT_AB_WAVES(NPASS, KT, HB)) void attn_bw
 template <int KT, int DH, int NPASS, bool HB>
 int launch_ab(const hftt_attn_desc& d, hipStream_t st) {
   using Cfg = AbCfg<KT, DH, NPASS>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<KT, DH, NPASS, HB>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-    if (e != hipSuccess) { hftt_set_error("attn_bwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return 2; }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((attn_bwd_kernel<KT, DH, NPASS, HB>), dim3((unsigned)(d.n_seq * d.n_heads)), dim3(Cfg::NTHR), Cfg::LDS_BYTES, st, d);
-  HFTT_CHECK_LAUNCH("attn_bwd");
-  return 0;
+  return hftt_launch<attn_bwd_kernel<KT, DH, NPASS, HB>>("attn_bwd", dim3((unsigned)(d.n_seq * d.n_heads)), dim3(Cfg::NTHR), Cfg::LDS_BYTES, st, d);
 }
 
 template <int DH, int NPASS, bool HB>

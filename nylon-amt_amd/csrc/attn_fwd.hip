@@ -8,7 +8,7 @@
 //   probe T4), V fragments come from the row-major LDS image through ds_read_b64_tr_b16 (probe T5).
 #include <type_traits>
 #include "hftt_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "x3_internal.h"
 #include "../../include/hftt_hip.h"
 #include <math.h>
@@ -367,16 +367,7 @@ __global__ __launch_bounds__(256, (NPASS == 3 ? 1 : 2)) void attn_fwd_kernel(con
 template <int KT, int DH, int NPASS, bool HB>
 int launch_af(const hftt_attn_desc& d, hipStream_t st) {
   using Cfg = AfCfg<KT, DH, NPASS>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<KT, DH, NPASS, HB>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-    if (e != hipSuccess) { hftt_set_error("attn_fwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return 2; }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((attn_fwd_kernel<KT, DH, NPASS, HB>), dim3((unsigned)(d.n_seq * d.n_heads)), dim3(256), Cfg::LDS_BYTES, st, d);
-  HFTT_CHECK_LAUNCH("attn_fwd");
-  return 0;
+  return hftt_launch<attn_fwd_kernel<KT, DH, NPASS, HB>>("attn_fwd", dim3((unsigned)(d.n_seq * d.n_heads)), dim3(256), Cfg::LDS_BYTES, st, d);
 }
 
 template <int DH, int NPASS, bool HB>

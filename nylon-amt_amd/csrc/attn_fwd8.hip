@@ -13,7 +13,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "hftt_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "x3_internal.h"
 #include "../../include/hftt_hip.h"
 #include <math.h>
@@ -200,13 +200,5 @@ int hftt_attn_fwd8_try(const hftt_attn_desc& d, hipStream_t st) {
   if (enabled < 0) { const char* e = getenv("HFTT_ATTN_FWD8"); enabled = !(e && e[0] == '0'); }
   if (!enabled || d.npass != 1 || d.dh != 64 || d.probs != nullptr || !hftt_attn_hb_form(d)) return -1;
   if (d.Lk <= 128 || d.Lk > 256 || d.Lq <= 128 || d.Lq > 256) return -1;                 // long rows, and enough query blocks for the 8 waves
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES8);
-    if (e != hipSuccess) { hftt_set_error("attn_fwd8: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return 2; }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(attn_fwd8_kernel, dim3((unsigned)(d.n_seq * d.n_heads)), dim3(512), LDS_BYTES8, st, d);
-  HFTT_CHECK_LAUNCH("attn_fwd8");
-  return 0;
+  return hftt_launch<attn_fwd8_kernel>("attn_fwd8", dim3((unsigned)(d.n_seq * d.n_heads)), dim3(512), LDS_BYTES8, st, d);
 }

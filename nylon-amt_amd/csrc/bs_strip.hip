@@ -16,7 +16,7 @@
 #include <type_traits>
 #include <utility>
 #include "hftt_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "strip_internal.h"
 #include "../../include/hftt_hip.h"
 
@@ -312,45 +312,18 @@ __global__ __launch_bounds__(256, 2) void bs_mlp_kernel(const hftt_ffn_desc g) {
   }
 }
 
-int bs_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-    n = prop.multiProcessorCount;
-  }
-  return n;
-}
-template <typename K>
-int bs_set_lds(K kernel, int lds, const char* what) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) { hftt_set_error("%s: hipFuncSetAttribute(%d B LDS) failed: %s", what, lds, hipGetErrorString(e)); return 2; }
-  return 0;
-}
 template <int K32, int NT, bool LN, bool HR>
 int launch_bs(const hftt_strip_desc& d, hipStream_t st) {
   using Cfg = BsCfg<K32, NT, LN>;
-  static bool attr = false;
-  if (!attr) { if (int rc = bs_set_lds(bs_linear_kernel<K32, NT, LN, HR>, Cfg::LDS, "bs_strip_linear")) return rc; attr = true; }
-  const int cus = bs_cus();
-  if (cus <= 0) { hftt_set_error("bs_strip_linear: device query failed"); return 2; }
-  const long nblk = ((long)d.M + 127) / 128;
-  const long cap = 2L * cus;
-  hipLaunchKernelGGL((bs_linear_kernel<K32, NT, LN, HR>), dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(256), Cfg::LDS, st, d);
-  HFTT_CHECK_LAUNCH("bs_strip_linear");
-  return 0;
+  const long grid = hftt_persistent_grid("bs_strip_linear", ((long)d.M + 127) / 128, 2);
+  if (grid < 0) return 2;
+  return hftt_launch<bs_linear_kernel<K32, NT, LN, HR>>("bs_strip_linear", dim3((unsigned)grid), dim3(256), Cfg::LDS, st, d);
 }
 template <int MODE>
 int launch_bsm(const hftt_ffn_desc& d, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) { if (int rc = bs_set_lds(bs_mlp_kernel<MODE>, BSM_LDS, "bs_strip_mlp")) return rc; attr = true; }
-  const int cus = bs_cus();
-  if (cus <= 0) { hftt_set_error("bs_strip_mlp: device query failed"); return 2; }
-  const long nblk = ((long)d.M + 127) / 128;
-  hipLaunchKernelGGL((bs_mlp_kernel<MODE>), dim3((unsigned)(nblk < 2L * cus ? nblk : 2L * cus)), dim3(256), BSM_LDS, st, d);
-  HFTT_CHECK_LAUNCH("bs_strip_mlp");
-  return 0;
+  const long grid = hftt_persistent_grid("bs_strip_mlp", ((long)d.M + 127) / 128, 2);
+  if (grid < 0) return 2;
+  return hftt_launch<bs_mlp_kernel<MODE>>("bs_strip_mlp", dim3((unsigned)grid), dim3(256), BSM_LDS, st, d);
 }
 
 }  // namespace

@@ -4,7 +4,7 @@
 #include <atomic>
 #include <stdio.h>
 #include "../../include/hftt_hip.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 
 static thread_local char g_err[512] = "";
 
@@ -18,7 +18,7 @@ void hftt_set_error(const char* fmt, ...) {
 int hftt_device_guard(const char* what) {
   static std::atomic<int> first{-1};
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;      // (the launch check in front of this has already reported a broken runtime)
+  if (hipGetDevice(&dev) != hipSuccess) return 0;      // (a broken runtime is reported by the launch check behind this)
   int seen = -1;
   if (first.compare_exchange_strong(seen, dev) || seen == dev) return 0;
   hftt_set_error("%s: this process launched on device %d before and is now on device %d -- one process drives one device (the launch "
@@ -36,10 +36,15 @@ extern "C" int hftt_build_options(void) {
   return 0;
 #endif
 }
-extern "C" int hftt_device_cus(void) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return -1;
-  hipDeviceProp_t p;
-  if (hipGetDeviceProperties(&p, dev) != hipSuccess) return -1;
-  return p.multiProcessorCount;
+int hftt_cus() {
+  static std::atomic<int> n{0};
+  if (n.load(std::memory_order_relaxed) == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
+    n.store(prop.multiProcessorCount, std::memory_order_relaxed);
+  }
+  return n.load(std::memory_order_relaxed);
 }
+// behind the guard like a launch: the count it returns (and caches for the launchers) is the count of the process's one device
+extern "C" int hftt_device_cus(void) { return hftt_device_guard("device_cus") != 0 ? -1 : hftt_cus(); }

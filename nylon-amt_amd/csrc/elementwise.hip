@@ -4,7 +4,7 @@
 // deterministic (no float atomics).  Entry points and reference citations: include/hftt_hip.h.
 #include "hftt_common.h"
 #include "x3_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "../../include/hftt_hip.h"
 #include <math.h>
 
@@ -864,41 +864,30 @@ inline int grid_for(long work_items, int block, int cap = 4096) {
 extern "C" int hftt_prep_weights(const float* params, uint16_t* wbf, float* wf32, float* fdst,
                                  const hftt_prep_entry* table_dev, int n_entries, void* stream) {
   HFTT_REQUIRE(params && (wbf || wf32 || fdst) && table_dev && n_entries > 0, "prep_weights: null operand");
-  hipLaunchKernelGGL(prep_weights_kernel, dim3((unsigned)n_entries, 48), dim3(256), 0, (hipStream_t)stream, params, wbf, wf32, fdst, table_dev);
-  HFTT_CHECK_LAUNCH("prep_weights");
-  return 0;
+  return hftt_launch<prep_weights_kernel>("prep_weights", dim3((unsigned)n_entries, 48), dim3(256), 0, (hipStream_t)stream, params, wbf, wf32, fdst, table_dev);
 }
 
 extern "C" int hftt_prep_weights_x3(const float* params, uint16_t* whi, uint16_t* wlo, float* fdst,
                                     const hftt_prep_entry* table_dev, int n_entries, void* stream) {
   HFTT_REQUIRE(params && whi && wlo && table_dev && n_entries > 0, "prep_weights_x3: null operand");
-  hipLaunchKernelGGL(prep_weights_x3_kernel, dim3((unsigned)n_entries, 48), dim3(256), 0, (hipStream_t)stream, params, whi, wlo, fdst, table_dev);
-  HFTT_CHECK_LAUNCH("prep_weights_x3");
-  return 0;
+  return hftt_launch<prep_weights_x3_kernel>("prep_weights_x3", dim3((unsigned)n_entries, 48), dim3(256), 0, (hipStream_t)stream, params, whi, wlo, fdst, table_dev);
 }
 
 extern "C" int hftt_embed_fold_fwd(const hftt_fold_desc* d, void* stream) {
   HFTT_REQUIRE(d && d->wconv && d->bconv && d->wtok && d->btok && (d->weff_bf || d->weff_f32 || d->weff_hi) && d->beff, "embed_fold_fwd: null operand");
   HFTT_REQUIRE((d->weff_hi == nullptr) == (d->weff_lo == nullptr), "embed_fold_fwd: the split planes come as a pair");
   HFTT_REQUIRE(d->Kp % 32 == 0 && d->Kp >= d->n_proc && d->d_pad >= d->d && d->n_proc >= d->kw, "embed_fold_fwd: bad shape");
-  hipLaunchKernelGGL(fold_fwd_kernel, dim3(grid_for((long)d->d_pad * d->Kp, 256)), dim3(256), 0, (hipStream_t)stream, *d);
-  HFTT_CHECK_LAUNCH("embed_fold_fwd");
-  return 0;
+  return hftt_launch<fold_fwd_kernel>("embed_fold_fwd", dim3(grid_for((long)d->d_pad * d->Kp, 256)), dim3(256), 0, (hipStream_t)stream, *d);
 }
 extern "C" int hftt_embed_fold_bwd(const hftt_fold_desc* d, void* stream) {
   HFTT_REQUIRE(d && d->dweff && d->dbeff && d->g_wconv && d->g_bconv && d->g_wtok && d->g_btok, "embed_fold_bwd: null operand");
   const int nw = d->n_proc - d->kw + 1;
-  hipLaunchKernelGGL(fold_bwd_tok_kernel, dim3(grid_for((long)d->d * d->C * nw, 256)), dim3(256), 0, (hipStream_t)stream, *d);
-  HFTT_CHECK_LAUNCH("embed_fold_bwd(tok)");
-  hipLaunchKernelGGL(fold_bwd_conv_kernel, dim3((unsigned)(d->C * d->kw + d->C)), dim3(256), 0, (hipStream_t)stream, *d);
-  HFTT_CHECK_LAUNCH("embed_fold_bwd(conv)");
-  return 0;
+  if (int rc = hftt_launch<fold_bwd_tok_kernel>("embed_fold_bwd(tok)", dim3(grid_for((long)d->d * d->C * nw, 256)), dim3(256), 0, (hipStream_t)stream, *d)) return rc;
+  return hftt_launch<fold_bwd_conv_kernel>("embed_fold_bwd(conv)", dim3((unsigned)(d->C * d->kw + d->C)), dim3(256), 0, (hipStream_t)stream, *d);
 }
 extern "C" int hftt_im2win(const float* spec, float* win, int32_t B, int32_t F, int32_t T, int32_t n_proc, int32_t Kp, void* stream) {
   HFTT_REQUIRE(spec && win && B > 0 && F > 0 && T > 0 && n_proc > 0 && Kp % 4 == 0 && Kp >= n_proc, "im2win: bad arguments");
-  hipLaunchKernelGGL(im2win_kernel, dim3(grid_for((long)B * T * F * (Kp / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream, spec, win, B, F, T, n_proc, Kp);
-  HFTT_CHECK_LAUNCH("im2win");
-  return 0;
+  return hftt_launch<im2win_kernel>("im2win", dim3(grid_for((long)B * T * F * (Kp / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream, spec, win, B, F, T, n_proc, Kp);
 }
 
 extern "C" int32_t hftt_ln_bwd_wgs(int32_t M) {
@@ -914,74 +903,57 @@ extern "C" int hftt_ln_bwd(const hftt_ln_bwd_desc* d, void* stream) {
   const uint32_t all_bf = HFTT_LNB_DY_BF16 | HFTT_LNB_DR_BF16 | HFTT_LNB_R_BF16;
   const bool fast = d->N == 256 && (d->io_flags & all_bf) == all_bf && (d->dr_drop == nullptr || d->drop_bf16) &&
                     ((((uintptr_t)d->dy | (uintptr_t)d->r | (uintptr_t)d->dr | (uintptr_t)d->dr_drop) & 15) == 0);
-  if (fast) hipLaunchKernelGGL(ln_bwd256_bf16_kernel, dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
-  else if (d->N == 256 && ((((uintptr_t)d->dy | (uintptr_t)d->r | (uintptr_t)d->dr | (uintptr_t)d->dr_drop | (uintptr_t)d->gamma) & 15) == 0))
-    hipLaunchKernelGGL((ln_bwd256_rows_kernel<2, true>), dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
-  else if (d->N == 256) hipLaunchKernelGGL(ln_bwd_kernel<4>, dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
-  else if (d->N == 128) hipLaunchKernelGGL(ln_bwd_kernel<2>, dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
-  else if (((((uintptr_t)d->dy | (uintptr_t)d->r | (uintptr_t)d->dr | (uintptr_t)d->dr_drop | (uintptr_t)d->gamma) & 15) == 0))
-    hipLaunchKernelGGL(ln_bwd64_kernel, dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
-  else hipLaunchKernelGGL(ln_bwd_kernel<1>, dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
-  HFTT_CHECK_LAUNCH("ln_bwd");
-  return 0;
+  if (fast) return hftt_launch<ln_bwd256_bf16_kernel>("ln_bwd", dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
+  if (d->N == 256 && ((((uintptr_t)d->dy | (uintptr_t)d->r | (uintptr_t)d->dr | (uintptr_t)d->dr_drop | (uintptr_t)d->gamma) & 15) == 0))
+    return hftt_launch<ln_bwd256_rows_kernel<2, true>>("ln_bwd", dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
+  if (d->N == 256) return hftt_launch<ln_bwd_kernel<4>>("ln_bwd", dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
+  if (d->N == 128) return hftt_launch<ln_bwd_kernel<2>>("ln_bwd", dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
+  if (((((uintptr_t)d->dy | (uintptr_t)d->r | (uintptr_t)d->dr | (uintptr_t)d->dr_drop | (uintptr_t)d->gamma) & 15) == 0))
+    return hftt_launch<ln_bwd64_kernel>("ln_bwd", dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
+  return hftt_launch<ln_bwd_kernel<1>>("ln_bwd", dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
 }
 extern "C" int hftt_ln_bwd_reduce(const float* ws, int32_t n_wg, int32_t N, float* dgamma, float* dbeta, float beta, void* stream) {
   HFTT_REQUIRE(ws && dgamma && dbeta && n_wg > 0 && N > 0, "ln_bwd_reduce: bad arguments");
-  hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((2 * N + 15) / 16), dim3(256), 0, (hipStream_t)stream, ws, n_wg, N, dgamma, dbeta, beta);
-  HFTT_CHECK_LAUNCH("ln_bwd_reduce");
-  return 0;
+  return hftt_launch<ln_bwd_reduce_kernel>("ln_bwd_reduce", dim3((2 * N + 15) / 16), dim3(256), 0, (hipStream_t)stream, ws, n_wg, N, dgamma, dbeta, beta);
 }
 
 extern "C" int hftt_time_embed_fwd(const float* x, const float* pos, float* y, int32_t B, int32_t T, int32_t Nn, int32_t d,
                                    float scale, float drop_p, uint32_t site, uint64_t seed, uint32_t io_flags, void* stream) {
   HFTT_REQUIRE(x && pos && y && d % 4 == 0, "time_embed_fwd: bad arguments");
-  hipLaunchKernelGGL(time_embed_fwd_kernel, dim3(grid_for((long)B * T * Nn * (d / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream,
-                     x, pos, y, B, T, Nn, d, scale, drop_p, site, seed, io_flags);
-  HFTT_CHECK_LAUNCH("time_embed_fwd");
-  return 0;
+  return hftt_launch<time_embed_fwd_kernel>("time_embed_fwd", dim3(grid_for((long)B * T * Nn * (d / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream,
+                                                              x, pos, y, B, T, Nn, d, scale, drop_p, site, seed, io_flags);
 }
 extern "C" int hftt_time_embed_bwd(const float* dy, float* dx, float* dym, int32_t B, int32_t T, int32_t Nn, int32_t d,
                                    float scale, float drop_p, uint32_t site, uint64_t seed, int32_t accumulate, uint32_t io_flags, void* stream) {
   HFTT_REQUIRE(dy && dx && d % 4 == 0, "time_embed_bwd: bad arguments");
-  hipLaunchKernelGGL(time_embed_bwd_kernel, dim3(grid_for((long)B * T * Nn * (d / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream,
-                     dy, dx, dym, B, T, Nn, d, scale, drop_p, site, seed, accumulate, io_flags);
-  HFTT_CHECK_LAUNCH("time_embed_bwd");
-  return 0;
+  return hftt_launch<time_embed_bwd_kernel>("time_embed_bwd", dim3(grid_for((long)B * T * Nn * (d / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream,
+                                                              dy, dx, dym, B, T, Nn, d, scale, drop_p, site, seed, accumulate, io_flags);
 }
 extern "C" int hftt_dropout_bwd(float* g, int64_t n, float drop_p, uint32_t site, uint64_t seed, uint32_t bf16, void* stream) {
   HFTT_REQUIRE(g && n > 0 && n % 4 == 0 && drop_p >= 0.f && drop_p < 1.f && ((uintptr_t)g & 15) == 0, "dropout_bwd: bad arguments (n %% 4 == 0, 16-byte aligned)");
   if (drop_p == 0.f) return 0;
-  hipLaunchKernelGGL(dropout_bwd_kernel, dim3(grid_for(n / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, g, (long)n, drop_p, site, seed, bf16);
-  HFTT_CHECK_LAUNCH("dropout_bwd");
-  return 0;
+  return hftt_launch<dropout_bwd_kernel>("dropout_bwd", dim3(grid_for(n / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, g, (long)n, drop_p, site, seed, bf16);
 }
 extern "C" int64_t hftt_colsum_ws_bytes(int64_t rows, int64_t n) { (void)rows; return (int64_t)CS_SPLITS * n * 4; }
 extern "C" int hftt_colsum(const float* x, int64_t rows, int64_t n, int64_t ld, float* out, float beta, float* ws, uint32_t x_bf16, void* stream) {
   HFTT_REQUIRE(x && out && ws && rows > 0 && n > 0 && ld >= n, "colsum: bad arguments");
-  hipLaunchKernelGGL(colsum_stage1_kernel, dim3((unsigned)((n + 255) / 256), CS_SPLITS), dim3(256), 0, (hipStream_t)stream, x, (long)rows, (long)n, (long)ld, ws, x_bf16);
-  HFTT_CHECK_LAUNCH("colsum(1)");
-  hipLaunchKernelGGL(colsum_stage2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, (long)n, out, beta);
-  HFTT_CHECK_LAUNCH("colsum(2)");
-  return 0;
+  if (int rc = hftt_launch<colsum_stage1_kernel>("colsum(1)", dim3((unsigned)((n + 255) / 256), CS_SPLITS), dim3(256), 0, (hipStream_t)stream, x, (long)rows, (long)n, (long)ld, ws, x_bf16)) return rc;
+  return hftt_launch<colsum_stage2_kernel>("colsum(2)", dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, (long)n, out, beta);
 }
 extern "C" int hftt_heads_split(const float* logits, int64_t ldl, float* onset, float* offset, float* mpe, float* velocity,
                                 int32_t B, int32_t T, int32_t Nn, int32_t V, int32_t time_major, void* stream) {
   HFTT_REQUIRE(logits && onset && offset && mpe && velocity, "heads_split: null operand");
   HFTT_REQUIRE(V % 4 == 0 && ldl % 4 == 0 && ldl >= V + 3, "heads_split: V=%d / ldl=%ld unsupported", V, (long)ldl);
-  hipLaunchKernelGGL(heads_split_kernel, dim3(grid_for((long)B * T * Nn * (V / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream,
-                     logits, (long)ldl, onset, offset, mpe, velocity, B, T, Nn, V, time_major);
-  HFTT_CHECK_LAUNCH("heads_split");
-  return 0;
+  return hftt_launch<heads_split_kernel>("heads_split", dim3(grid_for((long)B * T * Nn * (V / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream,
+                                                        logits, (long)ldl, onset, offset, mpe, velocity, B, T, Nn, V, time_major);
 }
 extern "C" int hftt_heads_split_bwd(const float* p_onset, const float* p_offset, const float* p_mpe,
                                     const float* d_onset, const float* d_offset, const float* d_mpe, const float* d_velocity,
                                     float* dlogits, int64_t ldl, int32_t B, int32_t T, int32_t Nn, int32_t V, int32_t time_major, void* stream) {
   HFTT_REQUIRE(p_onset && p_offset && p_mpe && d_onset && d_offset && d_mpe && d_velocity && dlogits, "heads_split_bwd: null operand");
   HFTT_REQUIRE(V % 4 == 0 && ldl % 4 == 0 && ldl >= V + 4, "heads_split_bwd: V=%d / ldl=%ld unsupported", V, (long)ldl);
-  hipLaunchKernelGGL(heads_split_bwd_kernel, dim3(grid_for((long)B * T * Nn * (ldl / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream,
-                     p_onset, p_offset, p_mpe, d_onset, d_offset, d_mpe, d_velocity, dlogits, (long)ldl, B, T, Nn, V, time_major);
-  HFTT_CHECK_LAUNCH("heads_split_bwd");
-  return 0;
+  return hftt_launch<heads_split_bwd_kernel>("heads_split_bwd", dim3(grid_for((long)B * T * Nn * (ldl / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream,
+                                                                p_onset, p_offset, p_mpe, d_onset, d_offset, d_mpe, d_velocity, dlogits, (long)ldl, B, T, Nn, V, time_major);
 }
 
 extern "C" int64_t hftt_loss_ws_bytes(int64_t n) { (void)n; return (int64_t)LOSS_WGS * 8 * 4; }
@@ -993,12 +965,9 @@ extern "C" int hftt_loss(const hftt_loss_desc* d, void* stream) {
   const bool v4 = d->V <= 128 && d->V % 4 == 0 && (((uintptr_t)d->vel[0] | (uintptr_t)d->vel[1] | (uintptr_t)d->d_vel[0] | (uintptr_t)d->d_vel[1]) & 15) == 0;
   if (v4) wgs = (int)((d->n + 7) / 8);
   if (wgs > LOSS_WGS) wgs = LOSS_WGS;
-  if (v4) hipLaunchKernelGGL(loss_v4_kernel, dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
-  else hipLaunchKernelGGL(loss_kernel, dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d);
-  HFTT_CHECK_LAUNCH("loss");
-  hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *d, wgs);
-  HFTT_CHECK_LAUNCH("loss_reduce");
-  return 0;
+  if (int rc = v4 ? hftt_launch<loss_v4_kernel>("loss", dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d)
+                  : hftt_launch<loss_kernel>("loss", dim3(wgs), dim3(256), 0, (hipStream_t)stream, *d)) return rc;
+  return hftt_launch<loss_reduce_kernel>("loss_reduce", dim3(1), dim3(256), 0, (hipStream_t)stream, *d, wgs);
 }
 
 extern "C" int hftt_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int32_t step,
@@ -1011,8 +980,6 @@ extern "C" int hftt_adam_step(float* p, const float* g, float* m, float* v, int6
   const double bc2 = 1.0 - pow(beta2, (double)step);
   const float lr_c = (float)(lr / bc1);
   const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
-                     lr_c, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, inv_sqrt_bc2, (float)grad_scale);
-  HFTT_CHECK_LAUNCH("adam_step");
-  return 0;
+  return hftt_launch<adam_kernel>("adam_step", dim3(grid_for(n / 4 + 1, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
+                                               lr_c, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, inv_sqrt_bc2, (float)grad_scale);
 }

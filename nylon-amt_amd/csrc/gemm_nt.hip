@@ -10,7 +10,7 @@
 #include <type_traits>
 #include "hftt_common.h"
 #include "x3_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "../../include/hftt_hip.h"
 
 namespace {
@@ -646,27 +646,9 @@ template <int APF, bool DBUF, bool ABF>
 int launch_nt_as(const hftt_gemm_nt_desc& d, hipStream_t st) {
   const int lds = ((DBUF ? 2 : 1) * 32 * (d.K + 8) + 2 * 256 * 40) * 2;
   if (lds > 160 * 1024) { hftt_set_error("gemm_nt: K=%d too large for the A-stationary tile (%d B LDS)", d.K, lds); return 1; }
-  static int attr_lds = 0;
-  if (lds > attr_lds) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_as_kernel<APF, DBUF, ABF>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) { hftt_set_error("gemm_nt: hipFuncSetAttribute(%d B LDS) failed: %s", lds, hipGetErrorString(e)); return 2; }
-    attr_lds = lds;
-  }
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { hftt_set_error("gemm_nt: device query failed"); return 2; }
-    n_cu = prop.multiProcessorCount;
-  }
-  const long nblk = ((long)d.M + 31) / 32;
-  const int per_cu = (lds <= 80 * 1024) ? 2 : 1;
-  long grid = (long)n_cu * per_cu;
-  if (grid > nblk) grid = nblk;
-  hipLaunchKernelGGL((gemm_nt_as_kernel<APF, DBUF, ABF>), dim3((unsigned)grid), dim3(512), lds, st, d);
-  HFTT_CHECK_LAUNCH("gemm_nt");
-  return 0;
+  const long grid = hftt_persistent_grid("gemm_nt", ((long)d.M + 31) / 32, (lds <= 80 * 1024) ? 2 : 1);
+  if (grid < 0) return 2;
+  return hftt_launch<gemm_nt_as_kernel<APF, DBUF, ABF>>("gemm_nt", dim3((unsigned)grid), dim3(512), lds, st, d);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -989,17 +971,8 @@ int launch_nt_as1(const hftt_gemm_nt_desc& d, hipStream_t st) {
   int lds = (BM_ * (d.K + 8) + 2 * 256 * 40) * 2;
   const int stage = BM_ * 260 * 4;
   if (MODE == 1 && stage > lds) lds = stage;
-  static int attr_lds = 0;
-  if (lds > attr_lds) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_as1_kernel<BM_, MODE, EW, PF>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) { hftt_set_error("gemm_nt: hipFuncSetAttribute(%d B LDS) failed: %s", lds, hipGetErrorString(e)); return 2; }
-    attr_lds = lds;
-  }
   dim3 grid((unsigned)((d.M + BM_ - 1) / BM_), 1, 1);
-  hipLaunchKernelGGL((gemm_nt_as1_kernel<BM_, MODE, EW, PF>), grid, dim3(512), lds, st, d);
-  HFTT_CHECK_LAUNCH("gemm_nt");
-  return 0;
+  return hftt_launch<gemm_nt_as1_kernel<BM_, MODE, EW, PF>>("gemm_nt", grid, dim3(512), lds, st, d);
 }
 
 template <int BN, int PREC, bool LN>
@@ -1007,18 +980,9 @@ int launch_nt(const hftt_gemm_nt_desc& d, hipStream_t st) {
   using Cfg = NtCfg<BN, PREC>;
   int lds = Cfg::LOOP_BYTES;
   if ((LN || (Cfg::X3M && BN == 256)) && Cfg::STAGE_BYTES > lds) lds = Cfg::STAGE_BYTES;      // (split modes: the row-pass epilogue stages the tile)
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<BN, PREC, LN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) { hftt_set_error("gemm_nt: hipFuncSetAttribute(%d B LDS) failed: %s", lds, hipGetErrorString(e)); return 2; }
-    attr_set = true;
-  }
   const int n_pad = ((d.N + 63) / 64) * 64;
   dim3 grid((unsigned)((d.M + BM - 1) / BM), (unsigned)((n_pad + BN - 1) / BN), 1);
-  hipLaunchKernelGGL((gemm_nt_kernel<BN, PREC, LN>), grid, dim3(512), lds, st, d);
-  HFTT_CHECK_LAUNCH("gemm_nt");
-  return 0;
+  return hftt_launch<gemm_nt_kernel<BN, PREC, LN>>("gemm_nt", grid, dim3(512), lds, st, d);
 }
 
 template <int PREC>

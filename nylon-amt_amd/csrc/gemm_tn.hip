@@ -12,7 +12,7 @@
 #include <stdlib.h>
 #include "hftt_common.h"
 #include "x3_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "../../include/hftt_hip.h"
 
 namespace {
@@ -496,19 +496,10 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_small_kernel(const hftt_ge
 template <int TM, int TN, int NPASS, bool DYB, bool XB>
 int launch_tn(const hftt_gemm_tn_desc& d, const TnPlan& p, hipStream_t st) {
   using Cfg = TnCfg<TM, TN, NPASS, DYB, XB>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_kernel<TM, TN, NPASS, DYB, XB>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-    if (e != hipSuccess) { hftt_set_error("gemm_tn: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return 2; }
-    attr_set = true;
-  }
   const int tiles = p.n_tiles * p.k_tiles;
   dim3 grid((unsigned)(((p.splits + 7) / 8) * 8 * tiles), 1, 1);
-  hipLaunchKernelGGL((gemm_tn_kernel<TM, TN, NPASS, DYB, XB>), grid, dim3(512), Cfg::LDS_BYTES, st, d, p.k_tiles, p.rows_per_split, p.nws, p.kws,
-                     tiles, p.splits);
-  HFTT_CHECK_LAUNCH("gemm_tn");
-  return 0;
+  return hftt_launch<gemm_tn_kernel<TM, TN, NPASS, DYB, XB>>("gemm_tn", grid, dim3(512), Cfg::LDS_BYTES, st, d, p.k_tiles, p.rows_per_split, p.nws, p.kws,
+                                                             tiles, p.splits);
 }
 
 }  // namespace
@@ -597,13 +588,9 @@ extern "C" int hftt_gemm_tn(const hftt_gemm_tn_desc* d, void* stream) {
   const int bias_blocks = (d->N + 3) / 4;
   if (total <= 65536 && p.splits >= 32) {             // small output, many partial tiles: the wide reduce
     const int blocks = (int)((total + 15) / 16);
-    hipLaunchKernelGGL(gemm_tn_reduce_small_kernel, dim3(blocks + bias_blocks), dim3(256), 0, st, *d, p.splits, p.nws, p.kws, blocks);
-    HFTT_CHECK_LAUNCH("gemm_tn_reduce");
-    return 0;
+    return hftt_launch<gemm_tn_reduce_small_kernel>("gemm_tn_reduce", dim3(blocks + bias_blocks), dim3(256), 0, st, *d, p.splits, p.nws, p.kws, blocks);
   }
   int blocks = (int)((total + 255) / 256);
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3(blocks + bias_blocks), dim3(256), 0, st, *d, p.splits, p.nws, p.kws, blocks);
-  HFTT_CHECK_LAUNCH("gemm_tn_reduce");
-  return 0;
+  return hftt_launch<gemm_tn_reduce_kernel>("gemm_tn_reduce", dim3(blocks + bias_blocks), dim3(256), 0, st, *d, p.splits, p.nws, p.kws, blocks);
 }

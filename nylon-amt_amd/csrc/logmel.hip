@@ -3,7 +3,7 @@
 //   -> sparse slaney/htk mel filterbank (CSR by mel: ~2k non-zeros of 1025x256) -> log(. + offset)
 // Replaces torchaudio MelSpectrogram + log of AMT.wav2feature (model/amt.py:59-61); see include/hftt_hip.h.
 #include "hftt_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "../../include/hftt_hip.h"
 
 namespace {
@@ -127,9 +127,7 @@ extern "C" int hftt_resample(const hftt_resample_desc* d, void* stream) {
   HFTT_REQUIRE(d->n_out <= (d->n_in * d->up + d->down - 1) / d->down, "resample: n_out exceeds ceil(n_in * up / down)");
   const long wlen = (long)(255 / d->up + 1) * d->down + d->taps;      // the input window of 256 consecutive outputs, staged in LDS
   HFTT_REQUIRE(wlen * 4 <= 64 * 1024, "resample: the input window of one workgroup (%ld samples at down = %d, taps = %d) exceeds 64 KB of LDS", wlen, d->down, d->taps);
-  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((d->n_out + 255) / 256)), dim3(256), (size_t)wlen * 4, (hipStream_t)stream, *d);
-  HFTT_CHECK_LAUNCH("resample");
-  return 0;
+  return hftt_launch<resample_kernel>("resample", dim3((unsigned)((d->n_out + 255) / 256)), dim3(256), (int)(wlen * 4), (hipStream_t)stream, *d);
 }
 
 extern "C" int hftt_logmel(const hftt_logmel_desc* d, void* stream) {
@@ -137,7 +135,5 @@ extern "C" int hftt_logmel(const hftt_logmel_desc* d, void* stream) {
   HFTT_REQUIRE(d->n_fft == 2048, "logmel: n_fft=%d unsupported (2048 only)", d->n_fft);
   HFTT_REQUIRE(d->hop > 0 && d->n_mels > 0 && d->n_frames > 0 && d->n_samples > 0, "logmel: bad shape");
   HFTT_REQUIRE(d->n_frames == 1 + d->n_samples / d->hop, "logmel: n_frames must be 1 + n_samples/hop");
-  hipLaunchKernelGGL((logmel_kernel<2048>), dim3((unsigned)d->n_frames), dim3(256), 0, (hipStream_t)stream, *d);
-  HFTT_CHECK_LAUNCH("logmel");
-  return 0;
+  return hftt_launch<logmel_kernel<2048>>("logmel", dim3((unsigned)d->n_frames), dim3(256), 0, (hipStream_t)stream, *d);
 }

@@ -15,7 +15,7 @@
 //     stores) overlaps the other's MFMA phase.
 #include <stdlib.h>
 #include "hftt_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "strip_internal.h"
 #include "x3_internal.h"
 #include "../../include/hftt_hip.h"
@@ -561,13 +561,6 @@ __global__ __launch_bounds__(256, 2) void strip_mlp_kernel(const hftt_ffn_desc g
   }
 }
 
-template <typename K>
-int set_lds(K kernel, int lds, const char* what) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) { hftt_set_error("%s: hipFuncSetAttribute(%d B LDS) failed: %s", what, lds, hipGetErrorString(e)); return 2; }
-  return 0;
-}
-
 #ifdef HFTT_STRIP_ABLATE
 int ablate_bits() { const char* e = getenv("HFTT_STRIP_ABLATE"); return e ? atoi(e) : 0; }
 #endif
@@ -579,11 +572,7 @@ int launch_linear(const hftt_strip_desc& d0, hipStream_t st) {
   d.pad = ablate_bits();
 #endif
   const int lds = RING_BYTES + 4 * (d.N + 512);
-  static int attr = 0;
-  if (lds > attr) { if (int rc = set_lds(strip_linear_kernel<XBF, CBF, LN>, lds, "strip_linear")) return rc; attr = lds; }
-  hipLaunchKernelGGL((strip_linear_kernel<XBF, CBF, LN>), dim3((unsigned)((d.M + 127) / 128)), dim3(256), lds, st, d);
-  HFTT_CHECK_LAUNCH("strip_linear");
-  return 0;
+  return hftt_launch<strip_linear_kernel<XBF, CBF, LN>>("strip_linear", dim3((unsigned)((d.M + 127) / 128)), dim3(256), lds, st, d);
 }
 template <int MODE>
 int launch_mlp(const hftt_ffn_desc& d0, hipStream_t st) {
@@ -592,11 +581,7 @@ int launch_mlp(const hftt_ffn_desc& d0, hipStream_t st) {
   d.pad = ablate_bits();
 #endif
   const int lds = RING_BYTES + 4 * (d.p + 768);
-  static int attr = 0;
-  if (lds > attr) { if (int rc = set_lds(strip_mlp_kernel<MODE>, lds, "strip_mlp")) return rc; attr = lds; }
-  hipLaunchKernelGGL((strip_mlp_kernel<MODE>), dim3((unsigned)((d.M + 127) / 128)), dim3(256), lds, st, d);
-  HFTT_CHECK_LAUNCH("strip_mlp");
-  return 0;
+  return hftt_launch<strip_mlp_kernel<MODE>>("strip_mlp", dim3((unsigned)((d.M + 127) / 128)), dim3(256), lds, st, d);
 }
 
 int check_ffn(const hftt_ffn_desc* d, int mode, const char* what) {
@@ -623,9 +608,7 @@ int check_ffn(const hftt_ffn_desc* d, int mode, const char* what) {
 extern "C" int hftt_strip_pack(const float* params, uint16_t* wstrip, const hftt_strip_pack_entry* table_dev, int n_entries, void* stream) {
   HFTT_REQUIRE(params != nullptr && wstrip != nullptr && table_dev != nullptr && n_entries > 0, "strip_pack: null argument");
   HFTT_REQUIRE(((uintptr_t)wstrip & 15) == 0 && ((uintptr_t)params & 15) == 0, "strip_pack: buffers must be 16-byte aligned");
-  hipLaunchKernelGGL(strip_pack_kernel, dim3(32, (unsigned)n_entries), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), params, wstrip, table_dev);
-  HFTT_CHECK_LAUNCH("strip_pack");
-  return 0;
+  return hftt_launch<strip_pack_kernel>("strip_pack", dim3(32, (unsigned)n_entries), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), params, wstrip, table_dev);
 }
 
 extern "C" int hftt_strip_linear(const hftt_strip_desc* d, void* stream) {

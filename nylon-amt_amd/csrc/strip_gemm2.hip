@@ -22,7 +22,7 @@
 #include <type_traits>
 #include <utility>
 #include "hftt_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "strip_internal.h"
 #include "../../include/hftt_hip.h"
 
@@ -697,37 +697,16 @@ __global__ __launch_bounds__(256, 1) void strip_mlp2_kernel(const hftt_ffn_desc 
   P.drain();
 }
 
-int n_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-    n = prop.multiProcessorCount;
-  }
-  return n;
-}
 bool v2_enabled() {
   const char* e = getenv("HFTT_STRIP_V2");
   return !(e && e[0] == '0');
 }
-template <typename K>
-int set_lds(K kernel, int lds, const char* what) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) { hftt_set_error("%s: hipFuncSetAttribute(%d B LDS) failed: %s", what, lds, hipGetErrorString(e)); return 2; }
-  return 0;
-}
 template <bool LN, int PASSES, int KCH, bool HR, bool STP>
 int launch_linear2_stp(const hftt_strip_desc& d, hipStream_t st) {
   const int lds = RING_BYTES + 4 * (d.N + 512) + (STP ? 4 * 2 * PATCH_BYTES : 0);
-  static int attr = 0;
-  if (lds > attr) { if (int rc = set_lds(strip_linear2_kernel<LN, PASSES, KCH, HR, STP>, lds, "strip_linear2")) return rc; attr = lds; }
-  const int cus = n_cus();
-  if (cus <= 0) { hftt_set_error("strip_linear2: device query failed"); return 2; }
-  const long nblk = ((long)d.M + 127) / 128;
-  hipLaunchKernelGGL((strip_linear2_kernel<LN, PASSES, KCH, HR, STP>), dim3((unsigned)(nblk < cus ? nblk : cus)), dim3(256), lds, st, d);
-  HFTT_CHECK_LAUNCH("strip_linear2");
-  return 0;
+  const long grid = hftt_persistent_grid("strip_linear2", ((long)d.M + 127) / 128, 1);
+  if (grid < 0) return 2;
+  return hftt_launch<strip_linear2_kernel<LN, PASSES, KCH, HR, STP>>("strip_linear2", dim3((unsigned)grid), dim3(256), lds, st, d);
 }
 // HFTT_LINEAR2_PATCH=0: the round-2 row-piece stores (A/B switch; default: whole lines through the LDS patch)
 template <bool LN, int PASSES, int KCH, bool HR>
@@ -739,15 +718,9 @@ int launch_linear2(const hftt_strip_desc& d, hipStream_t st) {
 template <int MODE, bool STP>
 int launch_mlp2(const hftt_ffn_desc& d, hipStream_t st) {
   const int lds = RING_BYTES + 4 * (d.p + 768) + (STP ? 4 * 3 * PATCH_BYTES : 0);
-  static int attr = 0;
-  if (lds > attr) { if (int rc = set_lds(strip_mlp2_kernel<MODE, 16, STP>, lds, "strip_mlp2")) return rc; attr = lds; }
-  const int cus = n_cus();
-  if (cus <= 0) { hftt_set_error("strip_mlp2: device query failed"); return 2; }
-  const long nblk = ((long)d.M + 127) / 128;
-  const long grid = cus;
-  hipLaunchKernelGGL((strip_mlp2_kernel<MODE, 16, STP>), dim3((unsigned)(nblk < grid ? nblk : grid)), dim3(256), lds, st, d);
-  HFTT_CHECK_LAUNCH("strip_mlp2");
-  return 0;
+  const long grid = hftt_persistent_grid("strip_mlp2", ((long)d.M + 127) / 128, 1);
+  if (grid < 0) return 2;
+  return hftt_launch<strip_mlp2_kernel<MODE, 16, STP>>("strip_mlp2", dim3((unsigned)grid), dim3(256), lds, st, d);
 }
 }  // namespace
 

@@ -11,7 +11,7 @@
 #include <type_traits>
 #include "hftt_common.h"
 #include "x3_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "x3_internal.h"
 #include "../../include/hftt_hip.h"
 #include <math.h>
@@ -337,15 +337,7 @@ template <int KT, int DH, bool MAP>
 int launch_xf2(const hftt_attn_desc& d, hipStream_t st) {
   using Cfg = XfCfg<KT, DH>;
   constexpr int NW = (KT == 8) ? 8 : 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(x3_attn_fwd_kernel<KT, DH, NW, MAP>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-    if (e != hipSuccess) { hftt_set_error("x3_attn_fwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return 2; }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((x3_attn_fwd_kernel<KT, DH, NW, MAP>), dim3((unsigned)(d.n_seq * d.n_heads)), dim3(NW * 64), Cfg::LDS_BYTES, st, d);
-  HFTT_CHECK_LAUNCH("x3_attn_fwd");
-  return 0;
+  return hftt_launch<x3_attn_fwd_kernel<KT, DH, NW, MAP>>("x3_attn_fwd", dim3((unsigned)(d.n_seq * d.n_heads)), dim3(NW * 64), Cfg::LDS_BYTES, st, d);
 }
 template <int KT, int DH>
 int launch_xf(const hftt_attn_desc& d, hipStream_t st) {

@@ -624,30 +624,13 @@ __global__ __launch_bounds__(KT * 64, (KT == 4 || (KT == 3 && (PL || DH == 32)))
 template <int KT, int DH, bool PL, int DM>
 int launch_xb(const hftt_attn_desc& d, hipStream_t st) {
   using Cfg = XbCfg<KT, DH>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(x3_attn_bwd_kernel<KT, DH, PL, DM>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-    if (e != hipSuccess) { hftt_set_error("x3_attn_bwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return 2; }
-    attr_set = true;
-  }
   long grid = (long)d.n_seq * d.n_heads;
   if (PL) {                                           // persistent: as many workgroups as the device holds at once
-    static int resident = 0;
-    if (resident == 0) {
-      int dev = 0, per_cu = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(x3_attn_bwd_kernel<KT, DH, PL, DM>), Cfg::NTHR, Cfg::LDS_BYTES) != hipSuccess || per_cu < 1) {
-        hftt_set_error("x3_attn_bwd: device / occupancy query failed");
-        return 2;
-      }
-      resident = per_cu * prop.multiProcessorCount;
-    }
+    int resident = 0;
+    if (int rc = hftt_resident_wgs<x3_attn_bwd_kernel<KT, DH, PL, DM>>("x3_attn_bwd", Cfg::NTHR, Cfg::LDS_BYTES, &resident)) return rc;
     if (grid > resident) grid = resident;
   }
-  hipLaunchKernelGGL((x3_attn_bwd_kernel<KT, DH, PL, DM>), dim3((unsigned)grid), dim3(Cfg::NTHR), Cfg::LDS_BYTES, st, d);
-  HFTT_CHECK_LAUNCH("x3_attn_bwd");
-  return 0;
+  return hftt_launch<x3_attn_bwd_kernel<KT, DH, PL, DM>>("x3_attn_bwd", dim3((unsigned)grid), dim3(Cfg::NTHR), Cfg::LDS_BYTES, st, d);
 }
 template <int KT, int DH, bool PL>
 int launch_xb3(const hftt_attn_desc& d, hipStream_t st) {

@@ -21,7 +21,7 @@
 #include <type_traits>
 #include "hftt_common.h"
 #include "x3_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "x3_internal.h"
 #include "../../include/hftt_hip.h"
 #include <math.h>
@@ -402,34 +402,14 @@ __global__ __launch_bounds__(NW * 64, (KT <= 3) ? 3 : (KT <= 4) ? 2 : 1) void x3
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the trailing re-fetch must not outlive the workgroup's LDS allocation
 }
 
-int pl_n_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-    n = prop.multiProcessorCount;
-  }
-  return n;
-}
-
 template <int KT, int NW, bool MAP, int DM>
 int launch_pf(const hftt_attn_desc& d, hipStream_t st) {
   using Cfg = PfCfg<KT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(x3p_attn_fwd_kernel<KT, NW, MAP, DM>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-    if (e != hipSuccess) { hftt_set_error("x3p_attn_fwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return 2; }
-    attr_set = true;
-  }
-  const int cus = pl_n_cus();
-  if (cus <= 0) { hftt_set_error("x3p_attn_fwd: device query failed"); return 2; }
   const int per_cu = Cfg::LDS_BYTES <= 53 * 1024 ? 3 : Cfg::LDS_BYTES <= 80 * 1024 ? 2 : 1;      // (<= 96 keys: 49 KB of images, three workgroups of four waves per CU; the launch bound keeps them at <= 170 registers)
   const long items = (long)d.n_seq * d.n_heads;
-  const long grid = items < (long)per_cu * cus ? items : (long)per_cu * cus;
-  hipLaunchKernelGGL((x3p_attn_fwd_kernel<KT, NW, MAP, DM>), dim3((unsigned)grid), dim3(NW * 64), Cfg::LDS_BYTES, st, d, (int)items);
-  HFTT_CHECK_LAUNCH("x3p_attn_fwd");
-  return 0;
+  const long grid = hftt_persistent_grid("x3p_attn_fwd", items, per_cu);
+  if (grid < 0) return 2;
+  return hftt_launch<x3p_attn_fwd_kernel<KT, NW, MAP, DM>>("x3p_attn_fwd", dim3((unsigned)grid), dim3(NW * 64), Cfg::LDS_BYTES, st, d, (int)items);
 }
 template <int KT, int NW, bool MAP>
 int launch_pf3(const hftt_attn_desc& d, hipStream_t st) {
@@ -509,7 +489,5 @@ extern "C" int hftt_x3_to_planes(const float* src, int64_t lds, float* dst, int6
   HFTT_REQUIRE(src != dst, "x3_to_planes: not an in-place operation (a thread's 16-byte outputs overlap its neighbours' 32-byte inputs)");
   const long total = (long)rows * (cols / 8);
   const long blocks = (total + 255) / 256;
-  hipLaunchKernelGGL(x3_to_planes_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, (long)lds, dst, (long)ldd, rows, cols);
-  HFTT_CHECK_LAUNCH("x3_to_planes");
-  return 0;
+  return hftt_launch<x3_to_planes_kernel>("x3_to_planes", dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, (long)lds, dst, (long)ldd, rows, cols);
 }

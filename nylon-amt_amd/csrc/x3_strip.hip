@@ -17,7 +17,7 @@
 #include <utility>
 #include "hftt_common.h"
 #include "x3_common.h"
-#include "hftt_host.h"
+#include "hftt_launch.h"
 #include "x3_internal.h"
 #include "../../include/hftt_hip.h"
 
@@ -1090,22 +1090,6 @@ __global__ __launch_bounds__(256, 1) void x3_oln_mlp_kernel(const hftt_strip_des
   P.drain();
 }
 
-int n_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-    n = prop.multiProcessorCount;
-  }
-  return n;
-}
-template <typename K>
-int set_lds(K kernel, int lds, const char* what) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) { hftt_set_error("%s: hipFuncSetAttribute(%d B LDS) failed: %s", what, lds, hipGetErrorString(e)); return 2; }
-  return 0;
-}
 // Resident strip chunks of the one-pass K-outer forms without LayerNorm (the K = 512 / 768 dX products): 8 = half a set, 256 registers (24 bytes
 // of scratch on the K = 768 residual form), two workgroups per CU -- one's epilogue under the other's MFMAs.  Same box, three interleaved runs each
 // way: 277.07 against 276.17 clips/s (+0.3 %, profiles/r06_ab_dx_two_workgroups.txt).  The LayerNorm form (fc_o + residual + LayerNorm) stays at
@@ -1118,51 +1102,31 @@ template <int E, bool LN, int PASSES, int KCH, bool HR>
 int launch_xl(const hftt_strip_desc& d, hipStream_t st) {
   constexpr int XR = (PASSES == 1 && !LN) ? HFTT_XL_XR : 16;
   const int lds = RING_BYTES + 4 * (PASSES * 256 + 512) + 4 * STG_BYTES_PER_WAVE;
-  static int attr = 0;
-  if (lds > attr) { if (int rc = set_lds(x3_linear_kernel<E, LN, PASSES, KCH, HR, XR>, lds, "x3_strip_linear")) return rc; attr = lds; }
-  const int cus = n_cus() * (XR == 16 ? 1 : 2);
-  if (cus <= 0) { hftt_set_error("x3_strip_linear: device query failed"); return 2; }
-  const long nblk = ((long)d.M + 127) / 128;
-  hipLaunchKernelGGL((x3_linear_kernel<E, LN, PASSES, KCH, HR, XR>), dim3((unsigned)(nblk < cus ? nblk : cus)), dim3(256), lds, st, d);
-  HFTT_CHECK_LAUNCH("x3_strip_linear");
-  return 0;
+  const long grid = hftt_persistent_grid("x3_strip_linear", ((long)d.M + 127) / 128, XR == 16 ? 1 : 2);
+  if (grid < 0) return 2;
+  return hftt_launch<x3_linear_kernel<E, LN, PASSES, KCH, HR, XR>>("x3_strip_linear", dim3((unsigned)grid), dim3(256), lds, st, d);
 }
 template <int E, int NT, bool HR, bool PLN = false, bool XD = false>
 int launch_xn(const hftt_strip_desc& d, hipStream_t st) {
   const int lds = RING_BYTES + 4 * d.N + 4 * STG_BYTES_PER_WAVE;
-  static int attr = 0;
-  if (lds > attr) { if (int rc = set_lds(x3_linear_n_kernel<E, NT, HR, PLN, XD>, lds, "x3_strip_linear")) return rc; attr = lds; }
-  const int cus = n_cus();
-  if (cus <= 0) { hftt_set_error("x3_strip_linear: device query failed"); return 2; }
-  const long nblk = ((long)d.M + 127) / 128;
-  hipLaunchKernelGGL((x3_linear_n_kernel<E, NT, HR, PLN, XD>), dim3((unsigned)(nblk < 2 * cus ? nblk : 2 * cus)), dim3(256), lds, st, d);
-  HFTT_CHECK_LAUNCH("x3_strip_linear");
-  return 0;
+  const long grid = hftt_persistent_grid("x3_strip_linear", ((long)d.M + 127) / 128, 2);
+  if (grid < 0) return 2;
+  return hftt_launch<x3_linear_n_kernel<E, NT, HR, PLN, XD>>("x3_strip_linear", dim3((unsigned)grid), dim3(256), lds, st, d);
 }
 template <int MODE, bool HH, bool GH = false>
 int launch_xm(const hftt_ffn_desc& d, hipStream_t st) {
   const int lds = RING_BYTES + 4 * (d.p + 768) + 4 * STG_BYTES_PER_WAVE;
-  static int attr = 0;
-  if (lds > attr) { if (int rc = set_lds(x3_mlp_kernel<MODE, 16, HH, GH>, lds, "x3_strip_mlp")) return rc; attr = lds; }
-  const int cus = n_cus();
-  if (cus <= 0) { hftt_set_error("x3_strip_mlp: device query failed"); return 2; }
-  const long nblk = ((long)d.M + 127) / 128;
-  hipLaunchKernelGGL((x3_mlp_kernel<MODE, 16, HH, GH>), dim3((unsigned)(nblk < cus ? nblk : cus)), dim3(256), lds, st, d);
-  HFTT_CHECK_LAUNCH("x3_strip_mlp");
-  return 0;
+  const long grid = hftt_persistent_grid("x3_strip_mlp", ((long)d.M + 127) / 128, 1);
+  if (grid < 0) return 2;
+  return hftt_launch<x3_mlp_kernel<MODE, 16, HH, GH>>("x3_strip_mlp", dim3((unsigned)grid), dim3(256), lds, st, d);
 }
 
 template <bool HH>
 int launch_xom(const hftt_strip_desc& o, const hftt_ffn_desc& d, hipStream_t st) {
   const int lds = RING_BYTES + 4 * 2048 + 4 * STG_BYTES_PER_WAVE;
-  static int attr = 0;
-  if (lds > attr) { if (int rc = set_lds(x3_oln_mlp_kernel<HH>, lds, "x3_attn_out_ffn")) return rc; attr = lds; }
-  const int cus = n_cus();
-  if (cus <= 0) { hftt_set_error("x3_attn_out_ffn: device query failed"); return 2; }
-  const long nblk = ((long)d.M + 127) / 128;
-  hipLaunchKernelGGL((x3_oln_mlp_kernel<HH>), dim3((unsigned)(nblk < cus ? nblk : cus)), dim3(256), lds, st, o, d);
-  HFTT_CHECK_LAUNCH("x3_attn_out_ffn");
-  return 0;
+  const long grid = hftt_persistent_grid("x3_attn_out_ffn", ((long)d.M + 127) / 128, 1);
+  if (grid < 0) return 2;
+  return hftt_launch<x3_oln_mlp_kernel<HH>>("x3_attn_out_ffn", dim3((unsigned)grid), dim3(256), lds, st, o, d);
 }
 
 #include "x3s_strip.h"
@@ -1313,8 +1277,6 @@ extern "C" int hftt_x3_strip_pack(const float* params, uint16_t* wstrip, const h
   HFTT_REQUIRE(((uintptr_t)wstrip & 15) == 0 && ((uintptr_t)params & 15) == 0, "x3_strip_pack: buffers must be 16-byte aligned");
   HFTT_REQUIRE(elem == X3_F16 || elem == X3_BF16, "x3_strip_pack: elem must be 2 (fp16 halves) or 4 (bf16 halves)");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (elem == X3_F16) hipLaunchKernelGGL(x3_strip_pack_kernel<X3_F16>, dim3(32, (unsigned)n_entries), dim3(256), 0, st, params, wstrip, table_dev);
-  else hipLaunchKernelGGL(x3_strip_pack_kernel<X3_BF16>, dim3(32, (unsigned)n_entries), dim3(256), 0, st, params, wstrip, table_dev);
-  HFTT_CHECK_LAUNCH("x3_strip_pack");
-  return 0;
+  if (elem == X3_F16) return hftt_launch<x3_strip_pack_kernel<X3_F16>>("x3_strip_pack", dim3(32, (unsigned)n_entries), dim3(256), 0, st, params, wstrip, table_dev);
+  return hftt_launch<x3_strip_pack_kernel<X3_BF16>>("x3_strip_pack", dim3(32, (unsigned)n_entries), dim3(256), 0, st, params, wstrip, table_dev);
 }

@@ -321,26 +321,15 @@ __global__ __launch_bounds__(256, 2) void x3s_mlp_kernel(const hftt_ffn_desc g) 
 template <int E, int K32, int NT, bool LN, bool HR>
 int launch_xs(const hftt_strip_desc& d, hipStream_t st) {
   using Cfg = XsCfg<K32, NT, LN>;
-  static bool attr = false;
-  if (!attr) { if (int rc = set_lds(x3s_linear_kernel<E, K32, NT, LN, HR>, Cfg::LDS, "x3s_strip_linear")) return rc; attr = true; }
-  const int cus = n_cus();
-  if (cus <= 0) { hftt_set_error("x3s_strip_linear: device query failed"); return 2; }
-  const long nblk = ((long)d.M + 127) / 128;
-  const long cap = (long)x3s_wgs(Cfg::LDS) * cus;
-  hipLaunchKernelGGL((x3s_linear_kernel<E, K32, NT, LN, HR>), dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(256), Cfg::LDS, st, d);
-  HFTT_CHECK_LAUNCH("x3s_strip_linear");
-  return 0;
+  const long grid = hftt_persistent_grid("x3s_strip_linear", ((long)d.M + 127) / 128, x3s_wgs(Cfg::LDS));
+  if (grid < 0) return 2;
+  return hftt_launch<x3s_linear_kernel<E, K32, NT, LN, HR>>("x3s_strip_linear", dim3((unsigned)grid), dim3(256), Cfg::LDS, st, d);
 }
 template <int MODE, bool HH>
 int launch_xsm(const hftt_ffn_desc& d, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) { if (int rc = set_lds(x3s_mlp_kernel<MODE, HH>, XSM_LDS, "x3s_strip_mlp")) return rc; attr = true; }
-  const int cus = n_cus();
-  if (cus <= 0) { hftt_set_error("x3s_strip_mlp: device query failed"); return 2; }
-  const long nblk = ((long)d.M + 127) / 128;
-  hipLaunchKernelGGL((x3s_mlp_kernel<MODE, HH>), dim3((unsigned)(nblk < 2L * cus ? nblk : 2L * cus)), dim3(256), XSM_LDS, st, d);
-  HFTT_CHECK_LAUNCH("x3s_strip_mlp");
-  return 0;
+  const long grid = hftt_persistent_grid("x3s_strip_mlp", ((long)d.M + 127) / 128, 2);
+  if (grid < 0) return 2;
+  return hftt_launch<x3s_mlp_kernel<MODE, HH>>("x3s_strip_mlp", dim3((unsigned)grid), dim3(256), XSM_LDS, st, d);
 }
 
 // the shapes of the d = 64 model (K x N): forward 64x192 (q, k, v), 64x128 (cross k, v), 64x64 (cross q; fc_o + LayerNorm), backward 64x64

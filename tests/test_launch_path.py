@@ -1,0 +1,114 @@
+"""One host launch path (csrc/hftt_launch.h): every kernel launch goes guard -> LDS attribute -> launch -> launch check through hftt_launch, and
+the per-process device state (first device, CU count, per-kernel LDS attribute and resident-workgroup count) lives in hftt_launch.h and
+capi.cpp alone.  The structure test keeps the next launcher from copying the plumbing again; the two-device GPU test holds the guard IN FRONT of the launch."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+import util
+
+CSRC = os.path.join(util.ROOT, 'nylon-amt_amd', 'csrc')
+
+
+def _sources():
+    return {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith(('.hip', '.h', '.cpp'))}
+
+
+def test_launch_plumbing_lives_in_one_place():
+    src = _sources()
+    assert 'hftt_launch.h' in src and len(src) >= 20
+    only_in = {'hipLaunchKernelGGL': {'hftt_launch.h'}, 'hipFuncSetAttribute': {'hftt_launch.h'},
+               'hipOccupancyMaxActiveBlocksPerMultiprocessor': {'hftt_launch.h'}, 'hipGetDeviceProperties': {'capi.cpp'}}
+    for call, allowed in only_in.items():
+        users = {f for f, s in src.items() if call in s}
+        assert users == allowed, (call, sorted(users))
+    # no launch that bypasses the path in another spelling either
+    assert not [f for f, s in src.items() if re.search(r'<<<|hipLaunchKernel\b|hipModuleLaunchKernel|hipExtLaunchKernel', s)]
+    # the hand-kept copies this path replaced, and the per-launcher caches that went with them
+    removed = re.compile(r'\b(n_cus|bs_cus|pl_n_cus|set_lds|bs_set_lds|HFTT_CHECK_LAUNCH)\b|static\s+\w+\s+(attr\w*|resident|n_cu)\b')
+    for f, s in src.items():
+        if f != 'hftt_launch.h':
+            assert removed.search(s) is None, (f, removed.search(s).group(0))
+    # every translation unit of the library that holds a kernel launches through the header
+    for f, s in src.items():
+        if '__global__' in s and f.endswith('.hip'):
+            assert '#include "hftt_launch.h"' in s and 'hftt_launch<' in s, f
+    # ... and the path itself checks the device before it touches the kernel
+    body = src['hftt_launch.h']
+    body = body[body.index('int hftt_launch('):]
+    order = [body.index(k) for k in ('hftt_device_guard(', 'hftt_lds_attr<', 'hipLaunchKernelGGL(', 'hipGetLastError(')]
+    assert order == sorted(order)
+
+
+def test_the_guard_test_op_is_a_single_launch_that_writes_its_sentinel():
+    '''test_second_device_is_refused_before_anything_is_enqueued tells guard-before-launch from guard-after-launch only if the FIRST launch of
+    the refused call writes the tensor that carries the sentinel: hftt_adam_step is one launch, and adam_kernel updates p, m, v in place.'''
+    s = _sources()['elementwise.hip']
+    body = s[s.index('extern "C" int hftt_adam_step('):]
+    body = body[:body.index('\n}\n')]
+    assert body.count('hftt_launch<') == 1 and 'hftt_launch<adam_kernel>' in body
+    kern = s[s.index('adam_kernel('):s.index('inline int grid_for(')]
+    assert re.search(r'\bp\[i\] -=', kern) and re.search(r'\bm\[i\] =', kern) and re.search(r'\bv\[i\] =', kern)
+
+
+_CHILD = r'''
+import sys
+sys.path[:0] = %r
+import torch
+from hftt_hip import HfttError, ops
+
+
+def tensors(device):
+    return [torch.full((1024,), f, device=device) for f in (-7.0, 1.0, 0.5, 0.25)]           # p, g, m, v
+
+
+second = int(sys.argv[1])
+p, g, m, v = tensors('cuda:0')
+ops.adam_step(p, g, m, v, 1, lr=1.0)
+torch.cuda.synchronize(0)
+assert (p.cpu() != -7.0).all() and (m.cpu() != 0.5).all() and (v.cpu() != 0.25).all(), 'adam_step does not write p, m, v'
+print('adam_step: one launch that writes p, m, v')
+if second == 0:
+    sys.exit(0)
+with torch.cuda.device(second):
+    p, g, m, v = tensors('cuda:%%d' %% second)
+    torch.cuda.synchronize(second)
+    try:
+        ops.adam_step(p, g, m, v, 1, lr=1.0)
+    except HfttError as e:
+        assert 'rc=3' in str(e) and 'one process drives one device' in str(e), str(e)
+    else:
+        raise AssertionError('the launch from a second device was not refused')
+    torch.cuda.synchronize(second)
+    for t, f in ((p, -7.0), (m, 0.5), (v, 0.25)):
+        assert torch.equal(t.cpu(), torch.full((1024,), f)), 'refused with status 3, but the kernel ran'
+print('second-device launch refused before anything was enqueued')
+'''
+
+
+def _child(second):
+    paths = [util.ROOT, os.path.join(util.ROOT, 'nylon-amt_amd')]
+    r = subprocess.run([sys.executable, '-c', _CHILD % (paths,), str(second)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    return r.stdout
+
+
+@pytest.mark.gpu
+def test_sentinel_op_overwrites_its_operands_on_the_first_device(dev):
+    '''The half of the guard test that one device can run: in a fresh process, adam_step on device 0 overwrites every element of p, m and v
+    (so an intact sentinel on the second device means that nothing ran there).'''
+    assert 'adam_step: one launch that writes p, m, v' in _child(0)
+
+
+@pytest.mark.gpu
+def test_second_device_is_refused_before_anything_is_enqueued(dev):
+    '''A fresh process (the guard's state is per process): adam_step on device 0, then the same call on device 1 with p, m, v pre-filled --
+    status 3 and all three intact.  adam_step is ONE launch that updates them in place (the CPU test above), so with the guard behind the
+    launch the kernel would have been enqueued and have overwritten them by the time status 3 came back.'''
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip('needs two visible devices')
+    assert 'refused before anything was enqueued' in _child(1)
