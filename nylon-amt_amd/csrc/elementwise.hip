@@ -149,6 +149,8 @@ __global__ void im2win_kernel(const float* __restrict__ spec, float* __restrict_
 }
 
 // ------------------------------------------------------------------ LayerNorm backward
+// one row per wave, element-wise accesses only: N = 128, and the form hftt_ln_bwd falls back to at N = 64 / 256 when an operand is not
+// 16-byte aligned (a view offset by one element), so no access here may be wider than the element.
 template <int VPL>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const hftt_ln_bwd_desc g) {
   constexpr int N = VPL * 64;
@@ -163,15 +165,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const hftt_ln_bwd_desc g) {
   for (long row = (long)blockIdx.x * 4 + wave; row < g.M; row += (long)gridDim.x * 4) {
     float dy[VPL], r[VPL];
     const long base = row * N + lane * VPL;
-    if (VPL == 4) {
-      const float4 a = hftt_load4(g.dy, dy_bf, base);
-      const float4 b = hftt_load4(g.r, r_bf, base);
-      dy[0] = a.x; dy[1 % VPL] = a.y; dy[2 % VPL] = a.z; dy[3 % VPL] = a.w;
-      r[0] = b.x; r[1 % VPL] = b.y; r[2 % VPL] = b.z; r[3 % VPL] = b.w;
-    } else {
 #pragma unroll
-      for (int e = 0; e < VPL; e++) { dy[e] = dy_bf ? bf2f(reinterpret_cast<const unsigned short*>(g.dy)[base + e]) : g.dy[base + e]; r[e] = r_bf ? bf2f(reinterpret_cast<const unsigned short*>(g.r)[base + e]) : g.r[base + e]; }
-    }
+    for (int e = 0; e < VPL; e++) { dy[e] = dy_bf ? bf2f(reinterpret_cast<const unsigned short*>(g.dy)[base + e]) : g.dy[base + e]; r[e] = r_bf ? bf2f(reinterpret_cast<const unsigned short*>(g.r)[base + e]) : g.r[base + e]; }
     const float mean = g.mean[row], rstd = g.rstd[row];
     float xh[VPL], gg[VPL], s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -193,25 +188,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const hftt_ln_bwd_desc g) {
       if (g.dr_drop != nullptr && g.drop_p > 0.f)
         od[e] = hftt_keep(g.drop_seed, g.drop_site, (uint64_t)(base + e), thr) ? o[e] * inv_keep : 0.f;
     }
-    if (VPL == 4) {
-      hftt_store4(g.dr, dr_bf, base, o[0], o[1 % VPL], o[2 % VPL], o[3 % VPL]);
-      if (g.dr_drop != nullptr) {
-        if (g.drop_bf16) {
-          uint2 u;
-          u.x = f2bf(od[0]) | ((unsigned)f2bf(od[1 % VPL]) << 16); u.y = f2bf(od[2 % VPL]) | ((unsigned)f2bf(od[3 % VPL]) << 16);
-          *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(g.dr_drop) + base) = u;
-        } else {
-          *reinterpret_cast<float4*>(g.dr_drop + base) = make_float4(od[0], od[1 % VPL], od[2 % VPL], od[3 % VPL]);
-        }
-      }
-    } else {
 #pragma unroll
-      for (int e = 0; e < VPL; e++) {
-        hftt_store1(g.dr, dr_bf, base + e, o[e]);
-        if (g.dr_drop != nullptr) {
-          if (g.drop_bf16) reinterpret_cast<unsigned short*>(g.dr_drop)[base + e] = f2bf(od[e]);
-          else g.dr_drop[base + e] = od[e];
-        }
+    for (int e = 0; e < VPL; e++) {
+      hftt_store1(g.dr, dr_bf, base + e, o[e]);
+      if (g.dr_drop != nullptr) {
+        if (g.drop_bf16) reinterpret_cast<unsigned short*>(g.dr_drop)[base + e] = f2bf(od[e]);
+        else g.dr_drop[base + e] = od[e];
       }
     }
   }

@@ -64,9 +64,9 @@ def test_loss_kernel_values_and_gradients(dev, V, n):
     capi.check(L.hftt_loss(C.byref(d), _st(dev)), 'loss')
     got = out[:9].cpu().double()
     assert abs(got[0] - total.item()) < 2e-5 * abs(total.item())
-    order = [0, 1, 2, 4, 5, 6, 3, 7]                        # loss_out[1..8]: the six BCE terms in prob[] order, then ... (checked below as a set)
-    ref_terms = sorted(t.item() for t in terms)
-    assert np.allclose(sorted(got[1:9].tolist()), ref_terms, rtol=2e-5, atol=1e-6)
+    # loss_out[1..8] IN the documented order (include/hftt_hip.h): onset_A, offset_A, mpe_A, velocity_A, onset_B, offset_B, mpe_B, velocity_B
+    ref_terms = [t.item() for t in terms]
+    assert np.allclose(got[1:9].tolist(), ref_terms, rtol=2e-5, atol=1e-6)
     # gradients; a saturated posterior on the wrong side has the clamped-log gradient torch gives (huge but finite): compare relative
     for i, k in enumerate((0, 1, 2, 3, 4, 5)):
         ref = p64[k].grad
