@@ -14,6 +14,8 @@
 //     every ds_read behind the youngest DMA).  Two workgroups per CU run free of each other, so one's epilogue (VALU,
 //     stores) overlaps the other's MFMA phase.
 #include <stdlib.h>
+#include <type_traits>
+#include <utility>
 #include "hftt_common.h"
 #include "hftt_launch.h"
 #include "strip_internal.h"
@@ -22,10 +24,7 @@
 
 namespace {
 
-constexpr int SLOT_BYTES = 16384;
-constexpr int NSLOT = 4;
-constexpr int RING_BYTES = NSLOT * SLOT_BYTES;
-constexpr int FILL_AHEAD = NSLOT - 1;
+#include "strip_pipe.h"
 
 // Ablation build (tools/ablate_strip.sh compiles this file with -DHFTT_STRIP_ABLATE into its own library): the descriptor's pad
 // field switches single mechanisms off so their cost can be read from the timing difference (results are then garbage).
@@ -106,25 +105,9 @@ __device__ __forceinline__ void wait_slot_after_stores(int s, int S) {
   else if (s + 1 < S) wait_vmcnt<4 + NST>();
   else wait_vmcnt<NST>();
 }
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
-  typedef float f2_t __attribute__((ext_vector_type(2)));
-  const f2_t v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf2_t));
-}
-__device__ __forceinline__ bf16x8 pack8(const float* v) {
-  uint4 o;
-  o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]); o.z = pack2(v[4], v[5]); o.w = pack2(v[6], v[7]);
-  return __builtin_bit_cast(bf16x8, o);
-}
-__device__ __forceinline__ void unpack8(uint4 q, float* v) {
-  v[0] = __uint_as_float(q.x << 16); v[1] = __uint_as_float(q.x & 0xFFFF0000u);
-  v[2] = __uint_as_float(q.y << 16); v[3] = __uint_as_float(q.y & 0xFFFF0000u);
-  v[4] = __uint_as_float(q.z << 16); v[5] = __uint_as_float(q.z & 0xFFFF0000u);
-  v[6] = __uint_as_float(q.w << 16); v[7] = __uint_as_float(q.w & 0xFFFF0000u);
-}
+// the header's bf16 packing in the types this file holds its operands in (HIP's uint4 loads, bf16x8 fragments)
+__device__ __forceinline__ bf16x8 pack8(const float* v) { return as_frag(pack8u(v)); }
+__device__ __forceinline__ void unpack8(uint4 q, float* v) { unpack8(__builtin_bit_cast(u4v, q), v); }
 // 16 consecutive activations (fp32 or bf16 storage) at element offset `off`
 __device__ __forceinline__ void load16(const void* base, bool bf, long off, float* v) {
   if (bf) {
@@ -150,30 +133,6 @@ __device__ __forceinline__ void store16(void* base, bool bf, long off, const flo
     for (int q = 0; q < 4; q++) p[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
   }
 }
-// 16 fp32 parameters from LDS (all lanes of a half read the same address: broadcast)
-__device__ __forceinline__ void lds16f(const float* p, float* v) {
-#pragma unroll
-  for (int q = 0; q < 4; q++) { const float4 t = reinterpret_cast<const float4*>(p)[q]; v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w; }
-}
-// dropout on 16 consecutive elements whose first element index is 2*q0 (even): one hash per pair
-__device__ __forceinline__ void drop16(float* v, uint64_t seed, uint32_t site, uint64_t q0, uint32_t thr, float inv_keep) {
-  // q0 = (index of the first element) / 4: the 16 elements are four hash quads (hftt_keep: byte idx&3 of hash(idx>>2) < thr)
-#pragma unroll
-  for (int e = 0; e < 4; e++) {
-    const uint32_t w = hftt_hash(seed, site, q0 + e);
-    // byte < thr as an arithmetic mask (sign of byte - thr).  A compare + select per element parks one SGPR pair per decision and hipcc
-    // hoists all 64 pairs of an epilogue: the scalar file spilled (231 SGPRs).  The shift is inline asm because instcombine turns
-    // (x - thr) >> 31 back into that compare.
-    uint32_t m[4];
-    asm("v_ashrrev_i32 %0, 31, %1" : "=v"(m[0]) : "v"((w & 0xFFu) - thr));
-    asm("v_ashrrev_i32 %0, 31, %1" : "=v"(m[1]) : "v"(((w >> 8) & 0xFFu) - thr));
-    asm("v_ashrrev_i32 %0, 31, %1" : "=v"(m[2]) : "v"(((w >> 16) & 0xFFu) - thr));
-    asm("v_ashrrev_i32 %0, 31, %1" : "=v"(m[3]) : "v"((w >> 24) - thr));
-#pragma unroll
-    for (int f = 0; f < 4; f++) v[4 * e + f] = __uint_as_float(__float_as_uint(v[4 * e + f] * inv_keep) & m[f]);
-  }
-}
-
 // stream slot s -> ring buffer s % 4 (nothing past the last slot: the tail waits below count exactly what is in flight);
 // wave w moves fragments 4w .. 4w+3 of the slot
 __device__ __forceinline__ void ring_fill(const unsigned short* w, int s, int s_last, unsigned ring, int wave, int lane) {

@@ -1,5 +1,7 @@
-// Helpers shared by the pipelined strip kernels (strip_gemm2.hip, bs_strip.hip): ring constants, static_for, LDS-DMA and store asm,
-// bf16 packing, the 16-element dropout, the slot's MFMA loops, the LayerNorm row pass.  Included inside an anonymous namespace.
+// Helpers shared by the strip kernels (strip_gemm.hip, strip_gemm2.hip, x3_strip.hip, bs_strip.hip and, through the last two, small_strip.h):
+// ring constants, static_for, LDS-DMA and store asm, bf16 packing, the 16- and 8-element dropout (the ONE mask generator of every strip kernel:
+// forward and backward regenerate the same mask from it), the slot's MFMA loops, the pair patch, the LayerNorm row pass.  Included inside an
+// anonymous namespace.
 #pragma once
 constexpr int SLOT_BYTES = 16384;
 constexpr int NSLOT = 4;

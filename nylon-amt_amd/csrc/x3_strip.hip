@@ -42,7 +42,7 @@ __host__ __device__ inline int x3_i_of_c(int c) { const int g = c & 15, hh = c >
 // Slots of 16 fragments.  order 0 ("linear"): slot = (tile >> 3) * (K / 16) + chunk, fragment = 2 * (tile & 7) + plane;
 // order 1 ("tile-major", K == 256): slot = 2 * tile + (chunk >> 3), fragment = 2 * (chunk & 7) + plane.
 // Stream position of a slot: slot_offset + slot_stride * (slot >> 1) + (slot & 1)   (slots come in pairs; the fused FFN interleaves pairs).
-// order 2 ("compact", small widths: x3s_strip.h): no slots -- the (hi, lo) pair of (chunk, tile) at pair index slot_offset + chunk * NT + tile.
+// order 2 ("compact", small widths: small_strip.h): no slots -- the (hi, lo) pair of (chunk, tile) at pair index slot_offset + chunk * NT + tile.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int E>
 __global__ __launch_bounds__(256) void x3_strip_pack_kernel(const float* __restrict__ params, unsigned short* __restrict__ dst,
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void x3_strip_pack_kernel(const float* __restr
     const int pt = k >> 5, hk2 = (k >> 4) & 1, u = (k >> 3) & 1;
     const int ch = 2 * pt + u;
     long off;
-    if (e.order == 2) {                                 // compact (x3s_strip.h): pair (chunk, tile) at slot_offset + chunk * NT + tile, NT = slot_stride
+    if (e.order == 2) {                                 // compact (small_strip.h): pair (chunk, tile) at slot_offset + chunk * NT + tile, NT = slot_stride
       off = (e.slot_offset + (long)ch * e.slot_stride + tile) * 1024 + (hk2 * 32 + i) * 8;
     } else {
       long slot, frag;
@@ -1129,7 +1129,92 @@ int launch_xom(const hftt_strip_desc& o, const hftt_ffn_desc& d, hipStream_t st)
   return hftt_launch<x3_oln_mlp_kernel<HH>>("x3_attn_out_ffn", dim3((unsigned)grid), dim3(256), lds, st, o, d);
 }
 
-#include "x3s_strip.h"
+// The small-width family (small_strip.h) on the split-operand stream: a chunk is the (hi, lo) pair of 8 features, three passes per fragment
+// pair, fp32 tensors (bf16 where h16 says so) through the row-segment stores above.
+template <int E>
+struct X3Stream {
+  using Chunk = XChunk;
+  static constexpr int PAIR_BYTES = 2048;
+  static constexpr int STAGE_BYTES = STG_BYTES_PER_WAVE;
+  static constexpr const char* LINEAR_WHAT = "x3s_strip_linear";
+  static constexpr const char* MLP_WHAT = "x3s_strip_mlp";
+  static constexpr bool STAGES_OUTSIDE = true;        // (the row-segment stores stage regardless and mask the store)
+  static constexpr int wgs(int lds_bytes) { return lds_bytes <= 52 * 1024 ? 3 : (lds_bytes <= 78 * 1024 ? 2 : 1); }
+
+  // packed stream -> LDS, 16 bytes per thread and step (every wave-instruction a contiguous kilobyte)
+  static __device__ __forceinline__ void copy_weights(unsigned char* lds, const unsigned short* w, int pairs, int tid) {
+    const uint4* src = reinterpret_cast<const uint4*>(w);
+    uint4* dst = reinterpret_cast<uint4*>(lds);
+    for (int i = tid; i < pairs * 128; i += 256) dst[i] = src[i];
+  }
+  template <int KC>
+  static __device__ __forceinline__ void load_strip(XChunk (&xr)[KC], const void* x, long off) {
+    const float* p0 = reinterpret_cast<const float*>(x) + off;
+#pragma unroll
+    for (int c = 0; c < KC; c++) chunk_load(xr[c], p0 + chunk_off(c));
+#pragma unroll
+    for (int c = 0; c < KC; c++) chunk_convert<E>(xr[c]);
+  }
+  // small terms first (the order of x3_slot_tiles)
+  static __device__ __forceinline__ void tile_mac(const unsigned char* wl, int pair, const XChunk& x, f32x16& acc) {
+    const unsigned char* p = wl + pair * 2048;
+    const bf16x8 fh = *reinterpret_cast<const bf16x8*>(p), fl = *reinterpret_cast<const bf16x8*>(p + 1024);
+    const bf16x8 xh = __builtin_bit_cast(bf16x8, x.a), xl = __builtin_bit_cast(bf16x8, x.b);
+    acc = X3<E>::mma(fl, xh, acc);
+    acc = X3<E>::mma(fh, xl, acc);
+    acc = X3<E>::mma(fh, xh, acc);
+  }
+  static __device__ __forceinline__ void load16(const void* base, long off, bool h16, float* v) {
+    if (h16) load16h(reinterpret_cast<const unsigned short*>(base) + off, v);
+    else load16f(reinterpret_cast<const float*>(base) + off, v);
+  }
+  static __device__ __forceinline__ void values8(const XChunk& c, float* v) { chunk_values<E>(c, v); }
+  static __device__ __forceinline__ void split16(const float* v, XChunk (&hf)[2]) {
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      bf16x8 hi, lo;
+      x3_split8<E>(v + 8 * u, hi, lo);
+      hf[u].a = __builtin_bit_cast(u4v, hi); hf[u].b = __builtin_bit_cast(u4v, lo);
+    }
+  }
+  static __device__ __forceinline__ void* rows(void* base, long off, bool h16) {
+    return h16 ? static_cast<void*>(reinterpret_cast<unsigned short*>(base) + off) : static_cast<void*>(reinterpret_cast<float*>(base) + off);
+  }
+  static __device__ __forceinline__ void emit(unsigned char* stg, const float* v, int j, int hb, int lane, void* rows, long ld, int t, bool ok, bool h16) {
+    float* stage = reinterpret_cast<float*>(stg);
+    if (h16) tile_store_rows_bf16(stage, v, j, hb, lane, reinterpret_cast<unsigned short*>(rows) + t * 32, ld, ok);
+    else tile_store_rows(stage, v, j, hb, lane, reinterpret_cast<float*>(rows) + t * 32, ld, ok);
+  }
+  template <int K32, int NT, bool LN, bool HR>
+  static int launch_linear(dim3 grid, int lds, hipStream_t st, const hftt_strip_desc& d);
+  template <int MODE, bool HH>
+  static int launch_mlp(dim3 grid, int lds, hipStream_t st, const hftt_ffn_desc& d);
+};
+
+#include "small_strip.h"
+
+template <int E, int K32, int NT, bool LN, bool HR>
+__global__ __launch_bounds__(256, X3Stream<E>::wgs(SmallCfg<X3Stream<E>, K32, NT, LN>::LDS)) void x3s_linear_kernel(const hftt_strip_desc g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  small_linear<X3Stream<E>, K32, NT, LN, HR>(g, smem);
+}
+// mode 0 takes fp16 halves, mode 1 bf16 halves
+template <int MODE> using X3MlpStream = X3Stream<(MODE == 0) ? X3_F16 : X3_BF16>;
+template <int MODE, bool HH>
+__global__ __launch_bounds__(256, 2) void x3s_mlp_kernel(const hftt_ffn_desc g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  small_mlp<X3MlpStream<MODE>, MODE, HH>(g, smem);
+}
+template <int E>
+template <int K32, int NT, bool LN, bool HR>
+int X3Stream<E>::launch_linear(dim3 grid, int lds, hipStream_t st, const hftt_strip_desc& d) {
+  return hftt_launch<x3s_linear_kernel<E, K32, NT, LN, HR>>(LINEAR_WHAT, grid, dim3(256), lds, st, d);
+}
+template <int E>
+template <int MODE, bool HH>
+int X3Stream<E>::launch_mlp(dim3 grid, int lds, hipStream_t st, const hftt_ffn_desc& d) {
+  return hftt_launch<x3s_mlp_kernel<MODE, HH>>(MLP_WHAT, grid, dim3(256), lds, st, d);
+}
 
 template <int E>
 int dispatch_xl(const hftt_strip_desc& d, hipStream_t st) {
@@ -1178,13 +1263,13 @@ int hftt_x3_strip_linear(const hftt_strip_desc& d0, hipStream_t st) {
   d.pad = x3_debug();
   // the tile stores form each lane's row offset with __umul24 (tile_store_rows*): a stride beyond 24 bits would wrap silently
   HFTT_REQUIRE(d.ldc >= 0 && d.ldc < (1 << 24), "x3_strip_linear: ldc=%lld must be below 2^24 (24-bit row offsets)", (long long)d.ldc);
-  if (d.K <= 192 && d.N <= 192) {                     // the small-width family (weights resident in LDS, compact pack): x3s_strip.h
+  if (d.K <= 192 && d.N <= 192) {                     // the small-width family (weights resident in LDS, compact pack): small_strip.h
     HFTT_REQUIRE(d.K % 32 == 0 && d.N % 32 == 0 && d.M % 32 == 0 && d.K > 0 && d.N > 0, "x3s_strip_linear: needs K %% 32 == 0, N %% 32 == 0, M %% 32 == 0 (M=%d N=%d K=%d)", d.M, d.N, d.K);
     HFTT_REQUIRE(d.gate == nullptr && !(d.flags & (HFTT_SL_X_BF16 | HFTT_SL_C_BF16 | HFTT_SL_RES_BF16 | HFTT_SL_X3_GRAD_HI | HFTT_SL_C_F16PAIR)),
                  "x3s_strip_linear: fp32 tensors, no gate / gradient-rounding / plane forms");
     HFTT_REQUIRE(d.ldx % 4 == 0 && d.ldc % 4 == 0 && (d.residual == nullptr || d.ldr % 4 == 0), "x3s_strip_linear: rows must be 16-byte aligned");
     HFTT_REQUIRE(((uintptr_t)d.w & 15) == 0, "x3s_strip_linear: the weight stream must be 16-byte aligned");
-    return (d.flags & HFTT_SL_X3_BF16) ? dispatch_xs<X3_BF16>(d, st) : dispatch_xs<X3_F16>(d, st);
+    return (d.flags & HFTT_SL_X3_BF16) ? small_dispatch_linear<X3Stream<X3_BF16>>(d, st) : small_dispatch_linear<X3Stream<X3_F16>>(d, st);
   }
   HFTT_REQUIRE(d.K % 256 == 0 && d.N % 256 == 0 && d.M % 32 == 0, "x3_strip_linear: needs K %% 256 == 0, N %% 256 == 0, M %% 32 == 0 (M=%d N=%d K=%d)", d.M, d.N, d.K);
   HFTT_REQUIRE(d.gate == nullptr, "x3_strip_linear: no gate form (the fused block hftt_ffn_bwd_dx carries the gate)");
@@ -1214,7 +1299,7 @@ int hftt_x3_strip_mlp(const hftt_ffn_desc& d0, hipStream_t st) {
   d.pad = x3_debug();
   HFTT_REQUIRE(d.ldh >= 0 && d.ldh < (1 << 24) && d.ldy >= 0 && d.ldy < (1 << 24),
                "x3_strip_mlp: ldh=%lld / ldy=%lld must be below 2^24 (24-bit row offsets)", (long long)d.ldh, (long long)d.ldy);
-  if (d.d == 64 && d.p == 128) {                      // the reference's default width: x3s_strip.h
+  if (d.d == 64 && d.p == 128) {                      // the reference's default width: small_strip.h
     HFTT_REQUIRE(d.M % 32 == 0, "x3s_strip_mlp: needs M %% 32 == 0 (M=%d)", d.M);
     HFTT_REQUIRE(!(d.flags & (HFTT_SL_X_BF16 | HFTT_SL_C_BF16 | HFTT_SL_RES_BF16 | HFTT_SL_X3_GRAD_HI)), "x3s_strip_mlp: fp32 tensors, no gradient-rounding form");
     HFTT_REQUIRE(d.mode == 1 || d.residual == nullptr, "x3s_strip_mlp: the forward block's residual is its input");
@@ -1222,9 +1307,9 @@ int hftt_x3_strip_mlp(const hftt_ffn_desc& d0, hipStream_t st) {
     HFTT_REQUIRE(d.ldx % 4 == 0 && d.ldy % 4 == 0 && ((uintptr_t)d.w & 15) == 0, "x3s_strip_mlp: rows / weight stream must be 16-byte aligned");
     if (d.flags & HFTT_SL_H_BF16) {
       HFTT_REQUIRE((d.h_out == nullptr || d.ldh % 8 == 0) && (d.gate == nullptr || d.ldg % 8 == 0), "x3s_strip_mlp: bf16 hidden rows must be 16-byte aligned");
-      return d.mode == 0 ? launch_xsm<0, true>(d, st) : launch_xsm<1, true>(d, st);
+      return d.mode == 0 ? small_launch_mlp<X3MlpStream<0>, 0, true>(d, st) : small_launch_mlp<X3MlpStream<1>, 1, true>(d, st);
     }
-    return d.mode == 0 ? launch_xsm<0, false>(d, st) : launch_xsm<1, false>(d, st);
+    return d.mode == 0 ? small_launch_mlp<X3MlpStream<0>, 0, false>(d, st) : small_launch_mlp<X3MlpStream<1>, 1, false>(d, st);
   }
   HFTT_REQUIRE(d.p == 512 && d.M % 32 == 0, "x3_strip_mlp: needs p == 512 and M %% 32 == 0 (M=%d p=%d)", d.M, d.p);
   HFTT_REQUIRE(!(d.flags & (HFTT_SL_X_BF16 | HFTT_SL_C_BF16 | HFTT_SL_RES_BF16)), "x3_strip_mlp: tensors are fp32 in the split modes");

@@ -43,6 +43,27 @@ def test_launch_plumbing_lives_in_one_place():
     assert order == sorted(order)
 
 
+def test_strip_helpers_and_the_small_width_family_are_written_once():
+    '''The strip kernels' device helpers (the dropout mask generator above all: forward and backward regenerate the same mask from it) have one
+    definition each, and the small-width kernels one body (small_strip.h) that the two streams instantiate under their own symbol names.'''
+    src = _sources()
+    defs = {'drop16': r'\bvoid drop16\(', 'drop8': r'\bvoid drop8\(', 'pack2': r'\bunsigned pack2\(', 'lds16f': r'\bvoid lds16f\(',
+            'wait_lgkm0': r'\bvoid wait_lgkm0\(', 'SLOT_BYTES': r'\bconstexpr int SLOT_BYTES\b'}
+    for name, pat in defs.items():
+        where = [f for f, s in src.items() for _ in re.findall(pat, s)]
+        assert len(where) == 1, (name, where)
+    for kernel in ('bs_linear_kernel', 'x3s_linear_kernel'):
+        where = [f for f, s in src.items() for _ in re.findall(r'__global__ .*\bvoid %s\(' % kernel, s)]
+        assert len(where) == 1, (kernel, where)
+    small = [src[f] for f in ('small_strip.h', 'bs_strip.hip', 'x3_strip.hip')]
+    assert 'x3s_strip.h' not in src
+    # the block loop of the family (x3_strip.hip's d = 256 kernels launder their own hb: they are not this family's)
+    marker = 'asm volatile("" : "+v"(hb))'
+    assert src['small_strip.h'].count(marker) == 1 and src['bs_strip.hip'].count(marker) == 0
+    tail = src['x3_strip.hip'][src['x3_strip.hip'].index('struct X3Stream'):]
+    assert tail.count(marker) == 0 and all('#include "small_strip.h"' in s for s in small[1:])
+
+
 def test_the_guard_test_op_is_a_single_launch_that_writes_its_sentinel():
     '''test_second_device_is_refused_before_anything_is_enqueued tells guard-before-launch from guard-after-launch only if the FIRST launch of
     the refused call writes the tensor that carries the sentinel: hftt_adam_step is one launch, and adam_kernel updates p, m, v in place.'''
