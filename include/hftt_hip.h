@@ -474,6 +474,67 @@ typedef struct {
 } hftt_resample_desc;
 int hftt_resample(const hftt_resample_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Note decoding on the device (csrc/notes.hip).  These entry points were ADDED at ABI 8: HFTT_ABI_VERSION stays 8, because nothing that an
+ * ABI-8 caller binds changed -- a caller that needs them looks the symbols up and treats their absence as an older library.
+ *
+ * Stitch (model/amt.py:104-113 transcript, :155-176 transcript_stride; the velocity argmax of :107,113): per clip c < b of one model call,
+ * rows src0 .. src0 + len of the [b, T, N] fp32 posteriors onset / offset / mpe go to rows dst[c] .. dst[c] + len of the [F, N] fp32 rolls,
+ * and for the same rows roll_velocity [F, N] int8 receives the argmax over the last axis of the [b, T, N, V] fp32 velocity logits (ties: the
+ * lowest index, as torch.argmax / numpy.argmax; NaN counts as the maximum).  transcript: src0 = 0, len = T; transcript_stride:
+ * src0 = n_offset, len = T / 2.  Rows that no clip covers are not touched.  No atomics: every element has one writer, so the row ranges of
+ * the clips must not overlap.  `dst` is a HOST array of b ints (read during the call, b <= HFTT_STITCH_MAX_CLIPS); every other pointer is
+ * device memory.  With V % 4 == 0 and a 16-byte aligned `velocity` the logits are read with 16-byte loads.
+ * --------------------------------------------------------------------------------------------- */
+#define HFTT_STITCH_MAX_CLIPS 64
+typedef struct {
+  int32_t b, T, N, V;          /* clips of this call, frames per clip, notes (1..128), velocity classes (1..128) */
+  int32_t src0, len;           /* 1 <= len <= T, 0 <= src0 <= T - len */
+  int64_t F;                   /* rows of the rolls */
+  const void* onset; const void* offset; const void* mpe;        /* fp32 [b, T, N] */
+  const void* velocity;                                          /* fp32 [b, T, N, V] logits */
+  void* roll_onset; void* roll_offset; void* roll_mpe;           /* fp32 [F, N] */
+  void* roll_velocity;                                           /* int8 [F, N] */
+  const int32_t* dst;          /* HOST [b]: first roll row of each clip, 0 <= dst[c] <= F - len */
+} hftt_stitch_desc;
+int hftt_stitch(const hftt_stitch_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Notes (model/amt.py:179-341 mpe2note, up to but without the final sort of :343): the rolls of one file -> its notes, in caller-supplied
+ * arrays of capacity `cap`, pitch-major and by ascending onset frame within a pitch (the order of a_note in front of :343).
+ *   peaks (:193-253)   every frame of a plateau is a peak when its value is >= the threshold and the nearest DIFFERENT value on each side is
+ *                      smaller or absent (a constant track above the threshold has F peaks: up to N * F notes exist).  Time: loc * hop_sec in
+ *                      double at frame 0, at F - 1 and between equal neighbours l == r; else float32(loc * hop_sec) - h2 * (l - r) / (c - r)
+ *                      for l > r, + h2 * (r - l) / (c - l) for l < r, with h2 = float32(hop_sec / 2), in fp32 (subtract, multiply,
+ *                      correctly rounded divide, subtract; no contraction), widened to double.
+ *   per onset (:255-336)  next onset = the next onset peak, or (F, (F - 1) * hop_sec); offset peak = the first with loc > loc_onset, clipped
+ *                      to the next onset; mpe end = the first frame of [loc_onset + 1, loc_next) below thred_mpe, at loc * hop_sec; the note's
+ *                      offset by the two flags and mode_offset; mode_velocity 0 drops velocity 0.
+ *   trim (:338-341)    between consecutive KEPT notes of one pitch: prev.offset = next.onset when next.onset < prev.offset.
+ * Thresholds are floats: the reference compares float32 rolls with a Python scalar, i.e. in float32.  *n_notes receives the number of notes
+ * that EXIST; when it exceeds cap, records 0 .. cap are written, nothing behind them, and the caller repeats the call with more room.
+ * The order is deterministic (prefix sums, no atomics).  ws: hftt_notes_ws_bytes(F, N) bytes, contents irrelevant on entry.  F == 0: *n_notes
+ * = 0, no kernel.  Frames are handled in chunks of HFTT_NOTES_CHUNK: one workgroup per pitch walks the chunks once forward and once backward
+ * carrying two ints per track, then one workgroup per (chunk, pitch) writes the notes.
+ * --------------------------------------------------------------------------------------------- */
+#define HFTT_NOTES_CHUNK 256
+typedef struct {
+  int64_t F; int32_t N; int32_t note_min;                        /* frames, notes (1..128), pitch of note 0 */
+  const void* onset; const void* offset; const void* mpe;        /* fp32 [F, N] */
+  const void* velocity;                                          /* int8 [F, N] */
+  float thred_onset, thred_offset, thred_mpe;
+  int32_t mode_velocity;       /* 0 = ignore_zero, 1 = org */
+  int32_t mode_offset;         /* 0 = shorter, 1 = longer, 2 = offset */
+  int32_t cap;                 /* capacity of the four output arrays, >= 0 */
+  double hop_sec;
+  void* out_pitch; void* out_velocity;                           /* int32 [cap] */
+  void* out_onset; void* out_offset;                             /* double [cap] */
+  void* n_notes;                                                 /* int32 [1] */
+  void* ws; int64_t ws_bytes;
+} hftt_notes_desc;
+int64_t hftt_notes_ws_bytes(int64_t F, int32_t N);
+int hftt_notes_decode(const hftt_notes_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

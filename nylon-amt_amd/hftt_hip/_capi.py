@@ -150,6 +150,29 @@ class ResampleDesc(C.Structure):
                 ('out', c_f32p), ('n_out', C.c_int64)]
 
 
+STITCH_MAX_CLIPS = 64                       # HFTT_STITCH_MAX_CLIPS
+NOTES_CHUNK = 256                           # HFTT_NOTES_CHUNK
+
+
+class StitchDesc(C.Structure):
+    _fields_ = [('b', C.c_int32), ('T', C.c_int32), ('N', C.c_int32), ('V', C.c_int32),
+                ('src0', C.c_int32), ('len', C.c_int32), ('F', C.c_int64),
+                ('onset', C.c_void_p), ('offset', C.c_void_p), ('mpe', C.c_void_p), ('velocity', C.c_void_p),
+                ('roll_onset', C.c_void_p), ('roll_offset', C.c_void_p), ('roll_mpe', C.c_void_p), ('roll_velocity', C.c_void_p),
+                ('dst', C.POINTER(C.c_int32))]
+
+
+class NotesDesc(C.Structure):
+    _fields_ = [('F', C.c_int64), ('N', C.c_int32), ('note_min', C.c_int32),
+                ('onset', C.c_void_p), ('offset', C.c_void_p), ('mpe', C.c_void_p), ('velocity', C.c_void_p),
+                ('thred_onset', C.c_float), ('thred_offset', C.c_float), ('thred_mpe', C.c_float),
+                ('mode_velocity', C.c_int32), ('mode_offset', C.c_int32), ('cap', C.c_int32),
+                ('hop_sec', C.c_double),
+                ('out_pitch', C.c_void_p), ('out_velocity', C.c_void_p), ('out_onset', C.c_void_p), ('out_offset', C.c_void_p),
+                ('n_notes', C.c_void_p),
+                ('ws', C.c_void_p), ('ws_bytes', C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/hftt_hip.h declares
 SIGNATURES = {
     'hftt_abi_version': (C.c_int, []),
@@ -193,6 +216,9 @@ SIGNATURES = {
                                  C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     'hftt_logmel': (C.c_int, [C.POINTER(LogmelDesc), C.c_void_p]),
     'hftt_resample': (C.c_int, [C.POINTER(ResampleDesc), C.c_void_p]),
+    'hftt_stitch': (C.c_int, [C.POINTER(StitchDesc), C.c_void_p]),
+    'hftt_notes_ws_bytes': (C.c_int64, [C.c_int64, C.c_int32]),
+    'hftt_notes_decode': (C.c_int, [C.POINTER(NotesDesc), C.c_void_p]),
 }
 
 _lib = None

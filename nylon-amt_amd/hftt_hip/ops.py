@@ -10,7 +10,8 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (AttnDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LnBwdDesc, LogmelDesc, LossDesc, ResampleDesc, PrepEntry, StripDesc, StripPackEntry,
+from ._capi import (AttnDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry,
+                    NOTES_CHUNK, STITCH_MAX_CLIPS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
                     ATTN_Q_F16PAIR, ATTN_KV_F16PAIR, check, lib)
 
@@ -562,3 +563,113 @@ def resample(wave_mono, sr_in, sr_out):
     d.out, d.n_out = out.data_ptr(), n_out
     check(lib().hftt_resample(C.byref(d), _stream(wave.device)), 'resample')
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# note decoding on the device (model/amt.py transcript / transcript_stride / mpe2note; csrc/notes.hip)
+# ------------------------------------------------------------------------------------------------
+MODE_VELOCITY = {'ignore_zero': 0, 'org': 1}
+MODE_OFFSET = {'shorter': 0, 'longer': 1, 'offset': 2}
+
+
+def stitch(onset, offset, mpe, velocity, rolls, dst, src0=0, length=None):
+    """One model call's outputs -> the file-long rolls (hftt_stitch).  onset / offset / mpe [b, T, N] fp32 and velocity [b, T, N, V] fp32 logits
+    (device tensors); rolls = (onset, offset, mpe fp32 [F, N], velocity int8 [F, N]) device tensors, written in place: rows src0 .. src0 + length
+    of clip c go to rows dst[c] .. dst[c] + length, the velocity roll receives the argmax over V.  dst: b ints (host)."""
+    _need_cuda(onset, offset, mpe, velocity, *rolls)
+    b, T, N = onset.shape
+    V = velocity.shape[3]
+    length = T if length is None else int(length)
+    srcs = [t if t.is_contiguous() else t.contiguous() for t in (onset, offset, mpe, velocity)]
+    for t, shape in zip(srcs, ((b, T, N),) * 3 + ((b, T, N, V),)):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise HfttError('stitch: the model outputs must be fp32 [b, T, N] and [b, T, N, V]')
+    F = rolls[0].shape[0]
+    for t, dt in zip(rolls, (torch.float32,) * 3 + (torch.int8,)):
+        if t.dtype != dt or tuple(t.shape) != (F, N) or not t.is_contiguous():
+            raise HfttError('stitch: the rolls must be contiguous [F, N] tensors, three fp32 and one int8')
+    dst = [int(x) for x in dst]
+    if len(dst) != b:
+        raise HfttError('stitch: %d first rows for %d clips' % (len(dst), b))
+    L = lib()
+    for c0 in range(0, b, STITCH_MAX_CLIPS):
+        nb = min(STITCH_MAX_CLIPS, b - c0)
+        d = StitchDesc()
+        d.b, d.T, d.N, d.V, d.src0, d.len, d.F = nb, T, N, V, int(src0), length, F
+        d.onset, d.offset, d.mpe, d.velocity = (t[c0:c0 + nb].data_ptr() for t in srcs)
+        d.roll_onset, d.roll_offset, d.roll_mpe, d.roll_velocity = (t.data_ptr() for t in rolls)
+        host_dst = (C.c_int32 * nb)(*dst[c0:c0 + nb])
+        d.dst = host_dst
+        check(L.hftt_stitch(C.byref(d), _stream(onset.device)), 'stitch')
+    return rolls
+
+
+def _notes_packed(onset, offset, mpe, velocity, thred_onset, thred_offset, thred_mpe, hop_sec, note_min, mode_velocity, mode_offset, cap):
+    """hftt_notes_decode into ONE device buffer (int8): [n_notes int32, pad to 8 | onset double cap | offset double cap | pitch int32 cap |
+    velocity int32 cap], so that the caller fetches the compact list with a single copy."""
+    _need_cuda(onset, offset, mpe, velocity)
+    if mode_velocity not in MODE_VELOCITY or mode_offset not in MODE_OFFSET:
+        raise HfttError('notes_decode: mode_velocity %r / mode_offset %r unknown' % (mode_velocity, mode_offset))
+    F, N = onset.shape
+    for t, dt in ((onset, torch.float32), (offset, torch.float32), (mpe, torch.float32), (velocity, torch.int8)):
+        if t.dtype != dt or tuple(t.shape) != (F, N) or not t.is_contiguous():
+            raise HfttError('notes_decode: the rolls must be contiguous [F, N] tensors, three fp32 and one int8')
+    L = lib()
+    dev = onset.device
+    ws_bytes = L.hftt_notes_ws_bytes(F, N)
+    ws = torch.empty(ws_bytes, dtype=torch.int8, device=dev)
+    buf = torch.empty(8 + 24 * cap, dtype=torch.int8, device=dev)
+    base = buf.data_ptr()
+    d = NotesDesc()
+    d.F, d.N, d.note_min = F, N, int(note_min)
+    d.onset, d.offset, d.mpe, d.velocity = onset.data_ptr(), offset.data_ptr(), mpe.data_ptr(), velocity.data_ptr()
+    # the host compares a float32 roll with a Python scalar: the scalar is rounded to float32 (NumPy 2 promotion)
+    d.thred_onset, d.thred_offset, d.thred_mpe = float(np.float32(thred_onset)), float(np.float32(thred_offset)), float(np.float32(thred_mpe))
+    d.mode_velocity, d.mode_offset, d.cap = MODE_VELOCITY[mode_velocity], MODE_OFFSET[mode_offset], cap
+    d.hop_sec = float(hop_sec)
+    d.n_notes = base
+    d.out_onset, d.out_offset, d.out_pitch, d.out_velocity = base + 8, base + 8 + 8 * cap, base + 8 + 16 * cap, base + 8 + 20 * cap
+    d.ws, d.ws_bytes = ws.data_ptr(), ws_bytes
+    check(L.hftt_notes_decode(C.byref(d), _stream(dev)), 'notes_decode')
+    return buf
+
+
+def _notes_unpack(buf, cap):
+    """views of the packed buffer (device or host): total, onset, offset, pitch, velocity"""
+    total = int(buf[:4].view(torch.int32)[0])
+    n = min(total, cap)
+    onset = buf[8:8 + 8 * cap].view(torch.float64)[:n]
+    offset = buf[8 + 8 * cap:8 + 16 * cap].view(torch.float64)[:n]
+    pitch = buf[8 + 16 * cap:8 + 20 * cap].view(torch.int32)[:n]
+    velocity = buf[8 + 20 * cap:8 + 24 * cap].view(torch.int32)[:n]
+    return total, onset, offset, pitch, velocity
+
+
+def notes_default_capacity(F, N):
+    """room for the notes of a first call: every frame of every pitch can be a note (N * F), real files hold far fewer"""
+    return min(N * F, max(4096, N * F // 32))
+
+
+def notes_decode(onset, offset, mpe, velocity, hop_sec, note_min=21, thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5,
+                 mode_velocity='ignore_zero', mode_offset='shorter', capacity=None, host=False):
+    """The rolls of one file (device tensors: onset / offset / mpe fp32 [F, N], velocity int8 [F, N]) -> (pitch int32, velocity int32, onset
+    float64, offset float64), the notes of AMT.mpe2note in front of its final sort: pitch-major, ascending onset frame (hftt_notes_decode).
+    The wrapper sizes the workspace and the capacity; when more notes exist than fit it runs once more with the exact count -- unless the caller
+    fixed capacity=, then it raises HfttError.  host=True: the four arrays come back as host tensors, fetched with one copy of the packed list."""
+    _need_cuda(onset, offset, mpe, velocity)
+    F, N = onset.shape
+    cap = notes_default_capacity(F, N) if capacity is None else int(capacity)
+    args = (onset, offset, mpe, velocity, thred_onset, thred_offset, thred_mpe, hop_sec, note_min, mode_velocity, mode_offset)
+    buf = _notes_packed(*args, cap)
+    if host:
+        buf = buf.cpu()
+    total, t_on, t_off, pitch, vel = _notes_unpack(buf, cap)
+    if total > cap:
+        if capacity is not None:
+            raise HfttError('notes_decode: %d notes exist, capacity=%d' % (total, cap))
+        cap = total
+        buf = _notes_packed(*args, cap)
+        if host:
+            buf = buf.cpu()
+        total, t_on, t_off, pitch, vel = _notes_unpack(buf, cap)
+    return pitch, vel, t_on, t_off

@@ -2,6 +2,7 @@
 
 Same surface as hftt_code/model/amt.py: ``AMT(config, model_path, batch_size=1, verbose_flag=False)``,
 ``wav2feature`` (:34), ``transcript`` (:66), ``transcript_stride`` (:121), ``mpe2note`` (:179), ``note2midi`` (:347).
+One addition: ``transcript_notes`` = ``mpe2note(*transcript(...))`` with the rolls and the decoding kept on the device (csrc/notes.hip).
 Differences in mechanism, not in results:
   * wav2feature runs the log-mel kernel of libhftt_hip.so (STFT + sparse mel + log on the GPU) instead of torchaudio;
   * transcript/transcript_stride gather ALL clip windows of a file and run them through the model in batches of
@@ -73,8 +74,9 @@ class AMT():
         wave, sr = _load_wav(f_wav)                       # [channels, n] float32 in [-1, 1)
         return self.wave2feature(torch.from_numpy(wave), sr)
 
-    def wave2feature(self, wave, sr):
-        """wave [channels, n] or [n] float tensor at sample rate sr -> log-mel [n_frames, n_mels] (CPU tensor like the reference)."""
+    def wave2feature(self, wave, sr, on_device=False):
+        """wave [channels, n] or [n] float tensor at sample rate sr -> log-mel [n_frames, n_mels] (CPU tensor like the reference;
+        on_device=True: the device tensor as the kernel left it, for transcript_notes)."""
         from hftt_hip import ops
         fe = self.config['feature']
         if not str(self.device).startswith('cuda'):
@@ -89,7 +91,7 @@ class AMT():
             self._logmel = ops.LogMel(self.device, sr=fe['sr'], n_fft=fe['fft_bins'], hop=fe['hop_sample'], n_mels=fe['mel_bins'],
                                       log_offset=fe['log_offset'])
         feat = self._logmel(wave_mono.to(self.device))
-        return feat.cpu()
+        return feat if on_device else feat.cpu()
 
     # ------------------------------------------------------------------ clip windowing + batched inference
     def _run_windows(self, a_input, starts, mode, ablation_flag):
@@ -206,6 +208,61 @@ class AMT():
                 full[i:i + half_frame] = r[c][n_offset:n_offset + half_frame]
             outs.append(full)
         return tuple(outs)
+
+    # ------------------------------------------------------------------ features -> notes without leaving the device
+    def transcript_notes(self, a_feature, n_offset=None, output='B', thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5,
+                         mode_velocity='ignore_zero', mode_offset='shorter'):
+        """The note list of ``mpe2note(*transcript(a_feature)[4:8], ...)`` (output='A': ``[0:4]``; with n_offset: of ``transcript_stride(a_feature,
+        n_offset)``), bit for bit, with everything between the features and the compact note list on the device: padding with min_value and
+        window slicing (torch as plumbing), one model call per batch, hftt_stitch per batch straight into the file-long rolls (velocity argmax
+        included), hftt_notes_decode once, ONE small device->host copy, and the final stable (onset, pitch) sort (amt.py:343) on the host.
+        a_feature [n_frames, n_bins]: a numpy array or a device tensor (``wave2feature(..., on_device=True)``).
+        One process, one GPU: with world > 1 this raises HfttError -- sharded inference keeps transcript / transcript_stride + mpe2note.
+        There is no CPU fallback."""
+        from hftt_hip import ops
+        if self.world > 1:
+            raise HfttError('transcript_notes runs on one GPU (world = %d): sharded inference uses transcript / transcript_stride + mpe2note' % self.world)
+        if output not in ('A', 'B'):
+            raise HfttError("output must be 'A' (heads 0-3) or 'B' (heads 5-8)")
+        if not str(self.device).startswith('cuda'):
+            raise HfttError('transcript_notes decodes on the device: a ROCm device is required (there is no CPU fallback)')
+        cin, cf, cm = self.config['input'], self.config['feature'], self.config['midi']
+        T, N = cin['num_frame'], cm['num_note']
+        if torch.is_tensor(a_feature):
+            ops._need_cuda(a_feature)
+            x = a_feature.to(device=self.device, dtype=torch.float32)
+        else:
+            x = torch.from_numpy(np.array(a_feature, dtype=np.float32)).to(self.device)
+        n = x.shape[0]
+        if n_offset is None:                                                    # transcript (amt.py:66-118)
+            step, src0, front = T, 0, cin['margin_b']
+            len_s = int(np.ceil(n / T) * T) - n
+            back = len_s + cin['margin_f']
+        else:                                                                   # transcript_stride (amt.py:121-176)
+            step, src0, front = int(T / 2), int(n_offset), cin['margin_b'] + int(n_offset)
+            tmp_len = n + cin['margin_b'] + cin['margin_f'] + step
+            len_s = int(np.ceil(tmp_len / step) * step) - tmp_len
+            back = len_s + cin['margin_f'] + (step - int(n_offset))
+        F = n + len_s
+        a_input = torch.full((front + n + back, cf['n_bins']), cin['min_value'], dtype=torch.float32, device=self.device)
+        a_input[front:front + n] = x
+        width = cin['margin_b'] + T + cin['margin_f']
+        starts = list(range(0, n, step))
+        rolls = tuple(torch.zeros(F, N, dtype=torch.int8 if k == 3 else torch.float32, device=self.device) for k in range(4))
+        h0 = 0 if output == 'A' else 5
+        self.model.eval()
+        for b0 in range(0, len(starts), self.batch_size):
+            batch = starts[b0:b0 + self.batch_size]
+            spec = torch.stack([a_input[i:i + width].T for i in batch], dim=0)   # [b, n_bins, width] (amt.py:89)
+            with torch.no_grad():
+                o = self.model(spec)
+            ops.stitch(o[h0], o[h0 + 1], o[h0 + 2], o[h0 + 3], rolls, batch, src0=src0, length=step)
+        hop_sec = float(cf['hop_sample'] / cf['sr'])
+        pitch, velocity, onset, offset = ops.notes_decode(*rolls, hop_sec, note_min=cm['note_min'], thred_onset=thred_onset, thred_offset=thred_offset,
+                                                          thred_mpe=thred_mpe, mode_velocity=mode_velocity, mode_offset=mode_offset, host=True)
+        pitch, velocity, onset, offset = pitch.numpy(), velocity.numpy(), onset.numpy(), offset.numpy()
+        order = np.lexsort((pitch, onset))                                      # stable: by onset, then pitch, then the order of a_note (amt.py:343)
+        return [{'pitch': int(pitch[i]), 'onset': float(onset[i]), 'offset': float(offset[i]), 'velocity': int(velocity[i])} for i in order]
 
     # ------------------------------------------------------------------ posteriorgram -> notes (amt.py:179-344)
     def mpe2note(self, a_onset=None, a_offset=None, a_mpe=None, a_velocity=None, thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5,

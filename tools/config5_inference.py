@@ -40,8 +40,22 @@ def run():
     t4 = time.time()
     return feat, outs, est, (t1 - t0, t2 - t1, t3 - t2, t4 - t3)
 
-run()                                               # warm-up (plans, workspaces)
-feat, outs, est, (t_fe, t_model, t_dec, t_midi) = run()
+def run_device():
+    """features -> sorted note list with the rolls and the decoding on the device (AMT.transcript_notes; csrc/notes.hip)"""
+    feat_dev = amt.wave2feature(wave.unsqueeze(0), sr, on_device=True)
+    torch.cuda.synchronize(); t1 = time.time()
+    est_dev = amt.transcript_notes(feat_dev)
+    t2 = time.time()                               # (the note list is on the host: nothing left in flight)
+    return est_dev, t2 - t1
+
+run(); run_device()                                 # warm-up (plans, workspaces)
+ab = {'host_transcript_plus_mpe2note': [], 'device_transcript_notes': []}
+for _ in range(5):                                  # interleaved, same process, same box (DESIGN.md section 8: A/B rule)
+    feat, outs, est, (t_fe, t_model, t_dec, t_midi) = run()
+    est_dev, t_dev = run_device()
+    ab['host_transcript_plus_mpe2note'].append(round(t_model + t_dec, 5))
+    ab['device_transcript_notes'].append(round(t_dev, 5))
+assert est_dev == est, 'the device note list differs from the host path'
 n_clips = -(-(feat.shape[0]) // 128)
 ref_roll = np.zeros((feat.shape[0], 88), bool)
 for n in notes:
@@ -49,6 +63,8 @@ for n in notes:
 line = {'workload': 'config 5: 60 s synthetic audio -> log-mel -> %d clips (paper size, %s mode, random-init weights) -> notes -> MIDI' % (n_clips, precision),
         'frames': int(feat.shape[0]), 'clips': n_clips,
         'seconds': {'logmel': round(t_fe, 4), 'model': round(t_model, 4), 'mpe2note_cpu': round(t_dec, 4), 'note2midi_cpu': round(t_midi, 4)},
+        'features_to_sorted_notes_seconds_interleaved': ab,
+        'features_to_sorted_notes_median': {k: sorted(v)[len(v) // 2] for k, v in ab.items()},
         'clips_per_s_model': round(n_clips / t_model, 1), 'clips_per_s_end_to_end': round(n_clips / (t_fe + t_model + t_dec + t_midi), 1),
         'audio_seconds_per_second_end_to_end': round(dur / (t_fe + t_model + t_dec + t_midi), 1),
         'scores_vs_generating_notes_RANDOM_WEIGHTS_no_accuracy_meaning': {
