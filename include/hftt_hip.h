@@ -535,6 +535,59 @@ typedef struct {
 int64_t hftt_notes_ws_bytes(int64_t F, int32_t N);
 int hftt_notes_decode(const hftt_notes_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Label rendering on the device (csrc/labels.hip): note lists -> the frame labels that training consumes, the opposite direction of the
+ * decoder above (corpus/conv_note2label.py:8-111 note2label).  Like the note decoder this entry point was ADDED at ABI 8 and HFTT_ABI_VERSION
+ * stays 8: a caller that needs it looks the symbol up.
+ *
+ * Note table (device memory, corpus-wide, built once by the caller): `notes` holds the records of every file grouped by (file, pitch) -- group
+ * g = file * N + pitch is records row_ptr[g] .. row_ptr[g + 1] -- and inside a group in the ORDER OF THE CALLER'S NOTE LIST (never sorted by
+ * time: the order decides the velocity where onset triangles overlap).  flags bit 0 = "no offset target": the note's offset equals, as a
+ * double, the onset of a note of the same pitch in the same file (:76-83).  file_nframe[file] = int(max offset * fps + 0.5) + 1 (:20-27), 1
+ * for a file without notes.
+ *
+ * Request: B windows of `len` frames; window b shows frames win_start[b] .. win_start[b] + len of file win_file[b], counted from the file's
+ * frame 0 (win_start may be negative or lie behind the file).  win_file / win_start are DEVICE arrays: nothing is read on the host.  Frames
+ * outside [0, file_nframe) -- and every frame of a window whose file index is outside 0 .. n_files -- are zero in all four tracks.
+ *
+ * One output element = frame f of one pitch: walk the group's notes in table order carrying o, off (fp32), mpe, vel (all 0 at the start):
+ *   on_f = (int)(onset * fps + 0.5), off_f = (int)(offset * fps + 0.5), on_ms = onset * 1000.0, off_ms = offset * 1000.0            (:37-43)
+ *   sharp = tol, with duration_tolerance: max(tol, (int)((off_ms - on_ms) * 0.2 / hop_ms + 0.5))                                    (:46-48)
+ *   |f - on_f| <= tol:  o = max(o, (float)max(0.0, 1.0 - fabs(f * hop_ms - on_ms) / (tol * hop_ms)));                               (:53-70)
+ *                       o >= 0.5f and (f >= on_f or vel == 0): vel = velocity     (the VALUE vel == 0 is tested, after the max)
+ *   on_f <= f <= off_f: mpe = 1                                                                                                     (:72-74)
+ *   bit 0 clear and |f - off_f| <= sharp: off = max(off, the same triangle around off_ms with half-width sharp)                     (:85-97)
+ * in fp64 without contraction and with IEEE division: operation for operation the reference's arithmetic, so the result is bit-identical to
+ * it.  hop_ms = 1000 * hop_sample / sr, fps = sr / hop_sample and tol = int(50.0 / hop_ms + 0.5) come from the host, computed as there.
+ *
+ * form HFTT_LABELS_TRAIN: onset / offset / mpe fp32 [B, len, N], velocity int64 (what the loss takes); HFTT_LABELS_STORE: onset / offset fp32,
+ * mpe uint8, velocity int8 (the dtypes of the stored tracks).  One launch; a workgroup owns (window, pitch, HFTT_LABELS_CHUNK frames), filters
+ * the pitch's notes against its frame range HFTT_LABELS_CHUNK at a time into LDS in order (prefix sum), and each frame walks the survivors.
+ * One writer per element, no atomics, no workspace.
+ * --------------------------------------------------------------------------------------------- */
+#define HFTT_LABELS_CHUNK 256
+#define HFTT_LABELS_TRAIN 0
+#define HFTT_LABELS_STORE 1
+typedef struct {
+  double onset_sec, offset_sec;
+  int32_t velocity;
+  int32_t flags;               /* bit 0: no offset target */
+} hftt_label_note;
+typedef struct {
+  const hftt_label_note* notes;                                  /* [n_notes] (may be NULL when n_notes == 0) */
+  const int32_t* row_ptr;                                        /* [n_files * N + 1] */
+  const int32_t* file_nframe;                                    /* [n_files] */
+  const int32_t* win_file; const int32_t* win_start;             /* [B] */
+  int32_t n_files, n_notes;
+  int32_t B, len, N;           /* windows, frames per window, notes (1..128); B * len * N < 2^31 */
+  int32_t tol;                 /* >= 1 */
+  int32_t duration_tolerance;  /* 0 / 1 */
+  int32_t form;                /* HFTT_LABELS_TRAIN / HFTT_LABELS_STORE */
+  double hop_ms, fps;
+  void* onset; void* offset; void* mpe; void* velocity;          /* [B, len, N] */
+} hftt_labels_desc;
+int hftt_labels_render(const hftt_labels_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,9 @@
 pickles): the corpus is ONE array per tensor, each file preceded / followed by padding so that every clip window of a file stays inside
 its own padding -- ``margin_b`` rows first, then per file ``n_i`` rows of data followed by ``margin_f + num_frame - 1`` rows of padding;
 ``idx`` lists the first frame of every clip (every frame of every file).  The feature padding value is ``log(log_offset)`` (:105-113),
-label padding is zero.  ``synth_store`` fills such a store with the synthetic recipe of SURVEY.md section 8(d) config 1."""
+label padding is zero.  ``assemble_note_store`` lays out the same ``feature`` and ``idx`` but keeps the NOTES of every file instead of four label
+tracks (training.dataset.NoteClipStore renders a batch's labels from them when it gathers it).  ``synth_store`` fills such a store with the
+synthetic recipe of SURVEY.md section 8(d) config 1."""
 import numpy as np
 
 
@@ -36,6 +38,23 @@ def assemble_store(features, labels, config):
         loc_d += n + gap
     return {'feature': feature, 'label_onset': lab['onset'], 'label_offset': lab['offset'], 'label_mpe': lab['mpe'],
             'label_velocity': lab['velocity'], 'idx': idx}
+
+
+def assemble_note_store(features, notes_per_file, config):
+    """features: list of [n_i, mel_bins] fp32; notes_per_file: one note list per file (what note2label takes).  -> dict(feature, idx: exactly
+    as assemble_store lays them out for the labels note2label would make of those notes; file_row0: int64 [n_files], the store row of every
+    file's frame 0; table: the host half of the note table (hftt_hip.ops.labels_table_host) that NoteClipStore uploads)."""
+    from hftt_hip.ops import labels_table_host
+    table = labels_table_host(notes_per_file, config)
+    cin, cm = config['input'], config['midi']
+    gap = cin['margin_f'] + cin['num_frame'] - 1
+    nf = np.array([max(f.shape[0], int(n)) for f, n in zip(features, table['file_nframe'])], np.int64)      # make_dataset.py:52
+    file_row0 = cin['margin_b'] + np.concatenate([[0], np.cumsum(nf + gap)[:-1]]).astype(np.int64)
+    # the feature / idx half of assemble_store: its label half sees only the LENGTH of each file's tracks
+    empty = [{k: np.zeros((int(n), 0), dt) for k, dt in (('onset', np.float32), ('offset', np.float32), ('mpe', bool), ('velocity', np.int8))}
+             for n in table['file_nframe']]
+    store = assemble_store(features, empty, dict(config, midi=dict(cm, num_note=0)))
+    return {'feature': store['feature'], 'idx': store['idx'], 'file_row0': file_row0, 'table': table}
 
 
 def prepare_config(config, max_value=0.0):

@@ -173,6 +173,23 @@ class NotesDesc(C.Structure):
                 ('ws', C.c_void_p), ('ws_bytes', C.c_int64)]
 
 
+LABELS_CHUNK = 256                          # HFTT_LABELS_CHUNK
+LABELS_TRAIN, LABELS_STORE = 0, 1           # HFTT_LABELS_TRAIN / HFTT_LABELS_STORE
+
+
+class LabelNote(C.Structure):
+    _fields_ = [('onset_sec', C.c_double), ('offset_sec', C.c_double), ('velocity', C.c_int32), ('flags', C.c_int32)]
+
+
+class LabelsDesc(C.Structure):
+    _fields_ = [('notes', C.c_void_p), ('row_ptr', C.c_void_p), ('file_nframe', C.c_void_p), ('win_file', C.c_void_p), ('win_start', C.c_void_p),
+                ('n_files', C.c_int32), ('n_notes', C.c_int32),
+                ('B', C.c_int32), ('len', C.c_int32), ('N', C.c_int32), ('tol', C.c_int32),
+                ('duration_tolerance', C.c_int32), ('form', C.c_int32),
+                ('hop_ms', C.c_double), ('fps', C.c_double),
+                ('onset', C.c_void_p), ('offset', C.c_void_p), ('mpe', C.c_void_p), ('velocity', C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/hftt_hip.h declares
 SIGNATURES = {
     'hftt_abi_version': (C.c_int, []),
@@ -219,6 +236,7 @@ SIGNATURES = {
     'hftt_stitch': (C.c_int, [C.POINTER(StitchDesc), C.c_void_p]),
     'hftt_notes_ws_bytes': (C.c_int64, [C.c_int64, C.c_int32]),
     'hftt_notes_decode': (C.c_int, [C.POINTER(NotesDesc), C.c_void_p]),
+    'hftt_labels_render': (C.c_int, [C.POINTER(LabelsDesc), C.c_void_p]),
 }
 
 _lib = None

@@ -10,8 +10,8 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (AttnDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry,
-                    NOTES_CHUNK, STITCH_MAX_CLIPS,
+from ._capi import (AttnDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry,
+                    LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, STITCH_MAX_CLIPS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
                     ATTN_Q_F16PAIR, ATTN_KV_F16PAIR, check, lib)
 
@@ -673,3 +673,124 @@ def notes_decode(onset, offset, mpe, velocity, hop_sec, note_min=21, thred_onset
             buf = buf.cpu()
         total, t_on, t_off, pitch, vel = _notes_unpack(buf, cap)
     return pitch, vel, t_on, t_off
+
+
+# ------------------------------------------------------------------------------------------------
+# Labels from note lists (hftt_labels_render): the corpus keeps notes, a batch's labels are rendered when it is gathered
+LABEL_NOTE = np.dtype([('onset_sec', np.float64), ('offset_sec', np.float64), ('velocity', np.int32), ('flags', np.int32)])
+assert LABEL_NOTE.itemsize == C.sizeof(LabelNote)
+LABELS_FORM = {'train': LABELS_TRAIN, 'store': LABELS_STORE}
+
+
+def labels_grid(config):
+    """(hop_ms, fps, tol) as the reference forms them (corpus/conv_note2label.py:11-13,20)"""
+    cf = config['feature']
+    hop_ms = 1000 * cf['hop_sample'] / cf['sr']
+    return hop_ms, cf['sr'] / cf['hop_sample'], int(50.0 / hop_ms + 0.5)
+
+
+def labels_table_host(notes_per_file, config):
+    """The note table of hftt_labels_render as numpy arrays: notes_per_file = one note list per file (dicts with 'pitch', 'onset', 'offset' in
+    seconds and 'velocity', as note2label takes them) -> dict(notes [n] LABEL_NOTE records grouped by (file, pitch) and inside a group in LIST
+    order, row_ptr int32 [n_files * N + 1], file_nframe int32 [n_files], N, hop_ms, fps, tol).  Raises HfttError for a note outside the
+    reference's working domain (there it indexes out of range or overflows int8)."""
+    cm = config['midi']
+    N, note_min = int(cm['num_note']), int(cm['note_min'])
+    hop_ms, fps, tol = labels_grid(config)
+    n_files = len(notes_per_file)
+    if n_files < 1:
+        raise HfttError('labels_table: no files')
+    if not 1 <= N <= 128 or n_files * N + 1 >= 1 << 31:
+        raise HfttError('labels_table: num_note=%d outside 1..128 (or too many files)' % N)
+    if tol < 1:
+        raise HfttError('labels_table: tol=%d: a hop of %g ms leaves the 50 ms triangle no frame' % (tol, hop_ms))
+    counts = np.array([len(a) for a in notes_per_file], np.int64)
+    flat = [n for a in notes_per_file for n in a]
+    try:
+        pitch = np.array([n['pitch'] for n in flat], np.float64)
+        velocity = np.array([n['velocity'] for n in flat], np.float64)
+        onset = np.array([n['onset'] for n in flat], np.float64) + 0.0          # (-0.0 -> +0.0)
+        offset = np.array([n['offset'] for n in flat], np.float64) + 0.0
+    except (KeyError, TypeError, ValueError) as e:
+        raise HfttError('labels_table: a note needs numeric pitch / onset / offset / velocity (%r)' % (e,))
+    file = np.repeat(np.arange(n_files), counts)
+
+    def refuse(bad, what):
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise HfttError('labels_table: file %d, note %d: %s (%r)' % (file[i], i - int(counts[:file[i]].sum()), what, flat[i]))
+    refuse(~((pitch == np.floor(pitch)) & (pitch >= note_min) & (pitch <= note_min + N - 1)), 'pitch outside note_min .. note_min + num_note - 1 = %d .. %d' % (note_min, note_min + N - 1))
+    refuse(~((onset >= 0.0) & (onset <= offset)), 'needs 0 <= onset <= offset')
+    refuse(~(offset * fps + 0.5 < float((1 << 31) - 1)), 'offset beyond 2^31 frames')
+    refuse(~((velocity == np.floor(velocity)) & (velocity >= 0) & (velocity <= 127)), 'velocity outside 0..127')
+    if len(flat) >= 1 << 31:
+        raise HfttError('labels_table: %d notes exceed the int32 index' % len(flat))
+    group = file * N + (pitch.astype(np.int64) - note_min)
+    # bit 0: the offset equals, as a double, the onset of a note (this one included) of the same file and pitch (conv_note2label.py:76-83)
+    key_on, key_off = np.empty(len(flat), np.complex128), np.empty(len(flat), np.complex128)
+    key_on.real = key_off.real = group
+    key_on.imag, key_off.imag = onset, offset
+    order = np.argsort(group, kind='stable')                                    # list order inside a group; never by time
+    notes = np.zeros(len(flat), LABEL_NOTE)
+    notes['onset_sec'], notes['offset_sec'] = onset[order], offset[order]
+    notes['velocity'] = velocity[order].astype(np.int32)
+    notes['flags'] = np.isin(key_off, key_on)[order].astype(np.int32)
+    row_ptr = np.zeros(n_files * N + 1, np.int32)
+    row_ptr[1:] = np.cumsum(np.bincount(group, minlength=n_files * N))
+    max_offset = np.zeros(n_files, np.float64)
+    np.maximum.at(max_offset, file, offset)
+    file_nframe = ((max_offset * fps + 0.5).astype(np.int64) + 1).astype(np.int32)      # conv_note2label.py:20-27
+    return {'notes': notes, 'row_ptr': row_ptr, 'file_nframe': file_nframe, 'N': N, 'hop_ms': hop_ms, 'fps': fps, 'tol': tol}
+
+
+class LabelsTable:
+    """the note table on one device (labels_table) + the three grid constants; file_nframe_host stays for callers that size outputs"""
+
+    def __init__(self, host, device):
+        self.device = torch.device(device)
+        self.N, self.hop_ms, self.fps, self.tol = host['N'], host['hop_ms'], host['fps'], host['tol']
+        self.file_nframe_host = host['file_nframe']
+        self.n_files, self.n_notes = len(host['file_nframe']), len(host['notes'])
+        self.notes = torch.from_numpy(np.ascontiguousarray(host['notes']).view(np.uint8).reshape(-1)).to(self.device)
+        self.row_ptr = torch.from_numpy(host['row_ptr']).to(self.device)
+        self.file_nframe = torch.from_numpy(host['file_nframe']).to(self.device)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.notes, self.row_ptr, self.file_nframe))
+
+
+def labels_table(notes_per_file, config, device):
+    """note lists of a corpus -> the device-resident note table of labels_render (built once: labels_table_host + one upload)"""
+    return LabelsTable(labels_table_host(notes_per_file, config), device)
+
+
+def labels_render(table, win_file, win_start, length, form='train', duration_tolerance=False):
+    """B windows of `length` frames -> (onset, offset, mpe, velocity) [B, length, N] device tensors in ONE launch (hftt_labels_render).
+    win_file / win_start: int32 [B] device tensors (file index; first frame counted from the file's frame 0, may be negative or behind the file:
+    frames outside the file are zero) -- nothing is read back to the host.  form 'train': fp32, fp32, fp32, int64 (what engine.loss takes);
+    'store': fp32, fp32, bool, int8 (the dtypes of corpus.conv_note2label.note2label_arrays)."""
+    if form not in LABELS_FORM:
+        raise HfttError('labels_render: form %r (train / store)' % (form,))
+    dev = table.device
+    win_file = torch.as_tensor(win_file, device=dev).to(torch.int32).contiguous()
+    win_start = torch.as_tensor(win_start, device=dev).to(torch.int32).contiguous()
+    _need_cuda(table.notes, table.row_ptr, table.file_nframe, win_file, win_start)
+    B, length = win_file.numel(), int(length)
+    if win_file.dim() != 1 or win_start.shape != win_file.shape:
+        raise HfttError('labels_render: win_file and win_start must be [B]')
+    shape = (B, length, table.N)
+    train = form == 'train'
+    onset = torch.empty(shape, dtype=torch.float32, device=dev)
+    offset = torch.empty(shape, dtype=torch.float32, device=dev)
+    mpe = torch.empty(shape, dtype=torch.float32 if train else torch.uint8, device=dev)
+    velocity = torch.empty(shape, dtype=torch.int64 if train else torch.int8, device=dev)
+    d = LabelsDesc()
+    d.notes, d.row_ptr, d.file_nframe = table.notes.data_ptr() if table.n_notes else None, table.row_ptr.data_ptr(), table.file_nframe.data_ptr()
+    d.win_file, d.win_start = win_file.data_ptr(), win_start.data_ptr()
+    d.n_files, d.n_notes = table.n_files, table.n_notes
+    d.B, d.len, d.N, d.tol = B, length, table.N, table.tol
+    d.duration_tolerance, d.form = int(bool(duration_tolerance)), LABELS_FORM[form]
+    d.hop_ms, d.fps = table.hop_ms, table.fps
+    d.onset, d.offset, d.mpe, d.velocity = onset.data_ptr(), offset.data_ptr(), mpe.data_ptr(), velocity.data_ptr()
+    check(lib().hftt_labels_render(C.byref(d), _stream(dev)), 'labels_render')
+    return onset, offset, (mpe if train else mpe.view(torch.bool)), velocity

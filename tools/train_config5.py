@@ -5,7 +5,8 @@
 
 Corpus: `--files` one-minute files from corpus.synth_audio (seeds 2000.., never the scored file's seed 1234) -> HIP log-mel
 (model.amt.AMT.wave2feature) -> frame labels (corpus.conv_note2label.note2label_arrays, the reference's label recipe) -> one MAESTRO-format
-store (corpus.make_dataset.assemble_store) resident in HBM (training.dataset.DeviceClipStore).  Training: the product's own step
+store (corpus.make_dataset.assemble_store) resident in HBM (training.dataset.DeviceClipStore); with --note-store the corpus keeps the NOTES
+instead of the label tracks (assemble_note_store, NoteClipStore) and every batch's labels are rendered on the device.  Training: the product's own step
 (hftt_hip.trainer.TrainStep: forward + fused loss + backward + fused Adam) in the chosen precision mode, dropout 0.1, batch 8, until the
 time budget is spent.  The model is pickled the way m_training.py:372-373 does it (whole module, protocol 4).
 
@@ -19,27 +20,37 @@ import torch
 import bench
 from corpus import synth_audio as SA
 from corpus.conv_note2label import note2label_arrays
-from corpus.make_dataset import assemble_store
-from training.dataset import MyDataset, DeviceClipStore
+from corpus.make_dataset import assemble_note_store, assemble_store
+from training.dataset import MyDataset, DeviceClipStore, NoteClipStore
 from model.amt import AMT
 from evaluation.metrics import note_metrics, frame_metrics
 
 
-def build_corpus(config, files, dev, n_slice=8):
-    """`files` one-minute plucked-string files (seeds 2000..) -> HIP log-mel -> reference-recipe labels -> one MAESTRO-format store in HBM"""
+def build_corpus(config, files, dev, n_slice=8, note_store=False):
+    """`files` one-minute plucked-string files (seeds 2000..) -> HIP log-mel -> reference-recipe labels -> one MAESTRO-format store in HBM;
+    note_store: features + note table in HBM instead, labels rendered per batch (a file is then as long as its label track, not cut to its
+    feature array)"""
     t0 = time.time()
     tmp = tempfile.mkdtemp()
     with open(os.path.join(tmp, 'init.pkl'), 'wb') as fh:
         pickle.dump(bench.build_model(bench.CONFIGS['tiny'], 1, 0.1, 'cpu'), fh, protocol=4)
     fe = AMT(config, os.path.join(tmp, 'init.pkl'), batch_size=1)              # (front end only)
-    feats, labs = [], []
+    feats, labs, note_lists = [], [], []
     for i in range(files):
         notes = SA.pluck_notes(2000 + i)
         f = fe.wave2feature(SA.pluck_wave(notes, device=dev).unsqueeze(0), SA.SR).numpy()
+        if note_store:
+            feats.append(f); note_lists.append(notes)
+            continue
         lab = note2label_arrays(config, notes)
         n = f.shape[0]
         lab = {k: (np.concatenate([v, np.zeros((n - len(v),) + v.shape[1:], v.dtype)]) if len(v) < n else v[:n]) for k, v in lab.items()}
         feats.append(f); labs.append(lab)
+    if note_store:
+        store = assemble_note_store(feats, note_lists, config)
+        clips = NoteClipStore(store, config, dev, n_slice)
+        return clips, {'files': files, 'frames': int(store['feature'].shape[0]), 'clips': len(clips), 'notes': clips.table.n_notes,
+                       'resident_bytes': clips.resident_bytes(), 'seconds_to_build': round(time.time() - t0, 1)}
     store = assemble_store(feats, labs, config)
     ds = MyDataset.from_arrays(store['feature'], store['label_onset'], store['label_offset'], store['label_mpe'], store['label_velocity'],
                                store['idx'], config, n_slice)
@@ -174,6 +185,7 @@ def main():
     ap.add_argument('--clip', type=float, default=0.0, help='global gradient-norm clip (0 = off, as the reference)')
     ap.add_argument('--save-state', default='', help='pattern with one %%d: write the full training state there at the steps of --save-state-at')
     ap.add_argument('--save-state-at', default='')
+    ap.add_argument('--note-store', action='store_true', help='keep notes instead of label tracks in HBM and render every batch\'s labels on the device (NoteClipStore)')
     ap.add_argument('--out', default='gpurun_out/config5_tiny.pkl')
     ap.add_argument('--score-only', default='', help='skip training: score this pickled model')
     ap.add_argument('--init', default='', help='start from this pickled model (weights only: the optimizer state starts afresh) -- chains runs that are each bounded by the GPU call limit')
@@ -191,7 +203,7 @@ def main():
             with open(args.init, 'rb') as fh:
                 model.load_state_dict(pickle.load(fh).state_dict())
             log['init'] = args.init
-        clips, log['corpus'] = build_corpus(config, args.files, dev)
+        clips, log['corpus'] = build_corpus(config, args.files, dev, note_store=args.note_store)
         # ---- training ----
         model = model.to(dev)
         saver = None
