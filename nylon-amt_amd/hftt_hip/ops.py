@@ -469,11 +469,20 @@ class LogMel:
         self.device = torch.device(device)
         _need_cuda(torch.empty(0, device=self.device))
         self.sr, self.n_fft, self.hop, self.n_mels, self.log_offset = sr, n_fft, hop, n_mels, log_offset
+        t = self.tables(sr, n_fft, n_mels)
+        self.nnz = t['nnz']
+        for name in ('window', 'twiddle', 'fb_start', 'fb_len', 'fb_off', 'fb_w'):
+            setattr(self, name, t[name].to(self.device))
+
+    @classmethod
+    def tables(cls, sr=16000, n_fft=2048, n_mels=256):
+        """The kernel's tables as host tensors, in the formats the device holds (no device needed): window [n_fft] and twiddle
+        [cos | sin of 2 pi k / n_fft, k < n_fft / 2] fp32, the filterbank as CSR by mel (fb_start / fb_len / fb_off int32, fb_w fp32), nnz."""
         n = np.arange(n_fft, dtype=np.float64)
         window = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / n_fft)                       # periodic hann
         k = np.arange(n_fft // 2, dtype=np.float64)
         tw = np.concatenate([np.cos(2.0 * np.pi * k / n_fft), np.sin(2.0 * np.pi * k / n_fft)])
-        fb = self.mel_filterbank(sr, n_fft, n_mels)                                # [n_freqs, n_mels] float64
+        fb = cls.mel_filterbank(sr, n_fft, n_mels)                                 # [n_freqs, n_mels] float64
         starts, lens, offs, weights = [], [], [], []
         for m in range(n_mels):
             nz = np.nonzero(fb[:, m])[0]
@@ -482,14 +491,10 @@ class LogMel:
             s, e = int(nz[0]), int(nz[-1]) + 1
             starts.append(s); lens.append(e - s); offs.append(len(weights))
             weights.extend(fb[s:e, m].tolist())
-        self.nnz = len(weights)
-        dev = self.device
-        self.window = torch.tensor(window, dtype=torch.float32, device=dev)
-        self.twiddle = torch.tensor(tw, dtype=torch.float32, device=dev)
-        self.fb_start = torch.tensor(starts, dtype=torch.int32, device=dev)
-        self.fb_len = torch.tensor(lens, dtype=torch.int32, device=dev)
-        self.fb_off = torch.tensor(offs, dtype=torch.int32, device=dev)
-        self.fb_w = torch.tensor(weights if weights else [0.0], dtype=torch.float32, device=dev)
+        return dict(window=torch.tensor(window, dtype=torch.float32), twiddle=torch.tensor(tw, dtype=torch.float32),
+                    fb_start=torch.tensor(starts, dtype=torch.int32), fb_len=torch.tensor(lens, dtype=torch.int32),
+                    fb_off=torch.tensor(offs, dtype=torch.int32), fb_w=torch.tensor(weights if weights else [0.0], dtype=torch.float32),
+                    nnz=len(weights))
 
     @staticmethod
     def mel_filterbank(sr, n_fft, n_mels):
