@@ -588,6 +588,56 @@ typedef struct {
 } hftt_labels_desc;
 int hftt_labels_render(const hftt_labels_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Guarded optimizer step (csrc/guard.hip): global-norm gradient clipping, a non-finite guard and decoupled weight decay around the fused
+ * Adam.  Like the note decoder and the label renderer these entry points were ADDED at ABI 8 and HFTT_ABI_VERSION stays 8: nothing that an
+ * ABI-8 caller binds changed (hftt_adam_step above is untouched and remains the default step); a caller that needs them looks the symbols up.
+ *
+ * The record: 32 bytes of DEVICE memory, 16-byte aligned, zeroed once by the caller.  The norm kernels write it, the Adam kernel reads it,
+ * the host never has to: a training loop that only wants the step guarded does not synchronise.
+ *
+ * Norm (torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2): total_norm = || g ||_2 over ALL parameters,
+ * clip_coef = max_norm / (total_norm + 1e-6), clamped to 1) over the flat gradient, with grad_scale folded in (the 1 / world of the
+ * all-reduced sum: the norm is that of the gradient Adam will see).  Two launches, no atomics: 256-thread workgroups (at most 2048, the grid
+ * of the Adam kernels) read g once with 16-byte loads (scalar tail for n % 4), every lane sums g * g in fp64, lanes then waves are combined in
+ * a fixed order into one fp64 partial per workgroup in ws; one workgroup then sums the partials in a fixed order and one lane stores
+ *     norm64 = |grad_scale| * sqrt(sum)                                   (double)
+ *     apply  = isfinite(norm64)
+ *     coef   = apply ? (float)min(1.0, max_norm / (norm64 + 1e-6)) : 0    (formed in double, rounded once)
+ *     skipped += !apply;  clipped += apply && coef < 1
+ * fp64 on purpose: |g| = 1e30 does not overflow and |g| = 1e-30 does not vanish, so "the norm is not finite" is the same statement as
+ * "some element is Inf or NaN" (squares cannot cancel).  max_norm = +inf switches clipping off (coef is exactly 1).  The record is bitwise
+ * reproducible from run to run.  ws: hftt_grad_norm_ws_bytes(n) bytes, 16-byte aligned, contents irrelevant on entry.
+ * Refused in front of the launch: null operands; n <= 0; g, ws or ctl not 16-byte aligned; grad_scale not finite; max_norm NaN or <= 0.
+ *
+ * Step: hftt_adam_step's update, one launch, read through the record.  apply == 0: the kernel returns without a store -- p, m, v keep their
+ * bits.  Otherwise per element
+ *     gr = g * ((float)grad_scale * coef)
+ *     p *= d,  d = (float)(1 - lr * weight_decay)        (torch.optim.AdamW: param.mul_(1 - lr * weight_decay), the decay first)
+ *     m = b1*m + (1-b1)*gr; v = b2*v + (1-b2)*gr*gr; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+ * with 1 - b, the bias corrections and d formed in double on the host and rounded once.  g is NOT rewritten: the clip factor lives in the
+ * kernel (clip_grad_norm_ scales the gradients in place).  With coef == 1 and weight_decay == 0 the result is bit-identical to
+ * hftt_adam_step.  `step` is the number of CALLS, as for hftt_adam_step: a skipped step still advances it, so the caller's step counter
+ * and checkpoints keep their meaning.  torch.amp.GradScaler differs: it does not count the steps it skips.  The effect here is a slightly
+ * smaller bias correction during the first few hundred steps after a skip.
+ * Refused in front of the launch: what hftt_adam_step refuses; ctl null or not 16-byte aligned; weight_decay NaN or negative;
+ * lr * weight_decay >= 1.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {            /* 32 bytes of DEVICE memory, 16-byte aligned, zeroed once by the caller */
+  float    norm;            /* || grad_scale * g ||_2 of the last call, fp32 rounding of the fp64 value (may be inf / nan) */
+  float    coef;            /* factor applied on top of grad_scale: min(1, max_norm / (norm + 1e-6)); 1 when clipping is off */
+  uint32_t apply;           /* 1: the step is applied; 0: the norm was not finite, the step is skipped */
+  uint32_t skipped;         /* cumulative count of skipped steps */
+  uint32_t clipped;         /* cumulative count of applied steps with coef < 1 */
+  uint32_t pad[3];
+} hftt_guard_ctl;
+int64_t hftt_grad_norm_ws_bytes(int64_t n);
+int hftt_grad_norm(const float* g, int64_t n, double grad_scale, double max_norm,
+                   void* ws, hftt_guard_ctl* ctl, void* stream);
+int hftt_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, int32_t step,
+                           double lr, double beta1, double beta2, double eps, double grad_scale,
+                           double weight_decay, const hftt_guard_ctl* ctl, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,164 @@
+// Guarded optimizer step (gfx950): the global L2 norm of the flat gradient as a two-launch fp64 reduction that leaves its verdict (norm, clip
+// factor, apply / skip, counters) in a 32-byte device record, and the Adam kernel that reads the record: it skips a step whose norm is not
+// finite, scales the gradient by the clip factor on the fly and applies decoupled weight decay.  No float atomics, no cross-workgroup
+// tickets: every sum has one fixed order, so the record is bitwise reproducible.  Entry points and the torch definitions they restate:
+// include/hftt_hip.h.  The unguarded step (hftt_adam_step / adam_kernel, csrc/elementwise.hip) is untouched and stays the default path.
+#include "hftt_common.h"
+#include "hftt_launch.h"
+#include "../../include/hftt_hip.h"
+#include <math.h>
+
+namespace {
+
+constexpr int GN_THREADS = 256;
+constexpr int GN_MAX_WGS = 2048;          // the grid cap of adam_kernel: one fp64 partial per workgroup
+
+// lanes of a wave: xor butterfly (the addition commutes, so every lane ends with the same bits)
+__device__ __forceinline__ double wave_sum64(double x) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+
+// lanes, then the four waves in order; the result is valid in thread 0
+__device__ __forceinline__ double block_sum64(double x) {
+  __shared__ double red[GN_THREADS / 64];
+  x = wave_sum64(x);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// ------------------------------------------------------------------ stage 1: one fp64 partial of sum g^2 per workgroup
+// The product of two fp32 values is exact in fp64 and |g| <= 3.4e38 squares to 1.2e77, far inside fp64: the partial is non-finite exactly
+// when some element is Inf / NaN, and squares cannot cancel.
+__global__ __launch_bounds__(GN_THREADS) void grad_sqsum_kernel(const float* __restrict__ g, long n, double* __restrict__ ws) {
+  const long n4 = n / 4;
+  const long stride = (long)gridDim.x * blockDim.x;
+  double acc = 0.0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    const double x = gg.x, y = gg.y, z = gg.z, w = gg.w;
+    acc += x * x; acc += y * y; acc += z * z; acc += w * w;
+  }
+  for (long i = n4 * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const double x = g[i];
+    acc += x * x;
+  }
+  const double s = block_sum64(acc);
+  if (threadIdx.x == 0) ws[blockIdx.x] = s;
+}
+
+// ------------------------------------------------------------------ stage 2: the partials in fixed order, the verdict, the record
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_finalize_kernel(const double* __restrict__ ws, int n_wg, double abs_scale, double max_norm,
+                                                                        hftt_guard_ctl* __restrict__ ctl) {
+  double acc = 0.0;
+  for (int w = threadIdx.x; w < n_wg; w += GN_THREADS) acc += ws[w];
+  const double sum = block_sum64(acc);
+  if (threadIdx.x == 0) {
+    const double norm64 = abs_scale * sqrt(sum);
+    const bool apply = isfinite(norm64);
+    const float coef = apply ? (float)fmin(1.0, max_norm / (norm64 + 1e-6)) : 0.f;
+    ctl->norm = (float)norm64;
+    ctl->coef = coef;
+    ctl->apply = apply ? 1u : 0u;
+    ctl->skipped += apply ? 0u : 1u;
+    ctl->clipped += (apply && coef < 1.f) ? 1u : 0u;
+  }
+}
+
+// ------------------------------------------------------------------ guarded Adam
+// adam_kernel's update on gr = g * (grad_scale * coef), behind p *= d (decoupled decay, d = 1 - lr * weight_decay); nothing is written
+// when the record says skip.  With coef == 1 and d == 1 every operation reproduces adam_kernel's bits.
+//
+// adam_kernel writes  m = beta1 * m + omb1 * gr;  v = beta2 * v + omb2 * gr * gr;  p -= lr_c * m / (sqrtf(v) * inv_sqrt_bc2 + eps)  and leaves
+// the choice of which product joins which sum in one fma to the compiler -- which chooses differently in its quad loop and in its tail
+// (and differently again for the same text behind `g * s` with s read from memory).  Bit-identity cannot rest on that, so the two forms
+// adam_kernel compiles to are written out here with contraction switched off around them: QUAD m = fma(beta1, m, omb1 gr),
+// v = fma(gr, omb2 gr, beta2 v); tail m = fma(omb1, gr, beta1 m), v = gr (omb2 gr) + beta2 v unfused; both den = fma(sqrt v, inv_sqrt_bc2, eps)
+// and an unfused p - q.  tests/test_guard_gpu.py::test_inactive_guard_is_bit_identical_to_adam_step holds the two kernels together.
+template <bool QUAD>
+__device__ __forceinline__ void adam_guarded_update(float& p, float g, float& m, float& v, float s, float d, float lr_c, float beta1, float beta2,
+                                                    float omb1, float omb2, float eps, float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  const float gr = g * s;
+  const float pd = p * d;
+  if (QUAD) {
+    m = __builtin_fmaf(beta1, m, omb1 * gr);
+    v = __builtin_fmaf(gr, omb2 * gr, beta2 * v);
+  } else {
+    m = __builtin_fmaf(omb1, gr, beta1 * m);
+    v = gr * (omb2 * gr) + beta2 * v;
+  }
+  const float den = __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+  p = pd - lr_c * m / den;
+}
+
+__global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
+                                    float lr_c, float beta1, float beta2, float omb1, float omb2, float eps, float inv_sqrt_bc2, float grad_scale,
+                                    float d, const hftt_guard_ctl* __restrict__ ctl) {
+  if (ctl->apply == 0u) return;               // (uniform: every lane of every workgroup reads the same word)
+  const float s = grad_scale * ctl->coef;
+  const long n4 = n / 4;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    float4 mm = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    float* pe = &pp.x; const float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
+#pragma unroll
+    for (int e = 0; e < 4; e++) adam_guarded_update<true>(pe[e], ge[e], me[e], ve[e], s, d, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(m)[i] = mm;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+  const long tail = n4 * 4;
+  for (long i = tail + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_guarded_update<false>(pi, g[i], mi, vi, s, d, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+  }
+}
+
+// workgroups over n elements read four at a time: adam_kernel's grid (ceil((n / 4 + 1) / 256), at most GN_MAX_WGS)
+inline int guard_grid(long n) {
+  long b = (n / 4 + 1 + GN_THREADS - 1) / GN_THREADS;
+  if (b < 1) b = 1;
+  if (b > GN_MAX_WGS) b = GN_MAX_WGS;
+  return (int)b;
+}
+
+}  // namespace
+
+extern "C" int64_t hftt_grad_norm_ws_bytes(int64_t n) { (void)n; return (int64_t)GN_MAX_WGS * 8; }
+
+extern "C" int hftt_grad_norm(const float* g, int64_t n, double grad_scale, double max_norm, void* ws, hftt_guard_ctl* ctl, void* stream) {
+  HFTT_REQUIRE(g && ws && ctl, "grad_norm: null operand");
+  HFTT_REQUIRE(n > 0, "grad_norm: n=%ld must be positive", (long)n);
+  HFTT_REQUIRE((((uintptr_t)g | (uintptr_t)ws | (uintptr_t)ctl) & 15) == 0, "grad_norm: g, ws and ctl must be 16-byte aligned");
+  HFTT_REQUIRE(isfinite(grad_scale), "grad_norm: grad_scale must be finite");
+  HFTT_REQUIRE(max_norm > 0.0, "grad_norm: max_norm must be positive (+inf: no clipping)");         // (false for NaN too)
+  const int wgs = guard_grid((long)n);
+  if (int rc = hftt_launch<grad_sqsum_kernel>("grad_norm(1)", dim3(wgs), dim3(GN_THREADS), 0, (hipStream_t)stream, g, (long)n, (double*)ws)) return rc;
+  return hftt_launch<grad_norm_finalize_kernel>("grad_norm(2)", dim3(1), dim3(GN_THREADS), 0, (hipStream_t)stream, (const double*)ws, wgs, fabs(grad_scale), max_norm, ctl);
+}
+
+extern "C" int hftt_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, int32_t step,
+                                      double lr, double beta1, double beta2, double eps, double grad_scale,
+                                      double weight_decay, const hftt_guard_ctl* ctl, void* stream) {
+  HFTT_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adam_step_guarded: bad arguments");
+  HFTT_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step_guarded: buffers must be 16-byte aligned");
+  HFTT_REQUIRE(ctl != nullptr, "adam_step_guarded: ctl is null");
+  HFTT_REQUIRE(((uintptr_t)ctl & 15) == 0, "adam_step_guarded: ctl must be 16-byte aligned");
+  HFTT_REQUIRE(weight_decay >= 0.0, "adam_step_guarded: weight_decay must be >= 0");                  // (false for NaN too)
+  HFTT_REQUIRE(lr * weight_decay < 1.0, "adam_step_guarded: lr * weight_decay must be below 1");
+  // as hftt_adam_step: everything that is a function of the hyper-parameters alone is formed in double and rounded once
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  const float lr_c = (float)(lr / bc1);
+  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  const float d = (float)(1.0 - lr * weight_decay);
+  return hftt_launch<adam_guarded_kernel>("adam_step_guarded", dim3(guard_grid((long)n)), dim3(GN_THREADS), 0, (hipStream_t)stream, p, g, m, v, (long)n,
+                                                                lr_c, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, inv_sqrt_bc2,
+                                                                (float)grad_scale, d, ctl);
+}

@@ -190,6 +190,11 @@ class LabelsDesc(C.Structure):
                 ('onset', C.c_void_p), ('offset', C.c_void_p), ('mpe', C.c_void_p), ('velocity', C.c_void_p)]
 
 
+class GuardCtl(C.Structure):                # hftt_guard_ctl: 32 bytes of device memory (the host only reads it back)
+    _fields_ = [('norm', C.c_float), ('coef', C.c_float), ('apply', C.c_uint32), ('skipped', C.c_uint32), ('clipped', C.c_uint32),
+                ('pad', C.c_uint32 * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/hftt_hip.h declares
 SIGNATURES = {
     'hftt_abi_version': (C.c_int, []),
@@ -237,6 +242,10 @@ SIGNATURES = {
     'hftt_notes_ws_bytes': (C.c_int64, [C.c_int64, C.c_int32]),
     'hftt_notes_decode': (C.c_int, [C.POINTER(NotesDesc), C.c_void_p]),
     'hftt_labels_render': (C.c_int, [C.POINTER(LabelsDesc), C.c_void_p]),
+    'hftt_grad_norm_ws_bytes': (C.c_int64, [C.c_int64]),
+    'hftt_grad_norm': (C.c_int, [c_f32p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hftt_adam_step_guarded': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32,
+                                         C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -459,6 +459,27 @@ def adam_step(p, g, m, v, step, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, grad_
                                grad_scale, _stream(p.device)), 'adam_step')
 
 
+def guard_buffers(n, device):
+    """(ctl, ws) of the guarded step over n elements: the zeroed 32-byte hftt_guard_ctl as an int32[8] tensor (norm and coef are its first
+    two words viewed as fp32, apply / skipped / clipped words 2, 3, 4) and the workspace of the norm's partials"""
+    ctl = torch.zeros(8, dtype=torch.int32, device=device)
+    ws = torch.empty(lib().hftt_grad_norm_ws_bytes(n) // 8, dtype=torch.float64, device=device)
+    return ctl, ws
+
+
+def grad_norm(g, ctl, ws, grad_scale=1.0, max_norm=math.inf):
+    """ctl <- the verdict on || grad_scale * g ||_2 (norm, clip factor, apply / skip, counters): two launches, no host sync"""
+    _need_cuda(g, ctl, ws)
+    check(lib().hftt_grad_norm(g.data_ptr(), g.numel(), grad_scale, max_norm, ws.data_ptr(), ctl.data_ptr(), _stream(g.device)), 'grad_norm')
+
+
+def adam_step_guarded(p, g, m, v, step, ctl, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, weight_decay=0.0):
+    """adam_step through the verdict in ctl: skipped when the norm was not finite, g scaled by the clip factor, decoupled weight decay"""
+    _need_cuda(p, g, m, v, ctl)
+    check(lib().hftt_adam_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), step, lr, beta1, beta2, eps,
+                                       grad_scale, weight_decay, ctl.data_ptr(), _stream(p.device)), 'adam_step_guarded')
+
+
 # ------------------------------------------------------------------------------------------------
 # log-mel front end (model/amt.py:55-63)
 # ------------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ gradient buffer.
 """
 from __future__ import annotations
 
+import math
 import weakref
 
 import torch
@@ -40,20 +41,45 @@ class FusedAdam(torch.optim.Optimizer):
     Drop-in at m_training.py:146: ``optimizer = FusedAdam(model.parameters(), lr=args.lr)`` (a model is accepted too).  It is a real
     ``torch.optim.Optimizer``: ``ReduceLROnPlateau(optimizer)`` (:147) and ``scheduler.step`` (:437) drive ``param_groups[0]['lr']``,
     ``state_dict()`` / ``load_state_dict()`` (:374-392, :268-299) have torch Adam's layout (per-parameter ``step`` / ``exp_avg`` /
-    ``exp_avg_sq``, here views into two flat moment buffers), so a reference ``.dat`` checkpoint's ``optimizer_dict`` loads."""
+    ``exp_avg_sq``, here views into two flat moment buffers), so a reference ``.dat`` checkpoint's ``optimizer_dict`` loads.
 
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
+    The guarded step (opt-in; with the three options at their defaults ``step()`` launches exactly the one Adam kernel above):
+
+    ``max_grad_norm``  global-norm clipping, ``torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)`` in front of the step: the
+                     L2 norm of the whole flat gradient (fp64 accumulation on the device, ``grad_scale`` folded in), factor
+                     ``min(1, max_grad_norm / (norm + 1e-6))``.  Unlike ``clip_grad_norm_``, which scales the gradients in place, the factor
+                     is applied INSIDE the Adam kernel: ``p.grad`` keeps the UNCLIPPED gradient.
+    ``guard``          a step whose gradient norm is not finite (some element is Inf / NaN) is skipped: parameters and both moments keep
+                     their bits.  Any of the three options turns the guard on.  ``state[p]['step']`` counts calls, so a skipped step still
+                     advances it (``GradScaler`` does not count skipped steps; here the bias correction is slightly smaller for the first few
+                     hundred steps after a skip, and checkpoints keep their layout).
+    ``weight_decay``   decoupled (``torch.optim.AdamW``: ``p *= 1 - lr * weight_decay`` before the update; ``param_groups[0]`` then says
+                     ``decoupled_weight_decay=True``).  The optimizer has ONE group, so the decay acts on every parameter, LayerNorm gains
+                     and biases included.  The L2 form (decay added to the gradient) is not implemented and a state that asks for it is refused.
+
+    The decision is taken on the device: ``grad_norm`` and ``clip_coef`` are 0-dim device views of the kernel's record (reading them does
+    not synchronise); ``skipped_steps`` and ``clipped_steps`` are Python ints, and reading them DOES synchronise.  ``state_dict()`` carries
+    the two counters as ``hftt_guard``; a state without that key (older checkpoints, the reference's ``.dat``) loads."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, guard=False, weight_decay=0.0):
         model = params if hasattr(params, 'hftt_engine') else None
         if model is not None:
             params = model.parameters()
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False, maximize=False, foreach=None, capturable=False,
-                                      differentiable=False, fused=None, decoupled_weight_decay=False))
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise HfttError('FusedAdam: max_grad_norm=%r must be positive (None: no clipping)' % (max_grad_norm,))
+        if not float(weight_decay) >= 0.0:
+            raise HfttError('FusedAdam: weight_decay=%r must be >= 0' % (weight_decay,))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None, capturable=False,
+                                      differentiable=False, fused=None, decoupled_weight_decay=weight_decay != 0,
+                                      max_grad_norm=None if max_grad_norm is None else float(max_grad_norm), guard=bool(guard)))
         if len(self.param_groups) != 1:
             raise HfttError('FusedAdam takes one parameter group (the whole model), as m_training.py:146 builds it')
         self._model = model
         self.engine = None
         self.step_count = 0
         self.exp_avg = self.exp_avg_sq = None
+        self._ctl = self._ws = None               # the guarded step's device record and workspace (attach)
+        self._pending_guard = None                # counters of a checkpoint loaded before any engine existed
 
     # ---- binding to the engine's flat buffers (lazy: the engine binds at the model's first forward)
     def _params(self):
@@ -78,6 +104,10 @@ class FusedAdam(torch.optim.Optimizer):
                 self.step_count = int(old[p]['step'])
             st['step'] = torch.tensor(float(self.step_count))
             st['exp_avg'], st['exp_avg_sq'] = m, v
+        self._ctl, self._ws = ops.guard_buffers(engine.flat_params.numel(), engine.flat_params.device)
+        if self._pending_guard is not None:
+            self._set_guard_counts(*self._pending_guard)
+            self._pending_guard = None
         ctr = getattr(self, '_pending_counter', None)
         if ctr is not None:                       # a checkpoint loaded before any engine existed: resume its dropout stream position
             engine.step_counter = int(ctr)
@@ -100,30 +130,84 @@ class FusedAdam(torch.optim.Optimizer):
         self.attach(self._find_engine())
         g = self.param_groups[0]
         self.step_count += 1
-        ops.adam_step(self.engine.flat_params, self.engine.flat_grads, self.exp_avg, self.exp_avg_sq, self.step_count,
-                      lr=float(g['lr']), beta1=g['betas'][0], beta2=g['betas'][1], eps=g['eps'], grad_scale=grad_scale)
+        if self._guarded(g):
+            mg = g.get('max_grad_norm')
+            ops.grad_norm(self.engine.flat_grads, self._ctl, self._ws, grad_scale=grad_scale, max_norm=math.inf if mg is None else float(mg))
+            ops.adam_step_guarded(self.engine.flat_params, self.engine.flat_grads, self.exp_avg, self.exp_avg_sq, self.step_count, self._ctl,
+                                  lr=float(g['lr']), beta1=g['betas'][0], beta2=g['betas'][1], eps=g['eps'], grad_scale=grad_scale,
+                                  weight_decay=float(g.get('weight_decay', 0)))
+        else:
+            ops.adam_step(self.engine.flat_params, self.engine.flat_grads, self.exp_avg, self.exp_avg_sq, self.step_count,
+                          lr=float(g['lr']), beta1=g['betas'][0], beta2=g['betas'][1], eps=g['eps'], grad_scale=grad_scale)
         self.engine._prepared_frozen = False          # (a frozen-weights inference engine must prepare its operands again)
         for p in self._params():
             self.state[p]['step'].fill_(self.step_count)
         return loss
 
+    # ---- the guarded step: options in param_groups[0], the verdict and the counters in the device record
+    @staticmethod
+    def _guarded(g):
+        return bool(g.get('guard', False)) or g.get('max_grad_norm') is not None or g.get('weight_decay', 0) != 0
+
+    def _ctl_word(self, i, dtype=None):
+        if self._ctl is None:
+            raise HfttError('FusedAdam: not attached to an engine yet (the record of the guarded step lives on its device)')
+        return (self._ctl if dtype is None else self._ctl.view(dtype))[i]
+
+    @property
+    def grad_norm(self):
+        """|| grad_scale * g ||_2 of the last guarded step: a 0-dim fp32 DEVICE view (no sync; inf / nan when the step was skipped)"""
+        return self._ctl_word(0, torch.float32)
+
+    @property
+    def clip_coef(self):
+        """the factor the last guarded step applied on top of grad_scale (1: not clipped, 0: skipped): a 0-dim fp32 DEVICE view (no sync)"""
+        return self._ctl_word(1, torch.float32)
+
+    def _guard_counts(self):
+        if self._ctl is None:
+            return self._pending_guard or (0, 0)
+        sk, cl = self._ctl[3:5].tolist()
+        return int(sk) & 0xFFFFFFFF, int(cl) & 0xFFFFFFFF
+
+    def _set_guard_counts(self, skipped, clipped):
+        to_i32 = lambda x: ((int(x) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000      # noqa: E731  (the record's words are uint32)
+        self._ctl[3:5] = torch.tensor([to_i32(skipped), to_i32(clipped)], dtype=torch.int32)
+
+    @property
+    def skipped_steps(self):
+        """steps skipped so far because the gradient norm was not finite (a Python int: reading it synchronises with the device)"""
+        return self._guard_counts()[0]
+
+    @property
+    def clipped_steps(self):
+        """applied steps whose clip factor was below 1 (a Python int: reading it synchronises with the device)"""
+        return self._guard_counts()[1]
+
     def state_dict(self):
         sd = super().state_dict()
         sd['hftt_step_counter'] = None if self.engine is None else int(self.engine.step_counter)      # dropout stream position (resume)
+        skipped, clipped = self._guard_counts()
+        sd['hftt_guard'] = {'skipped': skipped, 'clipped': clipped}
         return sd
 
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         ctr = state_dict.pop('hftt_step_counter', None)
+        guard = state_dict.pop('hftt_guard', None)   # absent in older checkpoints and in the reference's .dat
         super().load_state_dict(state_dict)          # torch's layout: state tensors are fresh copies, param_groups restored
         steps = [int(s['step']) for s in self.state.values() if 'step' in s]
         self.step_count = max(steps) if steps else 0
         for g in self.param_groups:                  # what the fused kernel does not implement must not be dropped silently
-            if g.get('weight_decay', 0) != 0 or g.get('amsgrad', False) or g.get('maximize', False):
+            l2 = g.get('weight_decay', 0) != 0 and not g.get('decoupled_weight_decay', False)       # (the decoupled form is the guarded kernel's)
+            if l2 or g.get('amsgrad', False) or g.get('maximize', False):
                 raise HfttError('FusedAdam: the loaded state asks for weight_decay / amsgrad / maximize, which the fused Adam kernel does not do '
                                 '(reference: optim.Adam(model.parameters(), lr), m_training.py:146)')
+            for k in ('max_grad_norm', 'guard'):     # a state written without the options keeps the ones this optimizer was built with
+                g.setdefault(k, self.defaults[k])
         eng, self.engine, self.exp_avg = self.engine, None, None
         self._pending_counter = None
+        self._pending_guard = None if guard is None else (int(guard['skipped']), int(guard['clipped']))
         if eng is not None:
             self.attach(eng)                         # copy the loaded moments into the flat buffers
             if ctr is not None:

@@ -86,20 +86,14 @@ def lr_at(step, lr, warmup=0, total=0, final_frac=1.0):
     return lr
 
 
-def clip_flat_gradient_(flat, max_norm):
-    """global-norm clipping of the engine's flat gradient without a host sync (torch ops on the flat buffer: plumbing beside the fused Adam)"""
-    n = torch.linalg.vector_norm(flat)
-    flat.mul_(torch.clamp(max_norm / (n + 1e-6), max=1.0))
-    return n
-
-
 def train_loop(model, clips, dev, precision, lr, steps=0, minutes=0.0, batch=8, seed=77, warmup=0, final_frac=1.0, clip=0.0, log_every=250,
-               on_step=None, tag=''):
-    """the product's own training step until `steps` (or the time budget); returns (TrainStep, steps done, epochs started, loss curve, seconds)"""
-    from hftt_hip.trainer import TrainStep
+               on_step=None, tag='', guard=False, weight_decay=0.0):
+    """the product's own training step until `steps` (or the time budget); returns (TrainStep, steps done, epochs started, loss curve, seconds).
+    clip > 0 / guard / weight_decay > 0 are FusedAdam's max_grad_norm / guard / weight_decay: the same TrainStep call, a guarded optimizer."""
+    from hftt_hip.trainer import FusedAdam, TrainStep
     model.hftt_precision = precision
     model.train()
-    ts = TrainStep(model, lr=lr)
+    ts = TrainStep(model, optimizer=FusedAdam(model, lr=lr, max_grad_norm=clip if clip > 0.0 else None, guard=guard, weight_decay=weight_decay))
     group = ts.opt.param_groups[0]
     t0, step, epoch, curve = time.time(), 0, 0, []
     acc = torch.zeros(9, device=dev)
@@ -107,13 +101,7 @@ def train_loop(model, clips, dev, precision, lr, steps=0, minutes=0.0, batch=8, 
     while not done:
         for b in clips.loader(batch, shuffle=True, seed=seed + epoch, drop_last=True):
             group['lr'] = lr_at(step + 1, lr, warmup, steps, final_frac)
-            if clip > 0.0:
-                acc += ts.forward_backward(b[0], *b[1:])
-                clip_flat_gradient_(ts.engine.flat_grads, clip)
-                with torch.cuda.device(ts.engine.device):
-                    ts.opt.step()
-            else:
-                acc += ts(b[0], *b[1:])
+            acc += ts(b[0], *b[1:])
             step += 1
             if on_step is not None:
                 on_step(ts, step)
@@ -182,7 +170,9 @@ def main():
     ap.add_argument('--warmup', type=int, default=0, help='linear warm-up steps (lr_at)')
     ap.add_argument('--final-frac', type=float, default=1.0, help='< 1 with --steps: cosine decay to lr * final_frac at the last step')
     ap.add_argument('--pos-scale', type=float, default=1.0, help='multiply the position-embedding tables by this at initialisation (scale_position_embeddings_)')
-    ap.add_argument('--clip', type=float, default=0.0, help='global gradient-norm clip (0 = off, as the reference)')
+    ap.add_argument('--clip', type=float, default=0.0, help='global gradient-norm clip, FusedAdam(max_grad_norm=...) (0 = off, as the reference)')
+    ap.add_argument('--guard', action='store_true', help='skip a step whose gradient norm is not finite, FusedAdam(guard=True) (--clip and --weight-decay imply it)')
+    ap.add_argument('--weight-decay', type=float, default=0.0, help='decoupled (AdamW) weight decay on every parameter, FusedAdam(weight_decay=...) (0 = off, as the reference)')
     ap.add_argument('--save-state', default='', help='pattern with one %%d: write the full training state there at the steps of --save-state-at')
     ap.add_argument('--save-state-at', default='')
     ap.add_argument('--note-store', action='store_true', help='keep notes instead of label tracks in HBM and render every batch\'s labels on the device (NoteClipStore)')
@@ -213,11 +203,13 @@ def main():
                 if step in at:
                     save_state(ts, step, args.save_state % step)
         ts, step, epoch, curve, secs = train_loop(model, clips, dev, args.precision, args.lr, steps=args.steps, minutes=args.minutes, batch=args.batch,
-                                                   seed=args.seed, warmup=args.warmup, final_frac=args.final_frac, clip=args.clip, on_step=saver)
+                                                   seed=args.seed, warmup=args.warmup, final_frac=args.final_frac, clip=args.clip, on_step=saver,
+                                                   guard=args.guard, weight_decay=args.weight_decay)
         if curve and curve[-1][1] != curve[-1][1]:
             log['diverged_at_step'] = step
         log['training'] = {'steps': step, 'epochs_started': epoch, 'seconds': round(secs, 1), 'lr': args.lr, 'warmup': args.warmup, 'final_frac': args.final_frac,
-                           'clip': args.clip, 'pos_scale': args.pos_scale, 'batch': args.batch, 'dropout': 0.1, 'seed': args.seed,
+                           'clip': args.clip, 'guard': args.guard, 'weight_decay': args.weight_decay,
+                           'skipped_steps': ts.opt.skipped_steps, 'clipped_steps': ts.opt.clipped_steps, 'pos_scale': args.pos_scale, 'batch': args.batch, 'dropout': 0.1, 'seed': args.seed,
                            'clips_per_s': round(step * args.batch / secs, 1), 'loss_curve': curve[:: max(1, len(curve) // 24)]}
         model.eval()
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
