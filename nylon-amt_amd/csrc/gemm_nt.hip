@@ -6,7 +6,8 @@
 //                         plane; v_mfma_f32_32x32x16_bf16; LDS rows padded to 80 B (conflict-free ds_read_b128).
 //   npass == 3 ("parity"): operands stay fp32 in LDS (rows of 33 floats: conflict-free ds_read_b32), weights come as a
 //                         prepared fp32 matrix; v_mfma_f32_32x32x2_f32 = exact fp32 FMA chains (<= 1e-3 parity mode).
-#include <stdlib.h>
+// bf16 mode with N a multiple of 256 and K <= 768 takes the A-stationary kernel further down (gemm_nt_as1_kernel); it and the split
+// modes' full tiles finish their rows in one shared row pass (row_pass).
 #include <type_traits>
 #include "hftt_common.h"
 #include "x3_common.h"
@@ -31,6 +32,82 @@ __device__ __forceinline__ void store_c4(float* C, bool bf, long off, float a, f
     *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(C) + off) = u;
   } else {
     *reinterpret_cast<float4*>(C + off) = make_float4(a, b, c, d);
+  }
+}
+
+// Row pass: finishes the rows of a staged 256-column tile (stage[row_l * ld + col_l], rows m0 .., columns n0 ..) -- one wave per row, 16 B
+// per lane: table add, gate, dropout, residual, LayerNorm, one 16-byte (bf16: 8-byte) store.  Each wave takes RPW rows, RB at a time: all
+// table / gate / residual loads of the RB rows are issued (from a clamped row: the wave-uniform pointer tests are the only branches), then
+// the arithmetic runs.  Dropout hashes once per quad: col % 4 == 0 and N % 4 == 0 here, so element e of the quad is byte e of that hash.
+//   BF     gate, residual and C may be stored as bf16 (io_flags)
+//   LNORM  LayerNorm where g.ln_gamma is set (N == 256: the row is complete)
+//   col_ok this lane's four columns exist (always where N % 256 == 0)
+template <int RPW, int RB, bool BF, bool LNORM>
+__device__ __forceinline__ void row_pass(const hftt_gemm_nt_desc g, const long m0, const int n0, const float* stage, const int ld, const bool col_ok,
+                                         const uint32_t thr, const float inv_keep) {
+  static_assert(RPW % RB == 0, "whole groups of rows");
+  // The bf16 forms add the table / residual registers even when no tensor was loaded into them (zeros: a -0 of the stage leaves as +0);
+  // the fp32 form adds only what exists (a -0 stays).  Kept apart from BF: it is a property of the results, not of the storage.
+  constexpr bool ADD_ZEROS = BF;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool c_bf = BF && (g.io_flags & HFTT_NT_C_BF16), gate_bf = BF && (g.io_flags & HFTT_NT_GATE_BF16), res_bf = BF && (g.io_flags & HFTT_NT_RES_BF16);
+  const bool ln = LNORM && g.ln_gamma != nullptr;
+  const int c4 = n0 + lane * 4;
+  float4 ga = make_float4(1.f, 1.f, 1.f, 1.f), be = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (ln) {
+    ga = *reinterpret_cast<const float4*>(g.ln_gamma + c4);
+    be = *reinterpret_cast<const float4*>(g.ln_beta + c4);
+  }
+#pragma unroll 1
+  for (int rb = 0; rb < RPW; rb += RB) {
+    if (RB == 1 && m0 + wave * RPW + rb >= g.M) break;      // (wave-uniform) this row and every later one lie past M
+    float4 tab[RB], gat[RB], res[RB];
+#pragma unroll
+    for (int rr = 0; rr < RB; rr++) {
+      const long row = m0 + wave * RPW + rb + rr;
+      tab[rr] = make_float4(0.f, 0.f, 0.f, 0.f); gat[rr] = tab[rr]; res[rr] = tab[rr];
+      const long rc = row < g.M ? row : (long)g.M - 1;
+      if (col_ok) {
+        if (g.add_table != nullptr) tab[rr] = *reinterpret_cast<const float4*>(g.add_table + (long)(rc % g.add_mod) * g.N + c4);
+        if (g.gate != nullptr) gat[rr] = load_gate4(g.gate, gate_bf, rc * g.ldg + c4);
+        if (g.residual != nullptr) res[rr] = load_gate4(g.residual, res_bf, (long)(rc % g.res_mod) * g.ldr + c4);
+      }
+    }
+#pragma unroll
+    for (int rr = 0; rr < RB; rr++) {
+      const int row_l = wave * RPW + rb + rr;
+      const long row = m0 + row_l;
+      if (row < g.M && col_ok) {         // (row: wave-uniform)
+        const float4 sv = *reinterpret_cast<const float4*>(stage + row_l * ld + lane * 4);
+        float v[4] = {sv.x, sv.y, sv.z, sv.w};
+        if (ADD_ZEROS || g.add_table != nullptr) { v[0] += tab[rr].x; v[1] += tab[rr].y; v[2] += tab[rr].z; v[3] += tab[rr].w; }
+        if (g.gate != nullptr) {
+          v[0] = gat[rr].x > 0.f ? v[0] * g.gate_scale : 0.f; v[1] = gat[rr].y > 0.f ? v[1] * g.gate_scale : 0.f;
+          v[2] = gat[rr].z > 0.f ? v[2] * g.gate_scale : 0.f; v[3] = gat[rr].w > 0.f ? v[3] * g.gate_scale : 0.f;
+        }
+        if (g.drop_p > 0.f) {
+          const uint32_t k4 = hftt_keep_quad(g.drop_seed, g.drop_site, ((uint64_t)row * (uint64_t)g.N + (uint64_t)c4) >> 2, thr);
+#pragma unroll
+          for (int e = 0; e < 4; e++) v[e] = ((k4 >> e) & 1u) ? v[e] * inv_keep : 0.f;
+        }
+        if (ADD_ZEROS || g.residual != nullptr) { v[0] += res[rr].x; v[1] += res[rr].y; v[2] += res[rr].z; v[3] += res[rr].w; }
+        if (ln) {
+          const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 256);
+          float q = 0.f;
+#pragma unroll
+          for (int e = 0; e < 4; e++) { const float dlt = v[e] - mean; q += dlt * dlt; }
+          const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / 256) + 1e-5f);
+          if (g.pre_ln_out != nullptr) *reinterpret_cast<float4*>(g.pre_ln_out + row * g.ldc + c4) = make_float4(v[0], v[1], v[2], v[3]);
+          v[0] = (v[0] - mean) * rstd * ga.x + be.x; v[1] = (v[1] - mean) * rstd * ga.y + be.y;
+          v[2] = (v[2] - mean) * rstd * ga.z + be.z; v[3] = (v[3] - mean) * rstd * ga.w + be.w;
+          if (lane == 0) {
+            if (g.ln_mean != nullptr) g.ln_mean[row] = mean;
+            if (g.ln_rstd != nullptr) g.ln_rstd[row] = rstd;
+          }
+        }
+        store_c4(g.C, c_bf, row * g.ldc + c4, v[0], v[1], v[2], v[3]);
+      }
+    }
   }
 }
 
@@ -336,33 +413,7 @@ __global__ __launch_bounds__(512) void gemm_nt_kernel(const hftt_gemm_nt_desc g)
 
   if (rowpass) {
     __syncthreads();
-    const int col = n0 + lane * 4;
-    for (int rr = 0; rr < BM / 8; rr++) {
-      const int row_l = wave * (BM / 8) + rr;
-      const long row = m0 + row_l;
-      if (row >= g.M) break;   // wave-uniform
-      if (col >= g.N) continue;
-      float4 v = *reinterpret_cast<const float4*>(stage + row_l * Cfg::STAGE_LD + lane * 4);
-      if (g.add_table != nullptr) {
-        const float4 t = *reinterpret_cast<const float4*>(g.add_table + (long)(row % g.add_mod) * g.N + col);
-        v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
-      }
-      if (g.gate != nullptr) {
-        const float4 gv = *reinterpret_cast<const float4*>(g.gate + row * g.ldg + col);
-        v.x = gv.x > 0.f ? v.x * g.gate_scale : 0.f; v.y = gv.y > 0.f ? v.y * g.gate_scale : 0.f;
-        v.z = gv.z > 0.f ? v.z * g.gate_scale : 0.f; v.w = gv.w > 0.f ? v.w * g.gate_scale : 0.f;
-      }
-      if (g.drop_p > 0.f) {
-        const uint32_t k4 = hftt_keep_quad(g.drop_seed, g.drop_site, ((uint64_t)row * (uint64_t)g.N + (uint64_t)col) >> 2, thr);
-        v.x = (k4 & 1u) ? v.x * inv_keep : 0.f; v.y = (k4 & 2u) ? v.y * inv_keep : 0.f;
-        v.z = (k4 & 4u) ? v.z * inv_keep : 0.f; v.w = (k4 & 8u) ? v.w * inv_keep : 0.f;
-      }
-      if (g.residual != nullptr) {
-        const float4 t = *reinterpret_cast<const float4*>(g.residual + (long)(row % g.res_mod) * g.ldr + col);
-        v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
-      }
-      *reinterpret_cast<float4*>(g.C + row * g.ldc + col) = v;
-    }
+    row_pass<BM / 8, 1, false, false>(g, m0, n0, stage, Cfg::STAGE_LD, n0 + lane * 4 < g.N, thr, inv_keep);
   }
 
   if (LN) {
@@ -398,269 +449,68 @@ __global__ __launch_bounds__(512) void gemm_nt_kernel(const hftt_gemm_nt_desc g)
   }
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// bf16 mode, A-stationary persistent form (N a multiple of 256, K <= 768).  These GEMMs are tall and short-K
-// (M ~ 10^5 tokens): the kernel is a streaming kernel with MFMA work hidden underneath.
-//   * persistent workgroups (2 per CU) walk the 32-row blocks of A;
-//   * a block of A (32 x K fp32) is read from HBM ONCE, converted to bf16 and kept in LDS; with DBUF the NEXT block's loads
-//     are issued before the current block's MFMA loop and land in the other LDS buffer afterwards (HBM latency hidden);
-//   * the (L2-resident) weight tiles of the current 256-wide N tile stream through a double-buffered LDS ring shared by the
-//     8 waves (a per-wave L2->register stream was measured 30 % slower: twice the L2 traffic in 32-byte pieces);
-//   * every N tile is finished through LDS: accumulators -> stage (the weight ring's space) -> one wave per row, 16 B per
-//     lane: table add, gate, dropout, residual, LayerNorm, float4 stores.  (Direct 4-byte stores from the accumulator
-//     layout were measured at 2.8 TB/s; the staged float4 form reaches > 4 TB/s.)
-// A is read once per GEMM regardless of N.
-// ------------------------------------------------------------------------------------------------------------------
-template <int APF, bool DBUF, bool ABF>
-__global__ __launch_bounds__(512, (DBUF ? 2 : 4)) void gemm_nt_as_kernel(const hftt_gemm_nt_desc g) {
-  constexpr int BM_ = 32;
-  constexpr int BN = 256;
-  constexpr int RSW = 40;                          // W tile row stride (bf16): 80 B
-  constexpr int W_ELEMS = BN * RSW;
-  constexpr int WCH = 2;                           // 16-byte chunks per thread per W tile (256 rows x 4 chunks / 512)
-  constexpr int STAGE_LD = BN + 4;
-  static_assert(BM_ * STAGE_LD * 4 <= 2 * W_ELEMS * 2, "stage must fit the weight ring");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int K = g.K;
-  const int RSA = K + 8;                           // A row stride (bf16): 2K+16 bytes, conflict-free ds_read_b128
-  const int A_ELEMS = BM_ * RSA;
-  unsigned short* As0 = reinterpret_cast<unsigned short*>(smem);
-  unsigned short* Ws = As0 + (DBUF ? 2 : 1) * A_ELEMS;
-  float* stage = reinterpret_cast<float*>(Ws);
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 31, lh = lane >> 5;
-  const int KT = K / 32;
-  const int NT = (g.N + BN - 1) / BN;
-  const int steps = NT * KT;
-  const int f4r = K >> 2;
-  const int a_total = BM_ * f4r;
-  const long nblk = (g.M + BM_ - 1) / BM_;
-  const unsigned short* Wb = reinterpret_cast<const unsigned short*>(g.W);
-  const uint32_t thr = hftt_keep_thr(g.drop_p);
-  const float inv_keep = hftt_keep_scale(g.drop_p);
-
-  uint4 wreg[WCH] = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
-  auto wload = [&](int s) {
-    const int nt = s / KT, kt = s - nt * KT;
+// A block of the A-stationary form: BM_ rows x K of A (row-major) -> bf16 in LDS (row stride RSA), every load of up to 8 chunks per thread
+// in flight before the first LDS write.  CH is the 16-byte chunk as it is stored: uint4 = 8 bf16, copied; float4 = 4 fp32, rounded to bf16.
+// Thread t owns chunks t, t + 512, ... of the block; (row, chunk) advance incrementally -- one integer division per thread instead of one
+// per load (the index math was ~20 % of the kernel's VALU time).  Rows past M or past the block read a clamped address and become zeros:
+// the loads stay unconditional (no branch, no early vmcnt wait).
+template <int BM_, typename CH>
+__device__ __forceinline__ void load_a_block(const hftt_gemm_nt_desc g, const long m0, unsigned short* As, const int RSA) {
+  constexpr bool ABF = std::is_same<CH, uint4>::value;
+  using T = typename std::conditional<ABF, unsigned short, float>::type;
+  constexpr int E = 16 / sizeof(T);                // elements per chunk
+  const T* A = reinterpret_cast<const T*>(g.A);
+  const int cpr = g.K / E;                         // chunks per row
+  const int total = BM_ * cpr;
+  const int drow = 512 / cpr, dch = 512 - drow * cpr;
+  int row = threadIdx.x / cpr, ch = threadIdx.x - row * cpr;
+  for (int base = 0; base < total; base += 512 * 8) {
+    CH v[8];
+    int rr[8], cc[8];
 #pragma unroll
-    for (int j = 0; j < WCH; j++) {
-      const int i = tid + 512 * j;
-      const int row = i >> 2, ch = i & 3;
-      wreg[j] = *reinterpret_cast<const uint4*>(Wb + (long)(nt * BN + row) * K + kt * 32 + ch * 8);
-    }
-  };
-  auto wstore = [&](int buf) {
-#pragma unroll
-    for (int j = 0; j < WCH; j++) {
-      const int i = tid + 512 * j;
-      const int row = i >> 2, ch = i & 3;
-      *reinterpret_cast<uint4*>(Ws + buf * W_ELEMS + row * RSW + ch * 8) = wreg[j];
-    }
-  };
-  constexpr bool a_bf = ABF;                       // A stored as bf16: APF counts 16-byte chunks either way
-  const bool c_bf = g.io_flags & HFTT_NT_C_BF16, gate_bf = g.io_flags & HFTT_NT_GATE_BF16, res_bf = g.io_flags & HFTT_NT_RES_BF16;
-  const int c8r = K >> 3;                          // 16-byte chunks per row when A is stored as bf16
-  const int a_total8 = BM_ * c8r;
-  float4 apf[APF];
-  auto aload = [&](long blk) {                     // HBM -> registers (APF x 16 B in flight per thread)
-    if (a_bf) {
-#pragma unroll
-      for (int u = 0; u < APF; u++) {
-        const int i = tid + 512 * u;
-        const int ic = i < a_total8 ? i : a_total8 - 1;
-        const int row = ic / c8r, c8 = ic - row * c8r;
-        const long grow = blk * BM_ + row;
-        const long gr = grow < g.M ? grow : (long)g.M - 1;
-        const float4 t = *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned short*>(g.A) + gr * g.lda + c8 * 8);
-        apf[u] = (i < a_total8 && grow < g.M) ? t : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      return;
+    for (int u = 0; u < 8; u++) {
+      rr[u] = row; cc[u] = ch;
+      const bool in = row < BM_;
+      const long grow = m0 + row;
+      const long gr = (in && grow < g.M) ? grow : (m0 < g.M ? m0 : 0);
+      const CH t = *reinterpret_cast<const CH*>(A + gr * g.lda + ch * E);
+      if constexpr (ABF) v[u] = (in && grow < g.M) ? t : make_uint4(0u, 0u, 0u, 0u);
+      else v[u] = (in && grow < g.M) ? t : make_float4(0.f, 0.f, 0.f, 0.f);
+      row += drow; ch += dch;
+      if (ch >= cpr) { ch -= cpr; row++; }
     }
 #pragma unroll
-    for (int u = 0; u < APF; u++) {
-      const int i = tid + 512 * u;
-      const int ic = i < a_total ? i : a_total - 1;        // clamped: loads stay unconditional
-      const int row = ic / f4r, c4 = ic - row * f4r;
-      const long grow = blk * BM_ + row;
-      const long gr = grow < g.M ? grow : (long)g.M - 1;
-      const float4 t = *reinterpret_cast<const float4*>(g.A + gr * g.lda + c4 * 4);
-      apf[u] = (i < a_total && grow < g.M) ? t : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  auto astore = [&](unsigned short* As) {          // registers -> bf16 -> LDS
-    if (a_bf) {
-#pragma unroll
-      for (int u = 0; u < APF; u++) {
-        const int i = tid + 512 * u;
-        if (i < a_total8) {
-          const int row = i / c8r, c8 = i - row * c8r;
-          *reinterpret_cast<float4*>(As + row * RSA + c8 * 8) = apf[u];
+    for (int u = 0; u < 8; u++)
+      if (rr[u] < BM_) {
+        // (fp32: the address as chunk pair + half -- with rr * RSA + cc * 4 hipcc keeps fewer loads in flight)
+        unsigned short* dst = ABF ? As + rr[u] * RSA + (cc[u] << 3) : As + rr[u] * RSA + ((cc[u] >> 1) << 3) + (cc[u] & 1) * 4;
+        if constexpr (ABF) {
+          *reinterpret_cast<uint4*>(dst) = v[u];
+        } else {
+          typedef __bf16 bf4_t __attribute__((ext_vector_type(4)));
+          const f32x4 fv = {v[u].x, v[u].y, v[u].z, v[u].w};
+          *reinterpret_cast<uint2*>(dst) = __builtin_bit_cast(uint2, __builtin_convertvector(fv, bf4_t));
         }
       }
-      return;
-    }
-#pragma unroll
-    for (int u = 0; u < APF; u++) {
-      const int i = tid + 512 * u;
-      if (i < a_total) {
-        const int row = i / f4r, c4 = i - row * f4r;
-        uint2 ph;
-        ph.x = f2bf(apf[u].x) | ((unsigned)f2bf(apf[u].y) << 16);
-        ph.y = f2bf(apf[u].z) | ((unsigned)f2bf(apf[u].w) << 16);
-        *reinterpret_cast<uint2*>(As + row * RSA + c4 * 4) = ph;
-      }
-    }
-  };
-
-  long blk = blockIdx.x;
-  if (blk >= nblk) return;
-  wload(0);
-  aload(blk);
-  astore(As0);
-  wstore(0);
-  __syncthreads();
-
-  int cur = 0;
-  for (; blk < nblk; blk += gridDim.x) {
-    const unsigned short* As = As0 + (DBUF ? cur : 0) * A_ELEMS;
-    const long m0 = blk * BM_;
-    const long nxt = blk + gridDim.x;
-    if (DBUF && nxt < nblk) aload(nxt);            // in flight during the whole MFMA loop of this block
-
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc[r] = 0.f;
-    int nt = 0, kt = 0;
-    for (int s = 0; s < steps; s++) {
-      const int buf = s & 1;
-      const bool last = (s + 1 == steps);
-      if (!last) wload(s + 1);
-      else if (nxt < nblk) wload(0);               // first weight tile of the next block
-      const unsigned short* Wt = Ws + buf * W_ELEMS;
-#pragma unroll
-      for (int ks = 0; ks < 2; ks++) {
-        const bf16x8 a = lds_read_b128(As + lr * RSA + kt * 32 + ks * 16 + lh * 8);
-        const bf16x8 b = lds_read_b128(Wt + (wave * 32 + lr) * RSW + ks * 16 + lh * 8);
-        acc = mfma32(a, b, acc);
-      }
-      if (kt != KT - 1) {
-        wstore(buf ^ 1);
-        kt++;
-      } else {
-        // ---------------- epilogue of N tile nt: accumulators -> stage (weight ring) -> row pass ----------------
-        const int n0 = nt * BN;
-        __syncthreads();                             // all MFMA reads of the weight ring are done
-        {
-          const int col_l = wave * 32 + lr;
-          const int col = n0 + col_l;
-          const float bv = (g.bias != nullptr && col < g.N) ? g.bias[col] : 0.f;
-#pragma unroll
-          for (int r = 0; r < 16; r++) {
-            float v = acc[r] + bv;
-            acc[r] = 0.f;
-            if (g.act == 1) v = fmaxf(v, 0.f);
-            stage[acc_row32(r, lh) * STAGE_LD + col_l] = v * g.out_scale;
-          }
-        }
-        __syncthreads();
-        {
-          constexpr int RPW = BM_ / 8;               // 4 rows per wave, finished two at a time
-          constexpr int RB = 2;
-          const int c4 = n0 + lane * 4;
-          float4 ga = make_float4(1.f, 1.f, 1.f, 1.f), be = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (g.ln_gamma != nullptr) {
-            ga = *reinterpret_cast<const float4*>(g.ln_gamma + c4);
-            be = *reinterpret_cast<const float4*>(g.ln_beta + c4);
-          }
-#pragma unroll 1
-          for (int rb = 0; rb < RPW; rb += RB) {
-          float4 tab[RB], gat[RB], res[RB];
-#pragma unroll
-          for (int rr = 0; rr < RB; rr++) {
-            const long row = m0 + wave * RPW + rb + rr;
-            tab[rr] = make_float4(0.f, 0.f, 0.f, 0.f); gat[rr] = tab[rr]; res[rr] = tab[rr];
-            const long rc = row < g.M ? row : (long)g.M - 1;      // clamped row: the (wave-uniform) pointer tests are the only branches
-            if (g.add_table != nullptr) tab[rr] = *reinterpret_cast<const float4*>(g.add_table + (long)(rc % g.add_mod) * g.N + c4);
-            if (g.gate != nullptr) gat[rr] = load_gate4(g.gate, gate_bf, rc * g.ldg + c4);
-            if (g.residual != nullptr) res[rr] = load_gate4(g.residual, res_bf, (long)(rc % g.res_mod) * g.ldr + c4);
-          }
-#pragma unroll
-          for (int rr = 0; rr < RB; rr++) {
-            const int row_l = wave * RPW + rb + rr;
-            const long row = m0 + row_l;
-            if (row < g.M) {         // wave-uniform
-              const float4 sv = *reinterpret_cast<const float4*>(stage + row_l * STAGE_LD + lane * 4);
-              float v[4] = {sv.x + tab[rr].x, sv.y + tab[rr].y, sv.z + tab[rr].z, sv.w + tab[rr].w};
-              if (g.gate != nullptr) {
-                v[0] = gat[rr].x > 0.f ? v[0] * g.gate_scale : 0.f; v[1] = gat[rr].y > 0.f ? v[1] * g.gate_scale : 0.f;
-                v[2] = gat[rr].z > 0.f ? v[2] * g.gate_scale : 0.f; v[3] = gat[rr].w > 0.f ? v[3] * g.gate_scale : 0.f;
-              }
-              if (g.drop_p > 0.f) {
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-                  v[e] = hftt_keep(g.drop_seed, g.drop_site, (uint64_t)row * g.N + c4 + e, thr) ? v[e] * inv_keep : 0.f;
-              }
-              v[0] += res[rr].x; v[1] += res[rr].y; v[2] += res[rr].z; v[3] += res[rr].w;
-              if (g.ln_gamma != nullptr) {              // N == 256: the row is complete
-                const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / BN);
-                float q = 0.f;
-#pragma unroll
-                for (int e = 0; e < 4; e++) { const float dlt = v[e] - mean; q += dlt * dlt; }
-                const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / BN) + 1e-5f);
-                if (g.pre_ln_out != nullptr) *reinterpret_cast<float4*>(g.pre_ln_out + row * g.ldc + c4) = make_float4(v[0], v[1], v[2], v[3]);
-                v[0] = (v[0] - mean) * rstd * ga.x + be.x; v[1] = (v[1] - mean) * rstd * ga.y + be.y;
-                v[2] = (v[2] - mean) * rstd * ga.z + be.z; v[3] = (v[3] - mean) * rstd * ga.w + be.w;
-                if (lane == 0) {
-                  if (g.ln_mean != nullptr) g.ln_mean[row] = mean;
-                  if (g.ln_rstd != nullptr) g.ln_rstd[row] = rstd;
-                }
-              }
-              store_c4(g.C, c_bf, row * g.ldc + c4, v[0], v[1], v[2], v[3]);
-            }
-          }
-          }
-        }
-        __syncthreads();                             // row pass finished reading the stage (= weight ring)
-        if (!last || nxt < nblk) wstore(last ? 0 : (buf ^ 1));
-        kt = 0;
-        nt++;
-      }
-      __syncthreads();
-    }
-    // ---- next block of A ----
-    if (nxt < nblk) {
-      if (DBUF) {
-        astore(As0 + (cur ^ 1) * A_ELEMS);
-        cur ^= 1;
-      } else {
-        aload(nxt);
-        astore(As0);
-      }
-      __syncthreads();
-    }
   }
 }
 
-template <int APF, bool DBUF, bool ABF>
-int launch_nt_as(const hftt_gemm_nt_desc& d, hipStream_t st) {
-  const int lds = ((DBUF ? 2 : 1) * 32 * (d.K + 8) + 2 * 256 * 40) * 2;
-  if (lds > 160 * 1024) { hftt_set_error("gemm_nt: K=%d too large for the A-stationary tile (%d B LDS)", d.K, lds); return 1; }
-  const long grid = hftt_persistent_grid("gemm_nt", ((long)d.M + 31) / 32, (lds <= 80 * 1024) ? 2 : 1);
-  if (grid < 0) return 2;
-  return hftt_launch<gemm_nt_as_kernel<APF, DBUF, ABF>>("gemm_nt", dim3((unsigned)grid), dim3(512), lds, st, d);
-}
-
 // ------------------------------------------------------------------------------------------------------------------
-// bf16 mode, A-stationary one-shot form for K <= 256 (measured faster there than the persistent form below): one
-// workgroup per BM-row block, A block loaded once (all loads in flight), weight tiles through a double-buffered LDS ring.
+// bf16 mode, A-stationary form (N a multiple of 256, K <= 768).  These GEMMs are tall and short-K (M ~ 10^5 tokens): a
+// streaming kernel with the MFMA work hidden underneath.  One workgroup per BM-row block; the block of A is read from HBM
+// ONCE regardless of N (all loads in flight), rounded to bf16 and kept in LDS; the (L2-resident) weight tiles stream
+// through a double-buffered LDS ring shared by the 8 waves (a per-wave L2 -> register stream was measured 30 % slower:
+// twice the L2 traffic in 32-byte pieces).
 //   MODE 0  plain (bias / ReLU / scale): stores straight from the accumulators;
-//   MODE 1  staged, single N tile (N == 256): tile -> LDS -> one wave per row, 16 B per lane (table add, gate, dropout,
-//           residual, LayerNorm with float4 traffic);
-//   MODE 2  staged, several N tiles (BM = 32): same row pass per N tile, staged in the weight ring.
+//   MODE 1  staged, single N tile (N == 256): tile -> LDS -> row_pass() (direct 4-byte stores from the accumulator layout
+//           were measured at 2.8 TB/s; the staged 16-byte form reaches > 4 TB/s);
+//   MODE 2  staged, several N tiles (BM = 32): the same row pass per N tile, staged in the weight ring.
 // ------------------------------------------------------------------------------------------------------------------
+// Waves per SIMD: at least 4 (128 VGPRs), and for the staged forms at most 4 -- their row pass holds ~100 VGPRs or more, so a fifth wave
+// is not to be had, and a scheduler left to hope for one (it cannot see the dynamic LDS either) gives up the k loop's overlap of the
+// LDS reads with the MFMAs for it: every MFMA of a step's first half then waits for lgkmcnt(0), measured +3 % at N = K = 256 with LayerNorm.
 template <int BM_, int MODE, bool EW = false, int PF = 1>
-__global__ __launch_bounds__(512, 4) void gemm_nt_as1_kernel(const hftt_gemm_nt_desc g) {
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, MODE == 0 ? 8 : 4))) void gemm_nt_as1_kernel(const hftt_gemm_nt_desc g) {
   constexpr int BN = 256;
   constexpr int WM = (BM_ == 32) ? 1 : 2;
   constexpr int WN = 8 / WM;
@@ -703,72 +553,19 @@ __global__ __launch_bounds__(512, 4) void gemm_nt_as1_kernel(const hftt_gemm_nt_
       w[j] = *reinterpret_cast<const uint4*>(Wb + (long)(nt * BN + row) * K + kt * 32 + ch * 8);
     }
   };
-  auto a_off = [&](int row, int c8) { return row * RSA + (c8 << 3); };
-  auto w_off = [&](int row, int ch) { return row * RSW + (ch << 3); };
   auto wstore = [&](const uint4 (&w)[WCH], int buf) {
 #pragma unroll
     for (int j = 0; j < WCH; j++) {
       const int i = tid + 512 * j;
       const int row = i >> 2, ch = i & 3;
-      *reinterpret_cast<uint4*>(Ws + buf * W_ELEMS + w_off(row, ch)) = w[j];
+      *reinterpret_cast<uint4*>(Ws + buf * W_ELEMS + row * RSW + ch * 8) = w[j];
     }
   };
 #pragma unroll
   for (int i = 0; i < PF; i++) wload(wr[i], i < steps ? i : steps - 1);
-  const bool a_bf = g.io_flags & HFTT_NT_A_BF16, c_bf = g.io_flags & HFTT_NT_C_BF16, gate_bf = g.io_flags & HFTT_NT_GATE_BF16, res_bf = g.io_flags & HFTT_NT_RES_BF16;
-  if (a_bf) {                                      // A stored as bf16: 16-byte chunks straight into LDS
-    // thread t owns 16-byte chunks t, t + 512, ... of the BM_ x K block (row-major); (row, chunk) advance incrementally --
-    // one integer division per thread instead of one per load (the index math was ~20 % of this kernel's VALU time)
-    const int c8r = K >> 3;
-    const int total = BM_ * c8r;
-    const int drow = 512 / c8r, dc8 = 512 - drow * c8r;
-    int row = tid / c8r, c8 = tid - row * c8r;
-    for (int base = 0; base < total; base += 512 * 8) {
-      uint4 v[8];
-      int rr[8], cc[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        rr[u] = row; cc[u] = c8;
-        const bool in = row < BM_;
-        const long grow = m0 + row;
-        const long gr = (in && grow < g.M) ? grow : (m0 < g.M ? m0 : 0);
-        const uint4 t = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(g.A) + gr * g.lda + c8 * 8);
-        v[u] = (in && grow < g.M) ? t : make_uint4(0u, 0u, 0u, 0u);
-        row += drow; c8 += dc8;
-        if (c8 >= c8r) { c8 -= c8r; row++; }
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++)
-        if (rr[u] < BM_) *reinterpret_cast<uint4*>(As + a_off(rr[u], cc[u])) = v[u];
-    }
-  } else {
-    const int f4r = K >> 2;
-    const int total = BM_ * f4r;
-    const int drow = 512 / f4r, dc4 = 512 - drow * f4r;
-    int row = tid / f4r, c4 = tid - row * f4r;
-    for (int base = 0; base < total; base += 512 * 8) {
-      float4 v[8];
-      int rr[8], cc[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        rr[u] = row; cc[u] = c4;
-        const bool in = row < BM_;                         // clamped address: loads stay unconditional (no branch, no early vmcnt wait)
-        const long grow = m0 + row;
-        const long gr = (in && grow < g.M) ? grow : (m0 < g.M ? m0 : 0);
-        const float4 t = *reinterpret_cast<const float4*>(g.A + gr * g.lda + c4 * 4);
-        v[u] = (in && grow < g.M) ? t : make_float4(0.f, 0.f, 0.f, 0.f);
-        row += drow; c4 += dc4;
-        if (c4 >= f4r) { c4 -= f4r; row++; }
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++)
-        if (rr[u] < BM_) {
-          typedef __bf16 bf4_t __attribute__((ext_vector_type(4)));
-          const f32x4 fv = {v[u].x, v[u].y, v[u].z, v[u].w};
-          *reinterpret_cast<uint2*>(As + a_off(rr[u], cc[u] >> 1) + (cc[u] & 1) * 4) = __builtin_bit_cast(uint2, __builtin_convertvector(fv, bf4_t));
-        }
-    }
-  }
+  const bool c_bf = g.io_flags & HFTT_NT_C_BF16;
+  if (g.io_flags & HFTT_NT_A_BF16) load_a_block<BM_, uint4>(g, m0, As, RSA);
+  else load_a_block<BM_, float4>(g, m0, As, RSA);
   wstore(wr[0], 0);
   __syncthreads();
 
@@ -900,61 +697,7 @@ __global__ __launch_bounds__(512, 4) void gemm_nt_as1_kernel(const hftt_gemm_nt_
       }
       if (MODE != 0) {
         __syncthreads();
-        constexpr int RPW = BM_ / 8;
-        constexpr int RB = RPW < 4 ? RPW : 4;
-        const int c4 = n0 + lane * 4;
-        float4 ga = make_float4(1.f, 1.f, 1.f, 1.f), be = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (g.ln_gamma != nullptr) {
-          ga = *reinterpret_cast<const float4*>(g.ln_gamma + c4);
-          be = *reinterpret_cast<const float4*>(g.ln_beta + c4);
-        }
-#pragma unroll 1
-        for (int rb = 0; rb < RPW; rb += RB) {
-          float4 tab[RB], gat[RB], res[RB];
-#pragma unroll
-          for (int rr = 0; rr < RB; rr++) {
-            const long row = m0 + wave * RPW + rb + rr;
-            tab[rr] = make_float4(0.f, 0.f, 0.f, 0.f); gat[rr] = tab[rr]; res[rr] = tab[rr];
-            const long rc = row < g.M ? row : (long)g.M - 1;      // clamped row: the (wave-uniform) pointer tests are the only branches
-            if (g.add_table != nullptr) tab[rr] = *reinterpret_cast<const float4*>(g.add_table + (long)(rc % g.add_mod) * g.N + c4);
-            if (g.gate != nullptr) gat[rr] = load_gate4(g.gate, gate_bf, rc * g.ldg + c4);
-            if (g.residual != nullptr) res[rr] = load_gate4(g.residual, res_bf, (long)(rc % g.res_mod) * g.ldr + c4);
-          }
-#pragma unroll
-          for (int rr = 0; rr < RB; rr++) {
-            const int row_l = wave * RPW + rb + rr;
-            const long row = m0 + row_l;
-            if (row < g.M) {
-              const float4 sv = *reinterpret_cast<const float4*>(stage + row_l * STAGE_LD + lane * 4);
-              float v[4] = {sv.x + tab[rr].x, sv.y + tab[rr].y, sv.z + tab[rr].z, sv.w + tab[rr].w};
-              if (g.gate != nullptr) {
-                v[0] = gat[rr].x > 0.f ? v[0] * g.gate_scale : 0.f; v[1] = gat[rr].y > 0.f ? v[1] * g.gate_scale : 0.f;
-                v[2] = gat[rr].z > 0.f ? v[2] * g.gate_scale : 0.f; v[3] = gat[rr].w > 0.f ? v[3] * g.gate_scale : 0.f;
-              }
-              if (g.drop_p > 0.f) {
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-                  v[e] = hftt_keep(g.drop_seed, g.drop_site, (uint64_t)row * g.N + c4 + e, thr) ? v[e] * inv_keep : 0.f;
-              }
-              v[0] += res[rr].x; v[1] += res[rr].y; v[2] += res[rr].z; v[3] += res[rr].w;
-              if (g.ln_gamma != nullptr) {
-                const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / BN);
-                float q = 0.f;
-#pragma unroll
-                for (int e = 0; e < 4; e++) { const float dlt = v[e] - mean; q += dlt * dlt; }
-                const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / BN) + 1e-5f);
-                if (g.pre_ln_out != nullptr) *reinterpret_cast<float4*>(g.pre_ln_out + row * g.ldc + c4) = make_float4(v[0], v[1], v[2], v[3]);
-                v[0] = (v[0] - mean) * rstd * ga.x + be.x; v[1] = (v[1] - mean) * rstd * ga.y + be.y;
-                v[2] = (v[2] - mean) * rstd * ga.z + be.z; v[3] = (v[3] - mean) * rstd * ga.w + be.w;
-                if (lane == 0) {
-                  if (g.ln_mean != nullptr) g.ln_mean[row] = mean;
-                  if (g.ln_rstd != nullptr) g.ln_rstd[row] = rstd;
-                }
-              }
-              store_c4(g.C, c_bf, row * g.ldc + c4, v[0], v[1], v[2], v[3]);
-            }
-          }
-        }
+        row_pass<BM_ / 8, (BM_ / 8 < 4 ? BM_ / 8 : 4), true, true>(g, m0, n0, stage, STAGE_LD, true, thr, inv_keep);
         if (s + 1 < steps) {
           __syncthreads();
           wstore(wr[0], buf ^ 1);
@@ -1000,10 +743,10 @@ int dispatch_nt(const hftt_gemm_nt_desc& d, hipStream_t st) {
   return launch_nt<64, PREC, false>(d, st);
 }
 
-// weight-tile prefetch distance of the one-shot kernels in k steps (HFTT_NT_PF = 1 | 2 | 4 overrides for measurements)
-int nt_pf() {
-  static const int pf = [] { const char* e = getenv("HFTT_NT_PF"); return (e && e[0] >= '1' && e[0] <= '4') ? e[0] - '0' : 2; }();
-  return pf;
+// weight-tile prefetch distance in k steps: the kernel unrolls groups of PF steps, so PF divides K / 32 -- 2 where that is even, else 1
+template <int BM_, int MODE, bool EW>
+int launch_nt_as1_pf(const hftt_gemm_nt_desc& d, hipStream_t st) {
+  return (d.K / 32) % 2 == 0 ? launch_nt_as1<BM_, MODE, EW, 2>(d, st) : launch_nt_as1<BM_, MODE, EW, 1>(d, st);
 }
 
 // bf16-mode dispatch
@@ -1015,31 +758,30 @@ int dispatch_nt_bf16(const hftt_gemm_nt_desc& d, hipStream_t st) {
                       (!d.pre_ln_out || ((uintptr_t)d.pre_ln_out & 15) == 0) &&
                       (!d.ln_gamma || d.N == 256);
   if (d.N % 256 == 0 && d.K <= 768 && d.M >= 256 && vec_ok) {
-    if (d.K <= 256) {       // one-shot form (measured: qkv 391 vs 518 us, o+LN 256 vs 300 us against the persistent form)
+    const bool pf2 = (d.K / 32) % 2 == 0;
+    if (d.K <= 256) {
       const bool rich = d.add_table || d.gate || d.drop_p > 0.f || d.residual || d.ln_gamma;
-      const int kt = d.K / 32;
-      const int pf = (nt_pf() >= 4 && kt % 4 == 0) ? 4 : (nt_pf() >= 2 && kt % 2 == 0) ? 2 : 1;
-      if (!rich) return pf == 4 ? launch_nt_as1<64, 0, false, 4>(d, st) : pf == 2 ? launch_nt_as1<64, 0, false, 2>(d, st) : launch_nt_as1<64, 0>(d, st);
+      if (!rich) return launch_nt_as1_pf<64, 0, false>(d, st);
       // dropout / bf16 ReLU gate on a bf16 C are elementwise: they ride in the direct packed-store epilogue (no staging pass)
       const bool elementwise = !d.add_table && !d.residual && !d.ln_gamma && (d.io_flags & HFTT_NT_C_BF16) && d.ldc % 2 == 0 &&
                                (!d.gate || ((d.io_flags & HFTT_NT_GATE_BF16) && d.ldg % 2 == 0));
-      if (elementwise) return pf == 4 ? launch_nt_as1<64, 0, true, 4>(d, st) : pf == 2 ? launch_nt_as1<64, 0, true, 2>(d, st) : launch_nt_as1<64, 0, true>(d, st);
-      if (d.N == 256) return pf == 4 ? launch_nt_as1<64, 1, false, 4>(d, st) : pf == 2 ? launch_nt_as1<64, 1, false, 2>(d, st) : launch_nt_as1<64, 1>(d, st);
+      if (elementwise) return launch_nt_as1_pf<64, 0, true>(d, st);
+      if (d.N == 256) return launch_nt_as1_pf<64, 1, false>(d, st);
       return launch_nt_as1<32, 2>(d, st);
     }
-    // measured at M = 262144 (us): K=512,N=256: persistent 450 | one-shot BM=64 486;  K=768,N=256: one-shot BM=64 504 |
-    // one-shot BM=32 713 | persistent double-buffered 744 | persistent 928
-    if (d.K > 512 && d.N == 256) {
-      const int kt = d.K / 32;
-      return (nt_pf() >= 4 && kt % 4 == 0) ? launch_nt_as1<64, 1, false, 4>(d, st) : (nt_pf() >= 2 && kt % 2 == 0) ? launch_nt_as1<64, 1, false, 2>(d, st) : launch_nt_as1<64, 1>(d, st);
-    }
-    // K = 512, N = 256 (measured at M = 262144, us): one-shot BM=64 (1 WG/CU) 254 | one-shot BM=32 275 | persistent 288 without
-    // LayerNorm; with it 354 | 340 | 369
-    if (d.K <= 512 && d.N == 256 && (d.K / 32) % 2 == 0 && nt_pf() >= 2)
-      return d.ln_gamma ? launch_nt_as1<32, 1, false, 2>(d, st) : launch_nt_as1<64, 1, false, 2>(d, st);
-    const bool abf = d.io_flags & HFTT_NT_A_BF16;
-    if (d.K <= 512) return abf ? launch_nt_as<4, false, true>(d, st) : launch_nt_as<8, false, false>(d, st);
-    return abf ? launch_nt_as<6, true, true>(d, st) : launch_nt_as<12, true, false>(d, st);
+    // N = 256, measured at M = 262144 (us): K = 768: BM=64 504 | BM=32 713;  K = 512: BM=64 (1 WG/CU) 254 | BM=32 275 without LayerNorm,
+    // with it 354 | 340
+    if (d.N == 256 && d.K > 512) return launch_nt_as1_pf<64, 1, false>(d, st);
+    if (d.N == 256 && pf2) return d.ln_gamma ? launch_nt_as1<32, 1, false, 2>(d, st) : launch_nt_as1<64, 1, false, 2>(d, st);
+    // Every other shape (N = 512, 768, ..; N = 256 with an odd K / 32) takes the BM = 32 form: one N tile after another over the resident A
+    // block.  Measured at M = 262144 (us, median of 60; in brackets a persistent form of the same loop -- 1 or 2 workgroups per CU walking
+    // the blocks, the next block's A loads under the MFMA loop -- whose own run-to-run spread was <= 11 us):
+    //   (N, K)        bf16 A, plain   bf16 A, +res -> bf16 C   fp32 A, plain   fp32 A, +res -> bf16 C
+    //   (512, 512)     490  (499)       502  (521)              493  (521)       521  (560)
+    //   (768, 512)     655  (673)       729  (764)              693  (729)       759  (810)
+    //   (512, 768)    1088 (1108)      1160 (1199)             1153 (1260)      1241 (1354)
+    //   (768, 768)    1623 (1690)      1718 (1815)             1687 (1853)      1770 (1961)
+    return launch_nt_as1<32, 2>(d, st);
   }
   if (d.io_flags & HFTT_NT_RES_BF16) { hftt_set_error("gemm_nt: a bf16 residual needs the A-stationary path (N %% 256 == 0, M >= 256, K <= 768)"); return 1; }
   return dispatch_nt<1>(d, st);      // small / ragged shapes: the k-tiled streaming kernel

@@ -386,6 +386,34 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const hftt_gemm_tn_desc g,
   }
 }
 
+// the segment that output row n belongs to (the last one that covers it), -1: none
+__device__ __forceinline__ int tn_segment(const hftt_gemm_tn_desc& g, const int n) {
+  int sg = -1;
+  for (int s = 0; s < g.n_seg; s++)
+    if (n >= g.seg_row0[s] && n < g.seg_row0[s] + g.seg_rows[s]) sg = s;
+  return sg;
+}
+
+// Bias rows of the two reduce kernels (their workgroups past the main ones; `block` counts from the first of them): one wave per output
+// row n, lanes stride over the splits, fixed-order tree reduce.
+__device__ __forceinline__ void tn_reduce_bias_rows(const hftt_gemm_tn_desc& g, const float* ws, const int splits, const long nws, const long sstride,
+                                                    const int block) {
+  const int n = block * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (n >= g.N) return;
+  const int sg = tn_segment(g, n);
+  if (sg < 0 || g.seg_db[sg] == nullptr) return;
+  const float* bs = ws + (long)splits * sstride;
+  float b = 0.f;
+  for (int q = lane; q < splits; q += 64) b += bs[(long)q * nws + n];
+  b = wave_sum(b);
+  if (lane == 0) {
+    float* db = g.seg_db[sg] + (n - g.seg_row0[sg]);
+    const float bv = b * g.out_scale;
+    *db = (g.beta != 0.f) ? (*db * g.beta + bv) : bv;
+  }
+}
+
 // Slab reduce: one thread per output element, splits summed in a FIXED order (bitwise reproducible) with 8 loads in flight.
 __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(const hftt_gemm_tn_desc g, const int splits, const long nws, const long kws,
                                                              const int nb_main) {
@@ -393,30 +421,12 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(const hftt_gemm_tn_
   const float* ws = reinterpret_cast<const float*>(g.ws);
   const long sstride = nws * kws;
   if ((int)blockIdx.x >= nb_main) {
-    // bias rows: one wave per output row n, lanes stride over the splits, fixed-order tree reduce
-    const int n = ((int)blockIdx.x - nb_main) * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (n >= g.N) return;
-    int sg = -1;
-    for (int s = 0; s < g.n_seg; s++)
-      if (n >= g.seg_row0[s] && n < g.seg_row0[s] + g.seg_rows[s]) sg = s;
-    if (sg < 0 || g.seg_db[sg] == nullptr) return;
-    const float* bs = ws + (long)splits * sstride;
-    float b = 0.f;
-    for (int q = lane; q < splits; q += 64) b += bs[(long)q * nws + n];
-    b = wave_sum(b);
-    if (lane == 0) {
-      float* db = g.seg_db[sg] + (n - g.seg_row0[sg]);
-      const float bv = b * g.out_scale;
-      *db = (g.beta != 0.f) ? (*db * g.beta + bv) : bv;
-    }
+    tn_reduce_bias_rows(g, ws, splits, nws, sstride, (int)blockIdx.x - nb_main);
     return;
   }
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)nb_main * blockDim.x) {
     const int n = (int)(idx / g.K_out), k = (int)(idx % g.K_out);
-    int sg = -1;
-    for (int s = 0; s < g.n_seg; s++)
-      if (n >= g.seg_row0[s] && n < g.seg_row0[s] + g.seg_rows[s]) sg = s;
+    const int sg = tn_segment(g, n);
     if (sg < 0) continue;
     const float* p = ws + (long)n * kws + k;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
@@ -444,22 +454,7 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_small_kernel(const hftt_ge
   const float* ws = reinterpret_cast<const float*>(g.ws);
   const long sstride = nws * kws;
   if ((int)blockIdx.x >= nb_main) {
-    const int n = ((int)blockIdx.x - nb_main) * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (n >= g.N) return;
-    int sg = -1;
-    for (int s = 0; s < g.n_seg; s++)
-      if (n >= g.seg_row0[s] && n < g.seg_row0[s] + g.seg_rows[s]) sg = s;
-    if (sg < 0 || g.seg_db[sg] == nullptr) return;
-    const float* bs = ws + (long)splits * sstride;
-    float b = 0.f;
-    for (int q = lane; q < splits; q += 64) b += bs[(long)q * nws + n];
-    b = wave_sum(b);
-    if (lane == 0) {
-      float* db = g.seg_db[sg] + (n - g.seg_row0[sg]);
-      const float bv = b * g.out_scale;
-      *db = (g.beta != 0.f) ? (*db * g.beta + bv) : bv;
-    }
+    tn_reduce_bias_rows(g, ws, splits, nws, sstride, (int)blockIdx.x - nb_main);
     return;
   }
   __shared__ float part[16][17];
@@ -482,9 +477,7 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_small_kernel(const hftt_ge
     float acc = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; i++) acc += part[i][e];
-    int sg = -1;
-    for (int q = 0; q < g.n_seg; q++)
-      if (n >= g.seg_row0[q] && n < g.seg_row0[q] + g.seg_rows[q]) sg = q;
+    const int sg = tn_segment(g, n);
     if (sg >= 0) {
       float* dst = g.seg_dw[sg] + (long)(n - g.seg_row0[sg]) * g.K_out + k;
       const float v = acc * g.out_scale;
@@ -500,6 +493,20 @@ int launch_tn(const hftt_gemm_tn_desc& d, const TnPlan& p, hipStream_t st) {
   dim3 grid((unsigned)(((p.splits + 7) / 8) * 8 * tiles), 1, 1);
   return hftt_launch<gemm_tn_kernel<TM, TN, NPASS, DYB, XB>>("gemm_tn", grid, dim3(512), Cfg::LDS_BYTES, st, d, p.k_tiles, p.rows_per_split, p.nws, p.kws,
                                                              tiles, p.splits);
+}
+
+// the tile the plan chose, for one form of the kernel; form 6 (HFTT_TN_DY_DROP) exists for the two 256-wide tiles only
+template <int NPASS, bool DYB, bool XB>
+int launch_tn_tile(const hftt_gemm_tn_desc& d, const TnPlan& p, hipStream_t st) {
+  if (p.tm == 2) return launch_tn<2, 4, NPASS, DYB, XB>(d, p, st);
+  if (p.tn == 4) return launch_tn<1, 4, NPASS, DYB, XB>(d, p, st);
+  if constexpr (NPASS == 6) {
+    hftt_set_error("gemm_tn: HFTT_TN_DY_DROP covers N >= 256 and K >= 256 (got N=%d K=%d)", d.N, d.K);
+    return 1;
+  } else {
+    if (p.tn == 2) return launch_tn<1, 2, NPASS, DYB, XB>(d, p, st);
+    return launch_tn<1, 1, NPASS, DYB, XB>(d, p, st);
+  }
 }
 
 }  // namespace
@@ -538,50 +545,25 @@ extern "C" int hftt_gemm_tn(const hftt_gemm_tn_desc* d, void* stream) {
   int rc;
   const bool dyb = d->io_flags & HFTT_TN_DY_BF16, xb = d->io_flags & HFTT_TN_X_BF16;
   if (d->npass == 3) {
-    if (p.tm == 2) rc = launch_tn<2, 4, 3, false, false>(*d, p, st);
-    else if (p.tn == 4) rc = launch_tn<1, 4, 3, false, false>(*d, p, st);
-    else if (p.tn == 2) rc = launch_tn<1, 2, 3, false, false>(*d, p, st);
-    else rc = launch_tn<1, 1, 3, false, false>(*d, p, st);
+    rc = launch_tn_tile<3, false, false>(*d, p, st);
   } else if (d->npass == 4 && (d->io_flags & HFTT_TN_DY_HI) && !dyb) {
 #ifndef HFTT_GRAD_HI_BUILD
     hftt_set_error("gemm_tn: this library was built without the gradient-rounding option (HFTT_BUILD_GRAD_HI=1 python nylon-amt_amd/build.py)");
     return 1;
 #else
-#define HFTT_TN_GO5(TM_, TN_) (xb ? launch_tn<TM_, TN_, 5, false, true>(*d, p, st) : launch_tn<TM_, TN_, 5, false, false>(*d, p, st))
-    if (p.tm == 2) rc = HFTT_TN_GO5(2, 4);
-    else if (p.tn == 4) rc = HFTT_TN_GO5(1, 4);
-    else if (p.tn == 2) rc = HFTT_TN_GO5(1, 2);
-    else rc = HFTT_TN_GO5(1, 1);
-#undef HFTT_TN_GO5
+    rc = xb ? launch_tn_tile<5, false, true>(*d, p, st) : launch_tn_tile<5, false, false>(*d, p, st);
 #endif
   } else if (d->npass == 4 && (d->io_flags & HFTT_TN_DY_DROP)) {
     HFTT_REQUIRE(!dyb && d->lddy == d->N && d->drop_p >= 0.f && d->drop_p < 1.f, "gemm_tn: HFTT_TN_DY_DROP takes an fp32 dY with lddy == N and 0 <= drop_p < 1");
     HFTT_REQUIRE(d->M < (1 << 24) && d->N % 4 == 0 && (((int64_t)d->M * d->N) >> 2) < (1ll << 32), "gemm_tn: HFTT_TN_DY_DROP indexes the site with 32-bit quads (M < 2^24, M * N < 2^34)");
-    if (p.tm == 2) rc = xb ? launch_tn<2, 4, 6, false, true>(*d, p, st) : launch_tn<2, 4, 6, false, false>(*d, p, st);
-    else if (p.tn == 4) rc = xb ? launch_tn<1, 4, 6, false, true>(*d, p, st) : launch_tn<1, 4, 6, false, false>(*d, p, st);
-    else { hftt_set_error("gemm_tn: HFTT_TN_DY_DROP covers N >= 256 and K >= 256 (got N=%d K=%d)", d->N, d->K); return 1; }
+    rc = xb ? launch_tn_tile<6, false, true>(*d, p, st) : launch_tn_tile<6, false, false>(*d, p, st);
   } else if (d->npass == 4) {
-#define HFTT_TN_GO4(TM_, TN_)                                                     \
-    (dyb ? launch_tn<TM_, TN_, 4, true, false>(*d, p, st) : (xb ? launch_tn<TM_, TN_, 4, false, true>(*d, p, st) : launch_tn<TM_, TN_, 4, false, false>(*d, p, st)))
-    if (p.tm == 2) rc = HFTT_TN_GO4(2, 4);
-    else if (p.tn == 4) rc = HFTT_TN_GO4(1, 4);
-    else if (p.tn == 2) rc = HFTT_TN_GO4(1, 2);
-    else rc = HFTT_TN_GO4(1, 1);
-#undef HFTT_TN_GO4
+    rc = dyb ? launch_tn_tile<4, true, false>(*d, p, st) : (xb ? launch_tn_tile<4, false, true>(*d, p, st) : launch_tn_tile<4, false, false>(*d, p, st));
   } else if (d->npass == 2) {
-    if (p.tm == 2) rc = launch_tn<2, 4, 2, false, false>(*d, p, st);
-    else if (p.tn == 4) rc = launch_tn<1, 4, 2, false, false>(*d, p, st);
-    else if (p.tn == 2) rc = launch_tn<1, 2, 2, false, false>(*d, p, st);
-    else rc = launch_tn<1, 1, 2, false, false>(*d, p, st);
+    rc = launch_tn_tile<2, false, false>(*d, p, st);
   } else {
-#define HFTT_TN_GO(TM_, TN_)                                                     \
-    (dyb ? (xb ? launch_tn<TM_, TN_, 1, true, true>(*d, p, st) : launch_tn<TM_, TN_, 1, true, false>(*d, p, st)) \
-         : (xb ? launch_tn<TM_, TN_, 1, false, true>(*d, p, st) : launch_tn<TM_, TN_, 1, false, false>(*d, p, st)))
-    if (p.tm == 2) rc = HFTT_TN_GO(2, 4);
-    else if (p.tn == 4) rc = HFTT_TN_GO(1, 4);
-    else if (p.tn == 2) rc = HFTT_TN_GO(1, 2);
-    else rc = HFTT_TN_GO(1, 1);
-#undef HFTT_TN_GO
+    rc = dyb ? (xb ? launch_tn_tile<1, true, true>(*d, p, st) : launch_tn_tile<1, true, false>(*d, p, st))
+             : (xb ? launch_tn_tile<1, false, true>(*d, p, st) : launch_tn_tile<1, false, false>(*d, p, st));
   }
   if (rc != 0) return rc;
   const long total = (long)d->N * d->K_out;

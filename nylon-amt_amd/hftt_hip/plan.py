@@ -56,12 +56,12 @@ def nt_meta(npass, a_hi, M, N, K, a_bf, c_bf, gate_bf, res_bf, add_table, gate, 
                 kname = 'gemm_nt_as1_kernel<64, 1, false, %d>' % pf
             else:
                 kname = 'gemm_nt_as1_kernel<32, 2, false, 1>'
+        elif N == 256 and K > 512:
+            kname = 'gemm_nt_as1_kernel<64, 1, false, %d>' % pf
         elif N == 256 and pf == 2:
-            kname = 'gemm_nt_as1_kernel<%d, 1, false, 2>' % (32 if (ln and K <= 512) else 64)
-        elif K <= 512:
-            kname = 'gemm_nt_as_kernel<4, false, true>' if a_bf else 'gemm_nt_as_kernel<8, false, false>'
+            kname = 'gemm_nt_as1_kernel<%d, 1, false, 2>' % (32 if ln else 64)
         else:
-            kname = 'gemm_nt_as_kernel<6, true, true>' if a_bf else 'gemm_nt_as_kernel<12, true, false>'
+            kname = 'gemm_nt_as1_kernel<32, 2, false, 1>'
     else:
         kname = 'gemm_nt_kernel<%d, %d, %s>' % (bn, 5 if a_hi else npass, _tf(ln))
     return {'kernel': kname, 'flops': 2.0 * M * N * K, 'bytes': float(nbytes), 'shape': (M, N, K)}

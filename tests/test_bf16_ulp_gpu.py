@@ -112,7 +112,8 @@ def _ln64(r, gam, bet, absr):
     return y, rstd * gam.double().abs() * (r.abs() + mu.abs() + absr) + bet.double().abs()
 
 
-@pytest.mark.parametrize('M,N,K', [(1000, 256, 256), (700, 768, 256), (515, 256, 512), (300, 256, 768), (257, 192, 96), (4096, 512, 256)])
+@pytest.mark.parametrize('M,N,K', [(1000, 256, 256), (700, 768, 256), (515, 256, 512), (300, 256, 768), (257, 192, 96), (4096, 512, 256),
+                                   (515, 512, 512), (300, 768, 768)])     # N, K > 256: the BM = 32 form, two / three N tiles, a ragged last block
 def test_gemm_nt_bf16_at_the_ulp(dev, M, N, K):
     """dispatch_nt_bf16: bf16 A, bf16 C, with bias + ReLU and (where the A-stationary path takes it) with a bf16 residual"""
     ops = _ops()

@@ -316,7 +316,9 @@ def _bf(t):
     return t.to(torch.bfloat16)
 
 
-@pytest.mark.parametrize('M,N,K', [(1000, 256, 256), (700, 768, 256), (515, 256, 512), (300, 256, 768), (257, 192, 96), (4096, 512, 256)])
+@pytest.mark.parametrize('M,N,K', [(1000, 256, 256), (700, 768, 256), (515, 256, 512), (300, 256, 768), (257, 192, 96), (4096, 512, 256),
+                                   (515, 512, 512), (300, 768, 768),      # N, K > 256: the BM = 32 form, two / three N tiles, a ragged last block
+                                   (515, 256, 352)])                      # N = 256 with an odd K / 32: the same form with LayerNorm
 def test_gemm_nt_bf16_storage(dev, M, N, K):
     ops = _ops()
     g = torch.Generator().manual_seed(M + N + K)
