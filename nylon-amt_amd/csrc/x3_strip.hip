@@ -155,10 +155,30 @@ __device__ __forceinline__ void chunk_load(XChunk& c, const float* p) {
   c.a = stream_load16(p);
   c.b = stream_load16(p + 4);
 }
+// a RAW chunk from / to eight fp32 values (bit copies; V: a float array or an accumulator vector, from element `at`)
+template <typename V>
+__device__ __forceinline__ void chunk_raw(XChunk& c, const V& v, int at = 0) {
+  c.a = u4v{__float_as_uint(v[at]), __float_as_uint(v[at + 1]), __float_as_uint(v[at + 2]), __float_as_uint(v[at + 3])};
+  c.b = u4v{__float_as_uint(v[at + 4]), __float_as_uint(v[at + 5]), __float_as_uint(v[at + 6]), __float_as_uint(v[at + 7])};
+}
+__device__ __forceinline__ void chunk_floats(const XChunk& c, float* v) {
+  v[0] = __uint_as_float(c.a.x); v[1] = __uint_as_float(c.a.y); v[2] = __uint_as_float(c.a.z); v[3] = __uint_as_float(c.a.w);
+  v[4] = __uint_as_float(c.b.x); v[5] = __uint_as_float(c.b.y); v[6] = __uint_as_float(c.b.z); v[7] = __uint_as_float(c.b.w);
+}
+// 16 values -> the (hi, lo) chunks of their two groups of eight (a tile's 16 features of the lane as the next product's operand)
+template <int E>
+__device__ __forceinline__ void x3_split16(const float* v, XChunk (&hf)[2]) {
+#pragma unroll
+  for (int u = 0; u < 2; u++) {
+    bf16x8 hi, lo;
+    x3_split8<E>(v + 8 * u, hi, lo);
+    hf[u].a = __builtin_bit_cast(u4v, hi); hf[u].b = __builtin_bit_cast(u4v, lo);
+  }
+}
 template <int E>
 __device__ __forceinline__ void chunk_convert(XChunk& c) {
-  const float v[8] = {__uint_as_float(c.a.x), __uint_as_float(c.a.y), __uint_as_float(c.a.z), __uint_as_float(c.a.w),
-                      __uint_as_float(c.b.x), __uint_as_float(c.b.y), __uint_as_float(c.b.z), __uint_as_float(c.b.w)};
+  float v[8];
+  chunk_floats(c, v);
   bf16x8 hi, lo;
   if (E == X3_BF16H) {                                 // hi half only (c.b is not read in this form)
     uint4 h;
@@ -172,11 +192,10 @@ __device__ __forceinline__ void chunk_convert(XChunk& c) {
 // a RAW chunk (elements 8 q .. 8 q + 7 of a dropout site's tensor) times its keep mask: the backward of a dropout whose output this strip is the
 // gradient of, applied as the strip arrives (the LayerNorm backward then writes no masked copy of its result)
 __device__ __forceinline__ void chunk_drop(XChunk& c, uint64_t seed, uint32_t site, uint64_t q0, uint32_t thr, float inv_keep) {
-  float v[8] = {__uint_as_float(c.a.x), __uint_as_float(c.a.y), __uint_as_float(c.a.z), __uint_as_float(c.a.w),
-                __uint_as_float(c.b.x), __uint_as_float(c.b.y), __uint_as_float(c.b.z), __uint_as_float(c.b.w)};
+  float v[8];
+  chunk_floats(c, v);
   drop8(v, seed, site, q0, thr, inv_keep);
-  c.a = u4v{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-  c.b = u4v{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])};
+  chunk_raw(c, v);
 }
 // hi + lo of a converted chunk back to fp32 (the residual of the fused FFN: the block input itself, to 2^-22)
 template <int E>
@@ -250,6 +269,20 @@ __device__ __forceinline__ void x3_slot_chunks(const unsigned char* slot, const 
   });
 }
 
+// accumulators start from a parameter row in LDS (the bias): one tile's 16 columns of the lane, or the eight tiles of a 256-column row
+__device__ __forceinline__ f32x16 acc_from_lds(const float* row) {
+  float b[16];
+  lds16f(row, b);
+  f32x16 acc;
+#pragma unroll
+  for (int q = 0; q < 16; q++) acc[q] = b[q];
+  return acc;
+}
+__device__ __forceinline__ void acc_from_lds(f32x16 (&acc)[8], const float* row) {
+#pragma unroll
+  for (int ot = 0; ot < 8; ot++) acc[ot] = acc_from_lds(row + ot * 32);
+}
+
 __device__ __forceinline__ void load16f(const float* p, float* v) {
 #pragma unroll
   for (int q = 0; q < 4; q++) { const float4 t = reinterpret_cast<const float4*>(p)[q]; v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w; }
@@ -269,16 +302,14 @@ constexpr int STG_BYTES_PER_WAVE = 16 * STG_RS * 4;
 // Addresses: gtile and the row-group offset (16 * half + 8 * k) * ld are wave-uniform (scalar registers, scalar multiplies); the lane's own part
 // is the 32-bit element offset ro = (lane >> 3) * ld + 4 * (lane & 7), one full-rate 24-bit multiply per call.  (Formed as 64-bit (row * ld) per
 // lane and store, the epilogue of the fc_o + LayerNorm kernel spent 236 v_mul_lo_u32 and 114 v_mad_u64_u32 -- quarter-rate -- on addresses.)
-__device__ __forceinline__ void tile_store_rows(float* stage, const float* v, int j, int h, int lane, float* gtile, long ld, bool ok) {
+// write_row(p): the lane writes its 64 bytes of the tile into its token's patch row p (128 bytes)
+template <typename W>
+__device__ __forceinline__ void tile_store_patch(float* stage, int j, int lane, float* gtile, long ld, bool ok, W&& write_row) {
   asm volatile("" : "+v"(lane));                    // (formed per call: hoisted out of the block loop the per-lane offsets of every tensor are spilled)
   const unsigned ro = __umul24((unsigned)lane >> 3, (unsigned)ld) + ((unsigned)lane & 7u) * 4u;
 #pragma unroll
   for (int half = 0; half < 2; half++) {
-    if ((j >> 4) == half) {
-      float* w = stage + (j & 15) * STG_RS + 16 * h;
-#pragma unroll
-      for (int q = 0; q < 4; q++) reinterpret_cast<float4*>(w)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-    }
+    if ((j >> 4) == half) write_row(stage + (j & 15) * STG_RS);
 #pragma unroll
     for (int k = 0; k < 2; k++) {
       const int r = (lane >> 3) + 8 * k;
@@ -286,6 +317,9 @@ __device__ __forceinline__ void tile_store_rows(float* stage, const float* v, in
       if (ok) stream_store16(gtile + (long)(half * 16 + 8 * k) * ld + ro, __builtin_bit_cast(u4v, t));
     }
   }
+}
+__device__ __forceinline__ void tile_store_rows(float* stage, const float* v, int j, int h, int lane, float* gtile, long ld, bool ok) {
+  tile_store_patch(stage, j, lane, gtile, ld, ok, [&](float* row) __attribute__((always_inline)) { store16f(row + 16 * h, v); });
 }
 
 // The same tile as bf16 (the saved FFN hidden and its gradient: operands of the weight-gradient products only, HFTT_SL_H_BF16): 64-byte row
@@ -316,27 +350,16 @@ __device__ __forceinline__ void tile_store_rows_bf16(float* stage, const float* 
 // further conversion -- x3_attn_pl.hip): the tile's 128 bytes per row hold its 32 hi halves (64 B), then its 32 lo halves -- the same
 // whole-line row segments as the fp32 form, through the same patch.
 __device__ __forceinline__ void tile_store_rows_f16pair(float* stage, const float* v, int j, int h, int lane, float* gtile, long ld, bool ok) {
-  asm volatile("" : "+v"(lane));                    // (formed per call, as in tile_store_rows)
-  const unsigned ro = __umul24((unsigned)lane >> 3, (unsigned)ld) + ((unsigned)lane & 7u) * 4u;
   bf16x8 hi0, lo0, hi1, lo1;
   x3_split8<X3_F16>(v, hi0, lo0);
   x3_split8<X3_F16>(v + 8, hi1, lo1);
-#pragma unroll
-  for (int half = 0; half < 2; half++) {
-    if ((j >> 4) == half) {
-      unsigned char* w = reinterpret_cast<unsigned char*>(stage + (j & 15) * STG_RS) + 32 * h;
-      *reinterpret_cast<bf16x8*>(w) = hi0;
-      *reinterpret_cast<bf16x8*>(w + 16) = hi1;
-      *reinterpret_cast<bf16x8*>(w + 64) = lo0;
-      *reinterpret_cast<bf16x8*>(w + 80) = lo1;
-    }
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-      const int r = (lane >> 3) + 8 * k;
-      const float4 t = *reinterpret_cast<const float4*>(stage + r * STG_RS + (lane & 7) * 4);
-      if (ok) stream_store16(gtile + (long)(half * 16 + 8 * k) * ld + ro, __builtin_bit_cast(u4v, t));
-    }
-  }
+  tile_store_patch(stage, j, lane, gtile, ld, ok, [&](float* row) __attribute__((always_inline)) {
+    unsigned char* w = reinterpret_cast<unsigned char*>(row) + 32 * h;
+    *reinterpret_cast<bf16x8*>(w) = hi0;
+    *reinterpret_cast<bf16x8*>(w + 16) = hi1;
+    *reinterpret_cast<bf16x8*>(w + 64) = lo0;
+    *reinterpret_cast<bf16x8*>(w + 80) = lo1;
+  });
 }
 __device__ __forceinline__ void load16h(const unsigned short* p, float* v) {      // 16 bf16 -> fp32
 #pragma unroll
@@ -390,6 +413,49 @@ __device__ __forceinline__ void x3_ln_rows(f32x16 (&acc)[8], const float* gamma_
   }
 }
 
+// What every kernel below opens with, after it has written its parameter rows to LDS: the ring (`slots` per block from `w`), the first block's
+// strip (XR chunks of the lane's row view `row0`) and three slots in flight.  On return slots 0 and 1 are complete in every wave and the
+// parameter rows are visible to all of them (they are read before the first slot's barrier).
+template <int XR>
+__device__ __forceinline__ XPipe x3_open(const unsigned short* w, int slots, unsigned char* smem, int wave, int lane, bool nofill, bool nobar,
+                                         XChunk (&xr)[XR], const float* row0) {
+  XPipe P;
+  P.w = w; P.S = slots; P.fill_pos = 0;
+  P.ring = (unsigned)(uintptr_t)HFTT_LDS_PTR(unsigned char, smem);
+  P.wave = wave; P.lane = lane;
+  P.nofill = nofill; P.nobar = nobar;
+#pragma unroll
+  for (int c = 0; c < XR; c++) chunk_load(xr[c], row0 + chunk_off(c));
+  P.fill<0>(); P.fill<1>(); P.fill<2>();
+  static_assert(FILL_AHEAD == 3, "prologue fills");
+  wait_lgkm0();
+  P.prologue_sync();
+  return P;
+}
+
+// The 16 slots of one K-outer step (256 features of the strip against eight output tiles).  The chunk set in the registers is this step's; as a
+// chunk is consumed its registers receive (`reload`) the same chunk position of the NEXT step's set from `nsrc` -- XR == 8: first the second half
+// of THIS set from `csrc` -- and the chunk of the next slot is converted in place one slot ahead (`convert`).
+template <int E, int XR>
+__device__ __forceinline__ void x3_kouter_slots(XPipe& P, const unsigned char* abase, XPre& pre, XChunk (&xr)[XR], f32x16 (&acc)[8],
+                                                bool reload, bool convert, const float* nsrc, const float* csrc) {
+  static_for<16>([&](auto c_c) __attribute__((always_inline)) {
+    constexpr int c = decltype(c_c)::value;
+    constexpr int BUF = c & 3;
+    P.begin_slot();
+    x3_slot_tiles<E>(abase + BUF * SLOT_BYTES, abase + ((BUF + 1) & 3) * SLOT_BYTES, pre, xr[c % XR], acc, [&](auto i_c) __attribute__((always_inline)) {
+      constexpr int i = decltype(i_c)::value;
+      if (i == 1) P.template refill<BUF>();
+      if (XR == 16) {
+        if (i == 5 && c > 0) { if (reload) chunk_load(xr[(c - 1) % XR], nsrc + chunk_off(c - 1)); }
+      } else {                                  // the registers of chunk c - 1 take chunk c - 1 + XR (of this set, then of the next)
+        if (i == 5 && c > 0) chunk_load(xr[(c - 1) % XR], (c - 1 + XR < 16) ? csrc + chunk_off((c - 1 + XR) & 15) : nsrc + chunk_off((c - 1 + XR) & 15));
+      }
+      if (i == 9 && c < 15) { if (convert) chunk_convert<E>(xr[(c + 1) % XR]); }
+    });
+  });
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // C = epi(x . Wl^T + bias), fp32 tensors, K = 256 * KCH, N = 256 * PASSES; LN: N == 256 with dropout / residual / LayerNorm
 // ---------------------------------------------------------------------------------------------------------------------
@@ -409,14 +475,7 @@ __global__ __launch_bounds__(256, XR == 16 ? 1 : 2) void x3_linear_kernel(const 
   const float* xb = reinterpret_cast<const float*>(g.x);
   float* cb = reinterpret_cast<float*>(g.C);
   float* preb = reinterpret_cast<float*>(g.pre_ln_out);
-  const float* rb = reinterpret_cast<const float*>(g.residual);
   const bool relu = g.flags & HFTT_SL_RELU;
-
-  XPipe P;
-  P.w = g.w; P.S = STEPS * 16; P.fill_pos = 0;
-  P.ring = (unsigned)(uintptr_t)HFTT_LDS_PTR(unsigned char, smem);
-  P.wave = wave; P.lane = lane;
-  P.nofill = XDBG(g, 1); P.nobar = XDBG(g, 2);
   const bool dbg_nostore = XDBG(g, 16), dbg_noload = XDBG(g, 32), dbg_noconv = XDBG(g, 64);
 
   auto tok_of = [&](long blk) { const long t = blk * 128 + wave * 32 + j; return t < g.M ? t : (long)g.M - 1; };
@@ -424,15 +483,7 @@ __global__ __launch_bounds__(256, XR == 16 ? 1 : 2) void x3_linear_kernel(const 
   for (int i = tid; i < g.N; i += 256) prm[i] = g.bias != nullptr ? g.bias[i] : 0.f;
   if (LN) { prm[g.N + tid] = g.ln_gamma[tid]; prm[g.N + 256 + tid] = g.ln_beta[tid]; }
   XChunk xr[XR];
-  {
-    const float* p0 = xb + tok_of(blockIdx.x) * g.ldx + 16 * h;
-#pragma unroll
-    for (int c = 0; c < XR; c++) chunk_load(xr[c], p0 + chunk_off(c));
-  }
-  P.fill<0>(); P.fill<1>(); P.fill<2>();
-  static_assert(FILL_AHEAD == 3, "prologue fills");
-  wait_lgkm0();
-  P.prologue_sync();                       // the parameter rows in LDS are read (by every wave) before the first slot's barrier
+  XPipe P = x3_open(g.w, STEPS * 16, smem, wave, lane, XDBG(g, 1), XDBG(g, 2), xr, xb + tok_of(blockIdx.x) * g.ldx + 16 * h);
   chunk_convert<E>(xr[0]);
 
   const uint32_t thr = hftt_keep_thr(g.drop_p);
@@ -452,40 +503,20 @@ __global__ __launch_bounds__(256, XR == 16 ? 1 : 2) void x3_linear_kernel(const 
     const float* prm_b = prm + zero;                  // (keeps the LDS parameter reads inside the iteration)
     for (int pass = 0; pass < PASSES; pass++) {
       f32x16 acc[8];
-#pragma unroll
-      for (int ot = 0; ot < 8; ot++) {                // accumulators start from the bias
-        float b[16];
-        lds16f(prm_b + pass * 256 + ot * 32 + 16 * hb, b);
-#pragma unroll
-        for (int q = 0; q < 16; q++) acc[ot][q] = b[q];
-      }
+      acc_from_lds(acc, prm_b + pass * 256 + 16 * hb);
       XPre pre;
       slot_head(abase, pre);                          // (every pass starts at ring buffer 0; inside the pass the slots hand `pre` on)
       for (int kc = 0; kc < KCH; kc++) {
-        // the chunk set in the registers at this step is k chunk kc; as a chunk is consumed its registers receive the same chunk position
-        // of the NEXT step's set (next k chunk, or k chunk 0 of the next pass / block).  KCH == 1: the set is re-used by every pass of
-        // the block and only replaced (by the next block's) during the last pass; conversion only in pass 0.
+        // the set in the registers at this step is k chunk kc, the NEXT step's set the next k chunk, or k chunk 0 of the next pass / block.
+        // KCH == 1: the set is re-used by every pass of the block and only replaced (by the next block's) during the last pass; conversion
+        // only in pass 0.
         const bool last_step = (pass == PASSES - 1) && (kc == KCH - 1);
         const bool reload = ((KCH > 1) || last_step) && !dbg_noload;
         const bool convert = ((KCH > 1) || (pass == 0)) && !dbg_noconv;
         // (past the last block: a harmless re-read of this block's rows)
         const float* nsrc = xb + lane_tok(last_step ? (nxt < nblk ? nxt : blk) : blk) * g.ldx + 16 * hb + (last_step ? 0 : ((kc + 1 == KCH) ? 0 : kc + 1) * 256);
         const float* csrc = (XR == 16) ? nsrc : xb + lane_tok(blk) * g.ldx + 16 * hb + kc * 256;       // XR == 8: the second half of THIS step's set
-        static_for<16>([&](auto c_c) __attribute__((always_inline)) {
-          constexpr int c = decltype(c_c)::value;
-          constexpr int BUF = c & 3;
-          P.begin_slot();
-          x3_slot_tiles<E>(abase + BUF * SLOT_BYTES, abase + ((BUF + 1) & 3) * SLOT_BYTES, pre, xr[c % XR], acc, [&](auto i_c) __attribute__((always_inline)) {
-            constexpr int i = decltype(i_c)::value;
-            if (i == 1) P.template refill<BUF>();
-            if (XR == 16) {
-              if (i == 5 && c > 0) { if (reload) chunk_load(xr[(c - 1) % XR], nsrc + chunk_off(c - 1)); }
-            } else {                                  // the registers of chunk c - 1 take chunk c - 1 + XR (of this set, then of the next)
-              if (i == 5 && c > 0) chunk_load(xr[(c - 1) % XR], (c - 1 + XR < 16) ? csrc + chunk_off((c - 1 + XR) & 15) : nsrc + chunk_off((c - 1 + XR) & 15));
-            }
-            if (i == 9 && c < 15) { if (convert) chunk_convert<E>(xr[(c + 1) % XR]); }
-          });
-        });
+        x3_kouter_slots<E>(P, abase, pre, xr, acc, reload, convert, nsrc, csrc);
         // the last chunk of the set is replaced here, and chunk 0 of the next set converted (its load is 15 slots old; XR == 8: 7 slots)
         if (XR == 16) { if (reload) chunk_load(xr[15], nsrc + chunk_off(15)); }
         else chunk_load(xr[XR - 1], nsrc + chunk_off(XR - 1));
@@ -494,10 +525,10 @@ __global__ __launch_bounds__(256, XR == 16 ? 1 : 2) void x3_linear_kernel(const 
       // ---------------- epilogue of this pass ----------------
       const long tokc_e = lane_tok(blk);
       const long tok = blk * 128 + wave * 32 + (tokc_e & 31);                 // (M % 32 == 0: the clamp never changes the low five bits)
-      const uint64_t rowq = ((uint64_t)tok * (uint64_t)g.N) >> 2;
       float* cwave = cb + (blk * 128 + wave * 32) * g.ldc + pass * 256;      // row 0 of this wave's strip, this pass's columns
+      const uint64_t rowq = ((uint64_t)tok * (uint64_t)g.N) >> 2;
       const long rrow = g.res_mod > 0 ? (long)((unsigned)tokc_e % (unsigned)g.res_mod) : tokc_e;
-      const float* rrow_p = rb + (HR ? rrow * g.ldr + pass * 256 + 16 * hb : 0);
+      const float* rrow_p = reinterpret_cast<const float*>(g.residual) + (HR ? rrow * g.ldr + pass * 256 + 16 * hb : 0);
       float rnext[16];
       if (HR) load16f(rrow_p, rnext);
 #pragma unroll
@@ -564,26 +595,12 @@ __global__ __launch_bounds__(256, 2) void x3_linear_n_kernel(const hftt_strip_de
   float* cb = reinterpret_cast<float*>(g.C);
   const float* rb = reinterpret_cast<const float*>(g.residual);
   const bool relu = g.flags & HFTT_SL_RELU;
-
-  XPipe P;
-  P.w = g.w; P.S = 2 * NT; P.fill_pos = 0;
-  P.ring = (unsigned)(uintptr_t)HFTT_LDS_PTR(unsigned char, smem);
-  P.wave = wave; P.lane = lane;
-  P.nofill = XDBG(g, 1); P.nobar = XDBG(g, 2);
   const bool dbg_nostore = XDBG(g, 16);
 
   auto tok_of = [&](long blk) { const long t = blk * 128 + wave * 32 + j; return t < g.M ? t : (long)g.M - 1; };
   for (int i = tid; i < g.N; i += 256) prm[i] = g.bias != nullptr ? g.bias[i] : 0.f;
   XChunk xr[16];
-  {
-    const float* p0 = xb + tok_of(blockIdx.x) * g.ldx + 16 * h;
-#pragma unroll
-    for (int c = 0; c < 16; c++) chunk_load(xr[c], p0 + chunk_off(c));
-  }
-  P.fill<0>(); P.fill<1>(); P.fill<2>();
-  static_assert(FILL_AHEAD == 3, "prologue fills");
-  wait_lgkm0();
-  P.prologue_sync();
+  XPipe P = x3_open(g.w, 2 * NT, smem, wave, lane, XDBG(g, 1), XDBG(g, 2), xr, xb + tok_of(blockIdx.x) * g.ldx + 16 * h);
 
   const uint32_t thr = hftt_keep_thr(g.drop_p);
   const float inv_keep = hftt_keep_scale(g.drop_p);
@@ -619,7 +636,7 @@ __global__ __launch_bounds__(256, 2) void x3_linear_n_kernel(const hftt_strip_de
       const int t = 2 * tp + half;
       const bool LAST = (t == NT - 1);
       f32x16 hacc;
-      {
+      {                                               // (acc_from_lds written out: through the call this kernel's forms move by -31 .. +11 registers)
         float b[16];
         lds16f(prm_b + t * 32 + 16 * hb, b);
 #pragma unroll
@@ -672,20 +689,36 @@ __global__ __launch_bounds__(256, 2) void x3_linear_n_kernel(const hftt_strip_de
 // fused two-GEMM block, d = 256, p = 32 * PT: mode 0 = FFN forward + residual + LayerNorm (fp16 halves), mode 1 = dX half of its
 // backward (bf16 halves).  Stream per hidden tile t: two slots of the first matrix (tile-major: k chunks 0-7, 8-15), then two slots of
 // the second (K-slice t: u = 0, 1).
+// HEAD (hftt_attn_out_ffn_fwd, mode 0): fc_o + dropout + residual + LayerNorm of descriptor o run on the same strip IN FRONT of the block -- the
+// two halves of an encoder / decoder layer behind its attention as one launch.  The head is x3_linear_kernel<X3_F16, true, 1, 1, true>'s block
+// (x3_kouter_slots, that kernel's row pass, x3_ln_rows); its LayerNorm output stays in the accumulator registers, is split into the strip's (hi, lo) chunks
+// there and never read back from memory -- in the inference plan it is not even written.  One weight stream of 16 + 4 PT slots per block:
+// fc_o (order 0), then the FFN's interleaved pair.  Results are bit-identical to the two launches: both are this text.
 // ---------------------------------------------------------------------------------------------------------------------
 // HH: h_out / gate are bf16 [M, p] (HFTT_SL_H_BF16) instead of fp32; GH (mode 1): the gradient strips (dy, dh) enter as their hi halves
-template <int MODE, int PT, bool HH, bool GH>
-__global__ __launch_bounds__(256, 1) void x3_mlp_kernel(const hftt_ffn_desc g) {
+struct XNoHead {};                                    // the head descriptor of the kernel without one
+// (one function body behind two one-line kernels: with the hidden-tile loop alone behind a call taking P, pre, xr and yacc by reference the fused
+// kernel spilled 3 / 7 registers to scratch.  The wrapper itself is not free of effect either: hipcc orders the blocks differently, and
+// x3_mlp_kernel<0, 16, false, false> takes 256 + 236 registers where it took 256 + 226 as a kernel of its own; no scratch in any form.)
+template <int MODE, int PT, bool HH, bool GH, bool HEAD, typename O>
+__device__ __forceinline__ void x3_mlp_block(const O& o, const hftt_ffn_desc& g) {
+  static_assert(!HEAD || MODE == 0, "the fc_o head belongs to the forward block");
   constexpr int E = (MODE == 0) ? X3_F16 : (GH ? X3_BF16H : X3_BF16);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 31, h = lane >> 5;
   constexpr int p = PT * 32;
+  constexpr int HP = HEAD ? 768 : 0;                  // the head's parameter rows
   const long nblk = ((long)g.M + 127) / 128;
-  float* prm = reinterpret_cast<float*>(smem + RING_BYTES);      // b1[p] | b2[256] | gamma[256] | beta[256] | four wave-private store patches
-  float* stage = reinterpret_cast<float*>(smem + RING_BYTES + 4 * (PT * 32 + 768) + wave * STG_BYTES_PER_WAVE);
-  const float* xb = reinterpret_cast<const float*>(g.x);
+  // [bo[256] | gamma1[256] | beta1[256]] | b1[p] | b2[256] | gamma[256] | beta[256] | four wave-private store patches
+  float* prm_head = reinterpret_cast<float*>(smem + RING_BYTES);
+  float* prm = prm_head + HP;
+  float* stage = reinterpret_cast<float*>(smem + RING_BYTES + 4 * (HP + PT * 32 + 768) + wave * STG_BYTES_PER_WAVE);
+  const float* xb;                                    // the strip the block loads: the head's (the attention output) or the FFN's own
+  long ldx;
+  if constexpr (HEAD) { xb = reinterpret_cast<const float*>(o.x); ldx = o.ldx; }
+  else { xb = reinterpret_cast<const float*>(g.x); ldx = g.ldx; }
   float* yb = reinterpret_cast<float*>(g.y);
   float* preb = reinterpret_cast<float*>(g.pre_ln_out);
   const float* rb = reinterpret_cast<const float*>(g.residual);
@@ -695,31 +728,26 @@ __global__ __launch_bounds__(256, 1) void x3_mlp_kernel(const hftt_ffn_desc g) {
   const unsigned short* gtb16 = reinterpret_cast<const unsigned short*>(g.gate);
   const bool has_res = (MODE == 1) && g.residual != nullptr;
 
-  XPipe P;
-  P.w = g.w; P.S = 4 * PT; P.fill_pos = 0;
-  P.ring = (unsigned)(uintptr_t)HFTT_LDS_PTR(unsigned char, smem);
-  P.wave = wave; P.lane = lane;
-  P.nofill = XDBG(g, 1); P.nobar = XDBG(g, 2);
-
   auto tok_of = [&](long blk) { const long t = blk * 128 + wave * 32 + j; return t < g.M ? t : (long)g.M - 1; };
 
+  if constexpr (HEAD) {
+    prm_head[tid] = o.bias != nullptr ? o.bias[tid] : 0.f;
+    prm_head[256 + tid] = o.ln_gamma[tid]; prm_head[512 + tid] = o.ln_beta[tid];
+  }
   for (int i = tid; i < p; i += 256) prm[i] = (MODE == 0 && g.b1 != nullptr) ? g.b1[i] : 0.f;
   prm[p + tid] = (MODE == 0 && g.b2 != nullptr) ? g.b2[tid] : 0.f;
   if (MODE == 0) { prm[p + 256 + tid] = g.ln_gamma[tid]; prm[p + 512 + tid] = g.ln_beta[tid]; }
 
   XChunk xr[16];
-  {
-    const float* p0 = xb + tok_of(blockIdx.x) * g.ldx + 16 * h;
-#pragma unroll
-    for (int c = 0; c < 16; c++) chunk_load(xr[c], p0 + chunk_off(c));
-  }
-  P.fill<0>(); P.fill<1>(); P.fill<2>();
-  static_assert(FILL_AHEAD == 3, "prologue fills");
-  wait_lgkm0();
-  P.prologue_sync();
+  const unsigned short* wstream;
+  if constexpr (HEAD) wstream = o.w; else wstream = g.w;
+  XPipe P = x3_open(wstream, (HEAD ? 16 : 0) + 4 * PT, smem, wave, lane, XDBG(g, 1), XDBG(g, 2), xr, xb + tok_of(blockIdx.x) * ldx + 16 * h);
 
   const uint32_t thr = hftt_keep_thr(g.drop_p);
   const float inv_keep = hftt_keep_scale(g.drop_p);
+  uint32_t thr_a = 0;                                 // the head's dropout
+  float inv_keep_a = 1.f;
+  if constexpr (HEAD) { thr_a = hftt_keep_thr(o.drop_p); inv_keep_a = hftt_keep_scale(o.drop_p); }
   const unsigned char* abase = smem + lane * 16;
   for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     int hb = h;
@@ -728,29 +756,67 @@ __global__ __launch_bounds__(256, 1) void x3_mlp_kernel(const hftt_ffn_desc g) {
     const bool wave_ok = (blk * 128 + wave * 32) < g.M;
     const long tokc = tok_of(blk);
     const long nxt = blk + gridDim.x;
-    const float* xrow_next = xb + (nxt < nblk ? tok_of(nxt) : tokc) * g.ldx + 16 * hb;
-    const uint64_t rowq_h = ((uint64_t)tok * (uint64_t)p) >> 2;
     int zero = 0;
     asm volatile("" : "+s"(zero));
     const float* prm_b = prm + zero;
-    // this block's strip: loaded by the previous block's epilogue (or the prologue), converted here.  Mode 1 with drop_p > 0: dy is the gradient
-    // of the block's OUTPUT dropout (site_o) and is masked here (the LayerNorm backward in front writes no masked copy)
-    if (MODE == 1 && g.drop_p > 0.f) {
-      const uint64_t rowq_x = ((uint64_t)tokc * 256ull) >> 2;
+    const float* xrow_next = xb + (nxt < nblk ? tok_of(nxt) : tokc) * ldx + 16 * hb;
+    const uint64_t rowq_h = ((uint64_t)tok * (uint64_t)p) >> 2;
+
+    if constexpr (HEAD) {
+      // ======== the head: fc_o over the attention-output strip (loaded by the previous block's last epilogue, or the prologue) ========
+      const float* prm_a = prm_b - HP;
+      chunk_convert<E>(xr[0]);
+      f32x16 acc[8];
+      acc_from_lds(acc, prm_a + 16 * hb);
+      XPre pre;
+      slot_head(abase, pre);
+      x3_kouter_slots<E>(P, abase, pre, xr, acc, false, true, nullptr, nullptr);
+      // scale, dropout (the attention branch's output site), residual = the layer input: the row pass of x3_linear_kernel's LayerNorm form, then
+      // LayerNorm 1.  (As one function shared with that kernel the pass costs x3_linear_kernel<X3_F16, true, 1, 2, true> a register, 494 -> 495, and
+      // puts 24 / 36 bytes of scratch into its half-set forms, which are free of it with the pass written out.)
+      const uint64_t rowq_a = ((uint64_t)tok * 256ull) >> 2;
+      const long rrow = o.res_mod > 0 ? (long)((unsigned)tokc % (unsigned)o.res_mod) : tokc;
+      const float* rrow_p = reinterpret_cast<const float*>(o.residual) + rrow * o.ldr + 16 * hb;
+      float rnext[16];
+      load16f(rrow_p, rnext);
 #pragma unroll
-      for (int c = 0; c < 16; c++) chunk_drop(xr[c], g.drop_seed, g.site_o, rowq_x + ((chunk_off(c) + 16 * hb) >> 2), thr, inv_keep);
+      for (int ot = 0; ot < 8; ot++) {
+        const int col0 = ot * 32 + 16 * hb;
+        float v[16], r[16];
+#pragma unroll
+        for (int q = 0; q < 16; q++) r[q] = rnext[q];
+        if (ot < 7) load16f(rrow_p + (ot + 1) * 32, rnext);
+#pragma unroll
+        for (int q = 0; q < 16; q++) v[q] = acc[ot][q] * o.out_scale;
+        if (o.drop_p > 0.f) drop16(v, o.drop_seed, o.drop_site, rowq_a + (col0 >> 2), thr_a, inv_keep_a);
+#pragma unroll
+        for (int q = 0; q < 16; q++) acc[ot][q] = v[q] + r[q];
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      float* pre1b = reinterpret_cast<float*>(o.pre_ln_out);
+      float* y1b = reinterpret_cast<float*>(o.C);      // LayerNorm-1 output: stored for the backward (training plan) or not at all (NULL)
+      const bool p16a = o.flags & HFTT_SL_PRE_BF16;
+      x3_ln_rows<true>(acc, prm_a + 256, prm_a + 512, hb, o.ln_mean, o.ln_rstd, tok, wave_ok, stage, j, lane,
+                       (pre1b != nullptr && !p16a) ? pre1b + (blk * 128 + wave * 32) * o.ldc : nullptr,
+                       y1b != nullptr ? y1b + (blk * 128 + wave * 32) * o.ldc : nullptr, o.ldc,
+                       (pre1b != nullptr && p16a) ? reinterpret_cast<unsigned short*>(pre1b) + (blk * 128 + wave * 32) * o.ldc : nullptr);
+      // the normalised rows become the FFN's strip: accumulator register q of tile ot is feature 32 ot + 16 h + q = chunk 2 ot + (q >> 3), element q & 7
+#pragma unroll
+      for (int c = 0; c < 16; c++) { chunk_raw(xr[c], acc[c >> 1], 8 * (c & 1)); chunk_convert<E>(xr[c]); }
+    } else {
+      // this block's strip: loaded by the previous block's epilogue (or the prologue), converted here.  Mode 1 with drop_p > 0: dy is the gradient
+      // of the block's OUTPUT dropout (site_o) and is masked here (the LayerNorm backward in front writes no masked copy)
+      if (MODE == 1 && g.drop_p > 0.f) {
+        const uint64_t rowq_x = ((uint64_t)tokc * 256ull) >> 2;
+#pragma unroll
+        for (int c = 0; c < 16; c++) chunk_drop(xr[c], g.drop_seed, g.site_o, rowq_x + ((chunk_off(c) + 16 * hb) >> 2), thr, inv_keep);
+      }
+#pragma unroll
+      for (int c = 0; c < 16; c++) chunk_convert<E>(xr[c]);
     }
-#pragma unroll
-    for (int c = 0; c < 16; c++) chunk_convert<E>(xr[c]);
 
     f32x16 yacc[8];
-#pragma unroll
-    for (int ot = 0; ot < 8; ot++) {
-      float b[16];
-      lds16f(prm_b + p + ot * 32 + 16 * hb, b);
-#pragma unroll
-      for (int q = 0; q < 16; q++) yacc[ot][q] = b[q];
-    }
+    acc_from_lds(yacc, prm_b + p + 16 * hb);
     float gnext[16];                                  // mode 1: stored hidden (the gate) of the next tile
     if (MODE == 1) { if (HH) load16h(gtb16 + tokc * g.ldg + 16 * hb, gnext); else load16f(gtb + tokc * g.ldg + 16 * hb, gnext); }
 
@@ -762,12 +828,7 @@ __global__ __launch_bounds__(256, 1) void x3_mlp_kernel(const hftt_ffn_desc g) {
     for (int t = 0; t < PT; t++) {
       // ---- first GEMM, hidden tile t: the whole strip against two slots ----
       f32x16 hacc;
-      {
-        float b[16];
-        lds16f(prm_b + t * 32 + 16 * hb, b);
-#pragma unroll
-        for (int q = 0; q < 16; q++) hacc[q] = b[q];
-      }
+      hacc = acc_from_lds(prm_b + t * 32 + 16 * hb);
       float gcur[16];
       if (MODE == 1) {
 #pragma unroll
@@ -801,16 +862,9 @@ __global__ __launch_bounds__(256, 1) void x3_mlp_kernel(const hftt_ffn_desc g) {
       }
       XChunk hf[2];
       if (XDBG(g, 1024)) {                           // (timing only: the raw accumulator bits as the operand -- no activation, dropout or split)
-        hf[0].a = u4v{__float_as_uint(hacc[0]), __float_as_uint(hacc[1]), __float_as_uint(hacc[2]), __float_as_uint(hacc[3])};
-        hf[0].b = u4v{__float_as_uint(hacc[4]), __float_as_uint(hacc[5]), __float_as_uint(hacc[6]), __float_as_uint(hacc[7])};
-        hf[1].a = u4v{__float_as_uint(hacc[8]), __float_as_uint(hacc[9]), __float_as_uint(hacc[10]), __float_as_uint(hacc[11])};
-        hf[1].b = u4v{__float_as_uint(hacc[12]), __float_as_uint(hacc[13]), __float_as_uint(hacc[14]), __float_as_uint(hacc[15])};
+        chunk_raw(hf[0], hacc, 0); chunk_raw(hf[1], hacc, 8);
       } else {
-        bf16x8 hi, lo;
-        x3_split8<E>(v, hi, lo);
-        hf[0].a = __builtin_bit_cast(u4v, hi); hf[0].b = __builtin_bit_cast(u4v, lo);
-        x3_split8<E>(v + 8, hi, lo);
-        hf[1].a = __builtin_bit_cast(u4v, hi); hf[1].b = __builtin_bit_cast(u4v, lo);
+        x3_split16<E>(v, hf);
       }
       const bool st_h = hob != nullptr;                                     // (wave-uniform)
       float* hwave = hob + (blk * 128 + wave * 32) * g.ldh + t * 32;          // row 0 of this wave's strip, this hidden tile's columns
@@ -876,223 +930,14 @@ __global__ __launch_bounds__(256, 1) void x3_mlp_kernel(const hftt_ffn_desc g) {
   }
   P.drain();
 }
-
-// ---------------------------------------------------------------------------------------------------------------------
-// fc_o + dropout + residual + LayerNorm  ->  FFN + residual + LayerNorm on ONE strip (hftt_attn_out_ffn_fwd, d = 256, p = 512, fp16 halves):
-// the two halves of an encoder / decoder layer behind its attention as one launch.  Phase A is x3_linear_kernel<X3_F16, true, 1, 1, true>'s block
-// (16 K-outer slots of fc_o, its epilogue), phase B x3_mlp_kernel<0>'s (64 slots); the LayerNorm output of phase A stays in the accumulator
-// registers, is split into the strip's (hi, lo) chunks there and never read back from memory -- in the inference plan it is not even written.
-// One weight stream of 80 slots per block: fc_o (order 0), then the FFN's interleaved pair.  Results are bit-identical to the two launches.
-// ---------------------------------------------------------------------------------------------------------------------
+template <int MODE, int PT, bool HH, bool GH>
+__global__ __launch_bounds__(256, 1) void x3_mlp_kernel(const hftt_ffn_desc g) { x3_mlp_block<MODE, PT, HH, GH, false>(XNoHead{}, g); }
 template <bool HH>
-__global__ __launch_bounds__(256, 1) void x3_oln_mlp_kernel(const hftt_strip_desc o, const hftt_ffn_desc g) {
-  constexpr int E = X3_F16, PT = 16, p = 512;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 31, h = lane >> 5;
-  const long nblk = ((long)g.M + 127) / 128;
-  float* prm = reinterpret_cast<float*>(smem + RING_BYTES);      // bo[256] | gamma1[256] | beta1[256] | b1[512] | b2[256] | gamma2[256] | beta2[256] | store patches
-  float* stage = reinterpret_cast<float*>(smem + RING_BYTES + 4 * 2048 + wave * STG_BYTES_PER_WAVE);
-  const float* cxb = reinterpret_cast<const float*>(o.x);        // the attention output (phase A's strip)
-  float* y1b = reinterpret_cast<float*>(o.C);                    // LayerNorm-1 output: stored for the backward (training plan) or not at all (NULL)
-  float* pre1b = reinterpret_cast<float*>(o.pre_ln_out);
-  const float* r1b = reinterpret_cast<const float*>(o.residual);
-  float* yb = reinterpret_cast<float*>(g.y);
-  float* preb = reinterpret_cast<float*>(g.pre_ln_out);
-  float* hob = reinterpret_cast<float*>(g.h_out);
-  unsigned short* hob16 = reinterpret_cast<unsigned short*>(g.h_out);
+__global__ __launch_bounds__(256, 1) void x3_oln_mlp_kernel(const hftt_strip_desc o, const hftt_ffn_desc g) { x3_mlp_block<0, 16, HH, false, true>(o, g); }
 
-  XPipe P;
-  P.w = o.w; P.S = 16 + 4 * PT; P.fill_pos = 0;
-  P.ring = (unsigned)(uintptr_t)HFTT_LDS_PTR(unsigned char, smem);
-  P.wave = wave; P.lane = lane;
-  P.nofill = false; P.nobar = false;
-
-  auto tok_of = [&](long blk) { const long t = blk * 128 + wave * 32 + j; return t < g.M ? t : (long)g.M - 1; };
-
-  prm[tid] = o.bias != nullptr ? o.bias[tid] : 0.f;
-  prm[256 + tid] = o.ln_gamma[tid]; prm[512 + tid] = o.ln_beta[tid];
-  for (int i = tid; i < p; i += 256) prm[768 + i] = g.b1 != nullptr ? g.b1[i] : 0.f;
-  prm[1280 + tid] = g.b2 != nullptr ? g.b2[tid] : 0.f;
-  prm[1536 + tid] = g.ln_gamma[tid]; prm[1792 + tid] = g.ln_beta[tid];
-
-  XChunk xr[16];
-  {
-    const float* p0 = cxb + tok_of(blockIdx.x) * o.ldx + 16 * h;
-#pragma unroll
-    for (int c = 0; c < 16; c++) chunk_load(xr[c], p0 + chunk_off(c));
-  }
-  P.fill<0>(); P.fill<1>(); P.fill<2>();
-  static_assert(FILL_AHEAD == 3, "prologue fills");
-  wait_lgkm0();
-  P.prologue_sync();
-
-  const uint32_t thr_a = hftt_keep_thr(o.drop_p), thr = hftt_keep_thr(g.drop_p);
-  const float inv_keep_a = hftt_keep_scale(o.drop_p), inv_keep = hftt_keep_scale(g.drop_p);
-  const unsigned char* abase = smem + lane * 16;
-  for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    int hb = h;
-    asm volatile("" : "+v"(hb));
-    const long tok = blk * 128 + wave * 32 + j;
-    const bool wave_ok = (blk * 128 + wave * 32) < g.M;
-    const long tokc = tok_of(blk);
-    const long nxt = blk + gridDim.x;
-    int zero = 0;
-    asm volatile("" : "+s"(zero));
-    const float* prm_b = prm + zero;
-
-    // ======== phase A: fc_o over the attention-output strip (loaded by the previous block's last epilogue, or the prologue) ========
-    chunk_convert<E>(xr[0]);
-    {
-      f32x16 acc[8];
-#pragma unroll
-      for (int ot = 0; ot < 8; ot++) {
-        float b[16];
-        lds16f(prm_b + ot * 32 + 16 * hb, b);
-#pragma unroll
-        for (int q = 0; q < 16; q++) acc[ot][q] = b[q];
-      }
-      XPre pre;
-      slot_head(abase, pre);
-      static_for<16>([&](auto c_c) __attribute__((always_inline)) {
-        constexpr int c = decltype(c_c)::value;
-        constexpr int BUF = c & 3;
-        P.begin_slot();
-        x3_slot_tiles<E>(abase + BUF * SLOT_BYTES, abase + ((BUF + 1) & 3) * SLOT_BYTES, pre, xr[c], acc, [&](auto i_c) __attribute__((always_inline)) {
-          constexpr int i = decltype(i_c)::value;
-          if (i == 1) P.template refill<BUF>();
-          if (i == 9 && c < 15) chunk_convert<E>(xr[c + 1]);
-        });
-      });
-      // ---- epilogue A: scale, dropout (the attention branch's output site), residual = the layer input, LayerNorm 1 ----
-      const uint64_t rowq_a = ((uint64_t)tok * 256ull) >> 2;
-      const long rrow = o.res_mod > 0 ? (long)((unsigned)tokc % (unsigned)o.res_mod) : tokc;
-      const float* rrow_p = r1b + rrow * o.ldr + 16 * hb;
-      float rnext[16];
-      load16f(rrow_p, rnext);
-#pragma unroll
-      for (int ot = 0; ot < 8; ot++) {
-        const int col0 = ot * 32 + 16 * hb;
-        float v[16], r[16];
-#pragma unroll
-        for (int q = 0; q < 16; q++) r[q] = rnext[q];
-        if (ot < 7) load16f(rrow_p + (ot + 1) * 32, rnext);
-#pragma unroll
-        for (int q = 0; q < 16; q++) v[q] = acc[ot][q] * o.out_scale;
-        if (o.drop_p > 0.f) drop16(v, o.drop_seed, o.drop_site, rowq_a + (col0 >> 2), thr_a, inv_keep_a);
-#pragma unroll
-        for (int q = 0; q < 16; q++) acc[ot][q] = v[q] + r[q];
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      const bool p16a = o.flags & HFTT_SL_PRE_BF16;
-      x3_ln_rows<true>(acc, prm_b + 256, prm_b + 512, hb, o.ln_mean, o.ln_rstd, tok, wave_ok, stage, j, lane,
-                       (pre1b != nullptr && !p16a) ? pre1b + (blk * 128 + wave * 32) * o.ldc : nullptr,
-                       y1b != nullptr ? y1b + (blk * 128 + wave * 32) * o.ldc : nullptr, o.ldc,
-                       (pre1b != nullptr && p16a) ? reinterpret_cast<unsigned short*>(pre1b) + (blk * 128 + wave * 32) * o.ldc : nullptr);
-      // the normalised rows become the FFN's strip: accumulator register q of tile ot is feature 32 ot + 16 h + q = chunk 2 ot + (q >> 3), element q & 7
-#pragma unroll
-      for (int ot = 0; ot < 8; ot++) {
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-          xr[2 * ot + u].a = u4v{__float_as_uint(acc[ot][8 * u]), __float_as_uint(acc[ot][8 * u + 1]), __float_as_uint(acc[ot][8 * u + 2]), __float_as_uint(acc[ot][8 * u + 3])};
-          xr[2 * ot + u].b = u4v{__float_as_uint(acc[ot][8 * u + 4]), __float_as_uint(acc[ot][8 * u + 5]), __float_as_uint(acc[ot][8 * u + 6]), __float_as_uint(acc[ot][8 * u + 7])};
-          chunk_convert<E>(xr[2 * ot + u]);
-        }
-      }
-    }
-
-    // ======== phase B: the FFN block of x3_mlp_kernel<0> on the strip in the registers ========
-    const float* xrow_next = cxb + (nxt < nblk ? tok_of(nxt) : tokc) * o.ldx + 16 * hb;
-    const uint64_t rowq_h = ((uint64_t)tok * (uint64_t)p) >> 2;
-    f32x16 yacc[8];
-#pragma unroll
-    for (int ot = 0; ot < 8; ot++) {
-      float b[16];
-      lds16f(prm_b + 1280 + ot * 32 + 16 * hb, b);
-#pragma unroll
-      for (int q = 0; q < 16; q++) yacc[ot][q] = b[q];
-    }
-    XPre pre;
-    slot_head(abase, pre);
-    for (int t = 0; t < PT; t++) {
-      f32x16 hacc;
-      {
-        float b[16];
-        lds16f(prm_b + 768 + t * 32 + 16 * hb, b);
-#pragma unroll
-        for (int q = 0; q < 16; q++) hacc[q] = b[q];
-      }
-      P.begin_slot();
-      x3_slot_chunks<E, 0>(abase + 0 * SLOT_BYTES, abase + 1 * SLOT_BYTES, pre, xr, hacc, [&](auto i_c) __attribute__((always_inline)) {
-        constexpr int i = decltype(i_c)::value;
-        if (i == 1) P.template refill<0>();
-      });
-      P.begin_slot();
-      x3_slot_chunks<E, 8>(abase + 1 * SLOT_BYTES, abase + 2 * SLOT_BYTES, pre, xr, hacc, [&](auto i_c) __attribute__((always_inline)) {
-        constexpr int i = decltype(i_c)::value;
-        if (i == 1) P.template refill<1>();
-      });
-      float v[16];
-      const int hcol0 = t * 32 + 16 * hb;
-#pragma unroll
-      for (int q = 0; q < 16; q++) v[q] = fmaxf(hacc[q], 0.f);
-      if (g.drop_p > 0.f) drop16(v, g.drop_seed, g.site_h, rowq_h + (hcol0 >> 2), thr, inv_keep);
-      XChunk hf[2];
-      {
-        bf16x8 hi, lo;
-        x3_split8<E>(v, hi, lo);
-        hf[0].a = __builtin_bit_cast(u4v, hi); hf[0].b = __builtin_bit_cast(u4v, lo);
-        x3_split8<E>(v + 8, hi, lo);
-        hf[1].a = __builtin_bit_cast(u4v, hi); hf[1].b = __builtin_bit_cast(u4v, lo);
-      }
-      const bool st_h = hob != nullptr;
-      float* hwave = hob + (blk * 128 + wave * 32) * g.ldh + t * 32;
-      unsigned short* hwave16 = hob16 + (blk * 128 + wave * 32) * g.ldh + t * 32;
-      P.begin_slot();
-      x3_slot_tiles<E>(abase + 2 * SLOT_BYTES, abase + 3 * SLOT_BYTES, pre, hf[0], yacc, [&](auto i_c) __attribute__((always_inline)) {
-        constexpr int i = decltype(i_c)::value;
-        if (i == 1) P.template refill<2>();
-        if (i == 4 && st_h) {
-          if (HH) tile_store_rows_bf16(stage, v, j, hb, lane, hwave16, g.ldh, wave_ok);
-          else tile_store_rows(stage, v, j, hb, lane, hwave, g.ldh, wave_ok);
-        }
-      });
-      P.begin_slot();
-      x3_slot_tiles<E>(abase + 3 * SLOT_BYTES, abase + 0 * SLOT_BYTES, pre, hf[1], yacc, [&](auto i_c) __attribute__((always_inline)) {
-        constexpr int i = decltype(i_c)::value;
-        if (i == 1) P.template refill<3>();
-      });
-    }
-    // ---- final epilogue: output dropout, residual = the strip (hi + lo), LayerNorm 2; the strip registers take the NEXT block's attention output ----
-    const uint64_t rowq = ((uint64_t)tok * 256ull) >> 2;
-    float* ywave = yb + (blk * 128 + wave * 32) * g.ldy;
-#pragma unroll
-    for (int ot = 0; ot < 8; ot++) {
-      const int col0 = ot * 32 + 16 * hb;
-      float v[16];
-#pragma unroll
-      for (int q = 0; q < 16; q++) v[q] = yacc[ot][q];
-      if (g.drop_p > 0.f) drop16(v, g.drop_seed, g.site_o, rowq + (col0 >> 2), thr, inv_keep);
-      float r[16];
-      chunk_values<E>(xr[2 * ot], r); chunk_values<E>(xr[2 * ot + 1], r + 8);
-#pragma unroll
-      for (int q = 0; q < 16; q++) yacc[ot][q] = v[q] + r[q];
-      chunk_load(xr[2 * ot], xrow_next + chunk_off(2 * ot));
-      chunk_load(xr[2 * ot + 1], xrow_next + chunk_off(2 * ot + 1));
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    const bool p16 = g.flags & HFTT_SL_PRE_BF16;
-    x3_ln_rows(yacc, prm_b + 1536, prm_b + 1792, hb, g.ln_mean, g.ln_rstd, tok, wave_ok, stage, j, lane,
-               (preb != nullptr && !p16) ? preb + (blk * 128 + wave * 32) * g.ldy : nullptr, ywave, g.ldy,
-               (preb != nullptr && p16) ? reinterpret_cast<unsigned short*>(preb) + (blk * 128 + wave * 32) * g.ldy : nullptr);
-  }
-  P.drain();
-}
-
-// Resident strip chunks of the one-pass K-outer forms without LayerNorm (the K = 512 / 768 dX products): 8 = half a set, 256 registers (24 bytes
-// of scratch on the K = 768 residual form), two workgroups per CU -- one's epilogue under the other's MFMAs.  Same box, three interleaved runs each
-// way: 277.07 against 276.17 clips/s (+0.3 %, profiles/r06_ab_dx_two_workgroups.txt).  The LayerNorm form (fc_o + residual + LayerNorm) stays at
+// Resident strip chunks of the one-pass K-outer forms without LayerNorm (the K = 512 / 768 dX products): 8 = half a set, 256 registers (the residual
+// forms have needed 24 / 36 bytes of scratch; tests/test_kernel_resources.py holds them to that), two workgroups per CU -- one's epilogue
+// under the other's MFMAs.  Same box, three interleaved runs each way: 277.07 against 276.17 clips/s (+0.3 %, profiles/r06_ab_dx_two_workgroups.txt).  The LayerNorm form (fc_o + residual + LayerNorm) stays at
 // 16: at 256 registers its epilogue spills (620 B per lane with 8 chunks, 468 B with 4, 332 B with the next block's strip loaded only behind
 // the epilogue) and the step LOSES 1.1 - 1.2 % in every one of those forms (same file).
 #ifndef HFTT_XL_XR
@@ -1169,14 +1014,7 @@ struct X3Stream {
     else load16f(reinterpret_cast<const float*>(base) + off, v);
   }
   static __device__ __forceinline__ void values8(const XChunk& c, float* v) { chunk_values<E>(c, v); }
-  static __device__ __forceinline__ void split16(const float* v, XChunk (&hf)[2]) {
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      bf16x8 hi, lo;
-      x3_split8<E>(v + 8 * u, hi, lo);
-      hf[u].a = __builtin_bit_cast(u4v, hi); hf[u].b = __builtin_bit_cast(u4v, lo);
-    }
-  }
+  static __device__ __forceinline__ void split16(const float* v, XChunk (&hf)[2]) { x3_split16<E>(v, hf); }
   static __device__ __forceinline__ void* rows(void* base, long off, bool h16) {
     return h16 ? static_cast<void*>(reinterpret_cast<unsigned short*>(base) + off) : static_cast<void*>(reinterpret_cast<float*>(base) + off);
   }
@@ -1294,50 +1132,52 @@ int hftt_x3_strip_linear(const hftt_strip_desc& d0, hipStream_t st) {
   return (d.flags & HFTT_SL_X3_BF16) ? dispatch_xl<X3_BF16>(d, st) : dispatch_xl<X3_F16>(d, st);
 }
 
+// the launch ladder of hftt_x3_strip_mlp: family x mode x gradient rounding, for one hidden format
+template <bool HH>
+static int launch_mlp_of(const hftt_ffn_desc& d, hipStream_t st, bool small, bool gh) {
+  if (small) return d.mode == 0 ? small_launch_mlp<X3MlpStream<0>, 0, HH>(d, st) : small_launch_mlp<X3MlpStream<1>, 1, HH>(d, st);
+  if (d.mode == 0) return launch_xm<0, HH>(d, st);
+#ifdef HFTT_GRAD_HI_BUILD
+  if (gh) return launch_xm<1, HH, true>(d, st);
+#endif
+  return launch_xm<1, HH, false>(d, st);
+}
+
 int hftt_x3_strip_mlp(const hftt_ffn_desc& d0, hipStream_t st) {
   hftt_ffn_desc d = d0;
   d.pad = x3_debug();
   HFTT_REQUIRE(d.ldh >= 0 && d.ldh < (1 << 24) && d.ldy >= 0 && d.ldy < (1 << 24),
                "x3_strip_mlp: ldh=%lld / ldy=%lld must be below 2^24 (24-bit row offsets)", (long long)d.ldh, (long long)d.ldy);
-  if (d.d == 64 && d.p == 128) {                      // the reference's default width: small_strip.h
+  const bool small = d.d == 64 && d.p == 128;         // the reference's default width: small_strip.h
+  const char* what = small ? "x3s_strip_mlp" : "x3_strip_mlp";
+  const bool gh = (d.flags & HFTT_SL_X3_GRAD_HI) != 0;
+  if (small) {
     HFTT_REQUIRE(d.M % 32 == 0, "x3s_strip_mlp: needs M %% 32 == 0 (M=%d)", d.M);
     HFTT_REQUIRE(!(d.flags & (HFTT_SL_X_BF16 | HFTT_SL_C_BF16 | HFTT_SL_RES_BF16 | HFTT_SL_X3_GRAD_HI)), "x3s_strip_mlp: fp32 tensors, no gradient-rounding form");
-    HFTT_REQUIRE(d.mode == 1 || d.residual == nullptr, "x3s_strip_mlp: the forward block's residual is its input");
-    HFTT_REQUIRE(((d.flags & HFTT_SL_X3_BF16) != 0) == (d.mode == 1), "x3s_strip_mlp: mode 0 takes fp16 halves (HFTT_SL_X3_F16), mode 1 bf16 halves");
+  } else {
+    HFTT_REQUIRE(d.p == 512 && d.M % 32 == 0, "x3_strip_mlp: needs p == 512 and M %% 32 == 0 (M=%d p=%d)", d.M, d.p);
+    HFTT_REQUIRE(!(d.flags & (HFTT_SL_X_BF16 | HFTT_SL_C_BF16 | HFTT_SL_RES_BF16)), "x3_strip_mlp: tensors are fp32 in the split modes");
+  }
+  HFTT_REQUIRE(d.mode == 1 || d.residual == nullptr, "%s: the forward block's residual is its input", what);
+  HFTT_REQUIRE(((d.flags & HFTT_SL_X3_BF16) != 0) == (d.mode == 1), "%s: mode 0 takes fp16 halves (HFTT_SL_X3_F16), mode 1 bf16 halves", what);
+  if (small) {
     HFTT_REQUIRE(d.ldx % 4 == 0 && d.ldy % 4 == 0 && ((uintptr_t)d.w & 15) == 0, "x3s_strip_mlp: rows / weight stream must be 16-byte aligned");
-    if (d.flags & HFTT_SL_H_BF16) {
-      HFTT_REQUIRE((d.h_out == nullptr || d.ldh % 8 == 0) && (d.gate == nullptr || d.ldg % 8 == 0), "x3s_strip_mlp: bf16 hidden rows must be 16-byte aligned");
-      return d.mode == 0 ? small_launch_mlp<X3MlpStream<0>, 0, true>(d, st) : small_launch_mlp<X3MlpStream<1>, 1, true>(d, st);
-    }
-    return d.mode == 0 ? small_launch_mlp<X3MlpStream<0>, 0, false>(d, st) : small_launch_mlp<X3MlpStream<1>, 1, false>(d, st);
-  }
-  HFTT_REQUIRE(d.p == 512 && d.M % 32 == 0, "x3_strip_mlp: needs p == 512 and M %% 32 == 0 (M=%d p=%d)", d.M, d.p);
-  HFTT_REQUIRE(!(d.flags & (HFTT_SL_X_BF16 | HFTT_SL_C_BF16 | HFTT_SL_RES_BF16)), "x3_strip_mlp: tensors are fp32 in the split modes");
-  HFTT_REQUIRE(d.mode == 1 || d.residual == nullptr, "x3_strip_mlp: the forward block's residual is its input");
-  HFTT_REQUIRE(((d.flags & HFTT_SL_X3_BF16) != 0) == (d.mode == 1), "x3_strip_mlp: mode 0 takes fp16 halves (HFTT_SL_X3_F16), mode 1 bf16 halves");
-  const bool gh = (d.flags & HFTT_SL_X3_GRAD_HI) != 0;
-  HFTT_REQUIRE(!gh || d.mode == 1, "x3_strip_mlp: HFTT_SL_X3_GRAD_HI belongs to the backward form");
+  } else {
+    HFTT_REQUIRE(!gh || d.mode == 1, "x3_strip_mlp: HFTT_SL_X3_GRAD_HI belongs to the backward form");
 #ifndef HFTT_GRAD_HI_BUILD
-  HFTT_REQUIRE(!gh, "x3_strip_mlp: this library was built without the gradient-rounding option (HFTT_BUILD_GRAD_HI=1 python nylon-amt_amd/build.py)");
+    HFTT_REQUIRE(!gh, "x3_strip_mlp: this library was built without the gradient-rounding option (HFTT_BUILD_GRAD_HI=1 python nylon-amt_amd/build.py)");
 #endif
-  if (d.flags & HFTT_SL_H_BF16) {
-    HFTT_REQUIRE((d.h_out == nullptr || d.ldh % 8 == 0) && (d.gate == nullptr || d.ldg % 8 == 0), "x3_strip_mlp: bf16 hidden rows must be 16-byte aligned");
-    if (d.mode == 0) return launch_xm<0, true>(d, st);
-#ifdef HFTT_GRAD_HI_BUILD
-    if (gh) return launch_xm<1, true, true>(d, st);
-#endif
-    return launch_xm<1, true, false>(d, st);
   }
-  if (d.mode == 0) return launch_xm<0, false>(d, st);
-#ifdef HFTT_GRAD_HI_BUILD
-  if (gh) return launch_xm<1, false, true>(d, st);
-#endif
-  return launch_xm<1, false, false>(d, st);
+  if (!(d.flags & HFTT_SL_H_BF16)) return launch_mlp_of<false>(d, st, small, gh);
+  HFTT_REQUIRE((d.h_out == nullptr || d.ldh % 8 == 0) && (d.gate == nullptr || d.ldg % 8 == 0), "%s: bf16 hidden rows must be 16-byte aligned", what);
+  return launch_mlp_of<true>(d, st, small, gh);
 }
 
 // hftt_attn_out_ffn_fwd: the fc_o + LayerNorm descriptor and the FFN descriptor of the two launches it replaces, unchanged, with o.C (the
 // LayerNorm-1 output) optional and the two weight streams adjacent (fc_o's 16 slots, then the FFN's 64)
-int hftt_x3_attn_out_ffn(const hftt_strip_desc& o, const hftt_ffn_desc& d, hipStream_t st) {
+int hftt_x3_attn_out_ffn(const hftt_strip_desc& o, const hftt_ffn_desc& d0, hipStream_t st) {
+  hftt_ffn_desc d = d0;
+  d.pad = x3_debug();                                // (the block's timing switches: ablation build only)
   HFTT_REQUIRE(o.ldc >= 0 && o.ldc < (1 << 24) && d.ldh >= 0 && d.ldh < (1 << 24) && d.ldy >= 0 && d.ldy < (1 << 24),
                "attn_out_ffn_fwd: ldc=%lld / ldh=%lld / ldy=%lld must be below 2^24 (24-bit row offsets)", (long long)o.ldc, (long long)d.ldh, (long long)d.ldy);
   HFTT_REQUIRE(o.M == d.M && o.M > 0 && o.M % 32 == 0 && o.N == 256 && o.K == 256 && d.d == 256 && d.p == 512 && d.mode == 0,

@@ -68,3 +68,30 @@ def test_attention_backward_on_planes_registers_and_occupancy():
         need = 3 if kt <= 3 else (2 if kt <= 4 or nw == 8 else 1)
         assert _get(v, 'Occupancy') >= need, (name, v)
     assert fwd >= 24
+
+
+@pytest.mark.skipif(HIPCC is None, reason='hipcc not found')
+def test_x3_strip_registers_and_occupancy():
+    """The split-precision strip kernels sit at the edge of the register file (the fused blocks at 256 + ~240 of 512), and their launchers size
+    the persistent grids on two workgroups per CU for every output-tile-major form and every half-set (XR == 8) form.  Scratch is allowed only
+    where it has been measured and accepted: the one-pass residual forms of the half-set kernel, 24 / 36 bytes per lane (x3_strip.hip, HFTT_XL_XR)."""
+    res = _resources('x3_strip.hip')
+    assert len(res) == 66
+    n_kernels = half_set = fused = 0
+    for name, v in res.items():
+        scratch, occ = _get(v, 'ScratchSize'), _get(v, 'Occupancy')
+        m = re.match(r'x3_linear_kernel<(\d), false, 1, ([23]), true, 8>', name)
+        if m:       # (element type, K / 256): the parent values of the four forms that had scratch
+            assert scratch <= {('4', '2'): 36, ('4', '3'): 24, ('2', '2'): 24, ('2', '3'): 36}[m.groups()], (name, v)
+        else:
+            assert scratch == 0, (name, v)
+        if name.startswith('x3_linear_n_kernel<'):
+            n_kernels += 1
+            assert occ >= 2, (name, v)
+        if re.match(r'x3_linear_kernel<.*, 8>$', name):
+            half_set += 1
+            assert occ >= 2, (name, v)
+        if name.startswith(('x3_mlp_kernel<', 'x3_oln_mlp_kernel<')):
+            fused += 1
+            assert scratch == 0 and _get(v, 'VGPRs') + _get(v, 'AGPRs') <= 512, (name, v)
+    assert (n_kernels, half_set, fused) == (18, 8, 6)

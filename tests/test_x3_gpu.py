@@ -635,12 +635,13 @@ def test_small_strip_linear_layernorm(dev, elem):
 
 
 @pytest.mark.parametrize('hbf', [False, True])
-@pytest.mark.parametrize('M,res_mod', [(256, 0), (4096 + 96, 0), (33024, 0), (1056, 88)])
+@pytest.mark.parametrize('M,res_mod', [(32, 0), (160, 0), (160, 88), (256, 0), (4096 + 96, 0), (33024, 0), (1056, 88)])
 def test_attention_output_and_ffn_as_one_launch_equal_the_two_launches_bit_for_bit(dev, M, res_mod, hbf):
     """hftt_attn_out_ffn_fwd (ABI v8) == hftt_strip_linear (fc_o + dropout + residual + LayerNorm) followed by hftt_ffn_res_ln_fwd: every stored
     tensor bit for bit, in the training form (everything a backward needs is written) and in the inference form (x1 is never written); the two
     launches themselves are held against fp64 by test_strip_linear_layernorm and test_fused_ffn_forward_and_dx.  33,024 tokens = 258 blocks for
-    256 resident workgroups; res_mod: the broadcast residual of the decoder's layer zero."""
+    256 resident workgroups; res_mod: the broadcast residual of the decoder's layer zero.  32 tokens: one live wave beside three clamped ones;
+    160: a second 128-token block with one live wave."""
     ops = _ops()
     d, pf = 256, 512
     g = torch.Generator().manual_seed(M + 7)

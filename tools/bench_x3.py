@@ -62,6 +62,9 @@ def main():
          4.0 * M * d * p, 4.0 * M * 2 * d)
     line('ffn fwd (training, hidden as bf16)', timeit(lambda: ops.ffn_res_ln_fwd(x, wf, p, b1, b2, gam, bet, drop_p=0.1, site_h=1, site_o=2, seed=5, x3=True, hidden_bf16=True)),
          4.0 * M * d * p, 4.0 * M * 3 * d + 2.0 * M * p)
+    wof = ops.x3_attn_out_ffn_pack(Wo, W1, W2)
+    line('o-proj + LN + ffn fwd as one launch', timeit(lambda: ops.attn_out_ffn_fwd(x, wof, bo, res, gam, bet, p, b1, b2, gam, bet, drop_p=0.1, site_a=3, site_h=1, site_o=2, seed=5)),
+         2.0 * M * d * d + 4.0 * M * d * p, 4.0 * M * (6 * d + p))
     hid = torch.relu(torch.randn(M, p, generator=g)).to(dev)
     wb = ops.x3_ffn_pack(W1, W2, backward=True)
     line('ffn bwd dx', timeit(lambda: ops.ffn_bwd_dx(x, wb, p, hid, gate_scale=1.1, residual=res, x3=True)), 4.0 * M * d * p, 4.0 * M * (3 * d + 2 * p))
