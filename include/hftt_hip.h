@@ -536,6 +536,61 @@ int64_t hftt_notes_ws_bytes(int64_t F, int32_t N);
 int hftt_notes_decode(const hftt_notes_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Many files at once (the file loop of evaluation/m_inference.py:77-165 around model/amt.py:66-176): the clip windows of a whole file list
+ * in one launch, and one decode over rolls that hold all files back to back.  Like the entry points above these were ADDED at ABI 8 and
+ * HFTT_ABI_VERSION stays 8.
+ *
+ * Clip windows (model/amt.py:89 a_input[i:i+width].T, with the min_value padding of :71-79 / :126-137 applied per window, not per file):
+ * `feature` holds the files' feature rows concatenated, file f = rows file_row0[f] .. file_row0[f + 1] (n_f rows, 0 allowed).  Window b shows
+ * frames win_start[b] .. win_start[b] + width of file win_file[b], counted from the file's frame 0 (the start may be negative or lie behind
+ * the file):
+ *     out[b, k, t] = feature[file_row0[f] + s + t, k]   when 0 <= s + t < n_f,   else fill
+ * and every element of a window whose file index is outside 0 .. n_files is fill: a window never shows a neighbouring file's frames.  A file
+ * whose rows do not lie inside 0 .. R is treated as outside as well (nothing is read there).  All pointers are DEVICE memory, nothing is read
+ * on the host.  One launch: a workgroup moves a tile of 64 frames x 64 bins through LDS -- read along the bins, written along the frames, both
+ * as whole 256-byte wave accesses; the tile row is padded by one word, so the column read meets 64 different banks.  One writer per element,
+ * no atomics, 64-bit indexing (R * n_bins may pass 2^31); n_bins and width need not be multiples of the tile.
+ * Refused in front of the launch: null pointers; B, width or n_bins < 1; n_files < 0; R < 0; B * n_bins * width >= 2^31.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {
+  const void* feature;                                           /* fp32 [R, n_bins] */
+  const int32_t* file_row0;                                      /* [n_files + 1] */
+  const int32_t* win_file; const int32_t* win_start;             /* [B] */
+  int32_t B, width, n_bins, n_files;
+  int64_t R;
+  float fill; int32_t pad;     /* fill: the config's min_value */
+  void* out;                                                     /* fp32 [B, n_bins, width] */
+} hftt_clip_windows_desc;
+int hftt_clip_windows(const hftt_clip_windows_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Segmented notes: `notes` describes rolls of F rows that hold n_seg segments (files) back to back, segment s = rows seg_row0[s] ..
+ * seg_row0[s + 1].  For every segment the notes are EXACTLY those of the one-file decode above on these rows alone, with F equal to the
+ * segment's length F_s: plateaus, peaks, the "next onset" default (F_s, (F_s - 1) * hop_sec), the edge rule of the peak time (frame 0 and
+ * F_s - 1) and every time loc * hop_sec are counted inside the segment; nothing is looked up across a border.  Order: segment-major, then
+ * pitch-major, then ascending onset frame.  seg_notes[s] = the number of notes in front of segment s; seg_notes[n_seg] == *n_notes = the
+ * number that exist; records behind cap are not written.  Segments of zero rows are legal and empty; n_seg == 0 or F == 0: zero notes.
+ * seg_row0_host is a HOST array, read and checked during the call ([0] == 0, non-decreasing, [n_seg] == F); seg_row0 holds the same values
+ * in DEVICE memory (uploaded by the caller) and is what the kernels read.  A segment whose device rows disagree with the host table's bounds
+ * is skipped, never followed out of the rolls or the workspace.
+ * Kernels: a table kernel writes the prefix of the per-segment chunk counts ceil(F_s / HFTT_NOTES_CHUNK) into ws; the scan runs one workgroup
+ * per (pitch, segment); counts lie [segment][pitch][chunk], so one prefix sum yields the order above and, at the segment heads, seg_notes; the
+ * emit kernel runs one workgroup per (chunk of any segment, pitch) and finds its segment in the table.  No atomics.
+ * Refused on top of the one-file decode's rejections: n_seg < 0 (or n_seg * N >= 2^31); a table pointer null at n_seg > 0; a table check
+ * failing; seg_notes null;
+ * ws_bytes below the value of the workspace helper (which is 0 for arguments outside the domain).
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {
+  hftt_notes_desc notes;       /* F = rows of all segments; ws sized by the helper below */
+  int32_t n_seg; int32_t pad;
+  const int32_t* seg_row0_host;                                  /* HOST [n_seg + 1] */
+  const void* seg_row0;                                          /* DEVICE int32 [n_seg + 1], the same values */
+  void* seg_notes;                                               /* DEVICE int32 [n_seg + 1], output */
+} hftt_notes_seg_desc;
+int64_t hftt_notes_seg_ws_bytes(int64_t F, int32_t N, int32_t n_seg);
+int hftt_notes_decode_seg(const hftt_notes_seg_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Label rendering on the device (csrc/labels.hip): note lists -> the frame labels that training consumes, the opposite direction of the
  * decoder above (corpus/conv_note2label.py:8-111 note2label).  Like the note decoder this entry point was ADDED at ABI 8 and HFTT_ABI_VERSION
  * stays 8: a caller that needs it looks the symbol up.

@@ -1,6 +1,8 @@
 // Note decoding on the device (gfx950): the host half of AMT.transcript / transcript_stride / mpe2note (model/amt.py) as kernels.
 //   hftt_stitch        a batch of model outputs -> rows of the file-long rolls, velocity logits -> int8 argmax (model/amt.py transcript)
 //   hftt_notes_decode  the four rolls of one file -> the note list of AMT.mpe2note before its final sort, pitch-major, ascending onset frame
+//   hftt_notes_decode_seg  the same for rolls that hold many files back to back, every file decoded on its own rows alone
+//   hftt_clip_windows  the clip windows of many files (a_input[i:i+width].T with the min_value padding), transposed through LDS in one launch
 // See include/hftt_hip.h for the contract.  No atomics anywhere: every output element has one writer, and the note order comes from prefix sums.
 #include <limits.h>
 #include <math.h>
@@ -115,19 +117,26 @@ __device__ double peak_time(const float* a, int N, int F, int i, double hop, flo
   return t;
 }
 
-// One workgroup per pitch.  Forward over the chunks: the run start at every chunk's first frame (both tracks).  Backward over the chunks: the
-// run end at every chunk's last frame, the next onset peak / offset peak / frame below thred_mpe / kept onset behind every chunk, and the
-// number of kept notes in it.  Two carried ints per track and direction; a run is decided in the chunk that holds the frame.
-__global__ __launch_bounds__(CH) void notes_scan_kernel(const hftt_notes_desc g, int nchunks) {
-  __shared__ int slots[16][4];
-  __shared__ int bc[8];
-  const int tid = threadIdx.x, j = blockIdx.x, N = g.N, F = (int)g.F;
-  const float* on = (const float*)g.onset + j;
-  const float* off = (const float*)g.offset + j;
-  const float* mp = (const float*)g.mpe + j;
-  const signed char* vel = (const signed char*)g.velocity + j;
-  int* st = (int*)g.ws + (long)j * nchunks * ST_INTS;
-  int* cnt = (int*)g.ws + (long)N * nchunks * ST_INTS + (long)j * nchunks;
+// The four tracks of one pitch over the rows that are decoded as one file: F rows from the base pointers, stride N
+struct notes_track {
+  const float* on; const float* off; const float* mp;
+  const signed char* vel;
+  int F;
+};
+
+__device__ inline notes_track track_of(const hftt_notes_desc& g, long row0, int F, int j) {
+  const long o = row0 * g.N + j;
+  return {(const float*)g.onset + o, (const float*)g.offset + o, (const float*)g.mpe + o, (const signed char*)g.velocity + o, F};
+}
+
+// One workgroup per pitch (and segment).  Forward over the chunks: the run start at every chunk's first frame (both tracks).  Backward over
+// the chunks: the run end at every chunk's last frame, the next onset peak / offset peak / frame below thred_mpe / kept onset behind every
+// chunk, and the number of kept notes in it.  Two carried ints per track and direction; a run is decided in the chunk that holds the frame.
+// st: ST_INTS ints per chunk, cnt: one int per chunk, both of this pitch's nchunks chunks.
+__device__ void notes_scan_body(const hftt_notes_desc& g, const notes_track& t, int nchunks, int* st, int* cnt, int (*slots)[4], int* bc) {
+  const int tid = threadIdx.x, N = g.N, F = t.F;
+  const float* on = t.on;
+  const float* off = t.off;
   int rs_on = 0, rs_off = 0;
   for (int k = 0; k < nchunks; k++) {
     const int f = k * CH + tid;
@@ -151,8 +160,8 @@ __global__ __launch_bounds__(CH) void notes_scan_kernel(const hftt_notes_desc g,
     int e_on, e_off, ex;
     const bool p_on = peak_of<2>(on, N, F, f, valid, g.thred_onset, st[k * ST_INTS + ST_RS_ON], re_on, slots, &e_on);
     const bool p_off = peak_of<4>(off, N, F, f, valid, g.thred_offset, st[k * ST_INTS + ST_RS_OFF], re_off, slots, &e_off);
-    const bool below = valid && mp[(long)f * N] < g.thred_mpe;
-    const bool kept = p_on && (g.mode_velocity != 0 || vel[(long)f * N] > 0);
+    const bool below = valid && t.mp[(long)f * N] < g.thred_mpe;
+    const bool kept = p_on && (g.mode_velocity != 0 || t.vel[(long)f * N] > 0);
     const int m_on = block_scan<OpMin, true>(p_on ? f : INT_MAX, slots[6], ex);
     const int m_off = block_scan<OpMin, true>(p_off ? f : INT_MAX, slots[7], ex);
     const int m_bl = block_scan<OpMin, true>(below ? f : INT_MAX, slots[8], ex);
@@ -169,6 +178,16 @@ __global__ __launch_bounds__(CH) void notes_scan_kernel(const hftt_notes_desc g,
     __syncthreads();
     re_on = bc[0]; re_off = bc[1]; nx_on = bc[2]; nx_off = bc[3]; nx_bl = bc[4]; nx_kp = bc[5];
   }
+}
+
+// one file: counts and state [pitch][chunk]
+__global__ __launch_bounds__(CH) void notes_scan_kernel(const hftt_notes_desc g, int nchunks) {
+  __shared__ int slots[16][4];
+  __shared__ int bc[8];
+  const int j = blockIdx.x;
+  int* st = (int*)g.ws + (long)j * nchunks * ST_INTS;
+  int* cnt = (int*)g.ws + (long)g.N * nchunks * ST_INTS + (long)j * nchunks;
+  notes_scan_body(g, track_of(g, 0, (int)g.F, j), nchunks, st, cnt, slots, bc);
 }
 
 // counts [n] (pitch-major, chunks ascending) -> their exclusive prefix sums in place; *total = the number of notes that exist
@@ -190,23 +209,19 @@ __global__ __launch_bounds__(CH) void notes_offsets_kernel(int* cnt, int n, int*
   if (tid == 0) *total = carry;
 }
 
-// One workgroup per (chunk, pitch): the per-onset part of AMT.mpe2note (model/amt.py), one thread per frame, for the onsets that are kept.
-__global__ __launch_bounds__(CH) void notes_emit_kernel(const hftt_notes_desc g, int nchunks, float h2) {
-  __shared__ int slots[16][4];
-  const int tid = threadIdx.x, k = blockIdx.x, j = blockIdx.y, N = g.N, F = (int)g.F;
-  const float* on = (const float*)g.onset + j;
-  const float* off = (const float*)g.offset + j;
-  const float* mp = (const float*)g.mpe + j;
-  const signed char* vel = (const signed char*)g.velocity + j;
-  const int* st = (const int*)g.ws + ((long)j * nchunks + k) * ST_INTS;
-  const int base = ((const int*)g.ws)[(long)N * nchunks * ST_INTS + (long)j * nchunks + k];
+// The per-onset part of AMT.mpe2note (model/amt.py) for chunk k of one pitch, one thread per frame, for the onsets that are kept.  st: the
+// chunk's ST_INTS ints of state; base: the number of notes in front of the chunk's first; j: the pitch index that the records carry.
+__device__ void notes_emit_body(const hftt_notes_desc& g, const notes_track& t, int j, int k, const int* st, int base, float h2, int (*slots)[4]) {
+  const int tid = threadIdx.x, N = g.N, F = t.F;
+  const float* on = t.on;
+  const float* off = t.off;
   const int f = k * CH + tid;
   const bool valid = f < F;
   int e, x_on, x_off, x_bl, x_kp, rank;
   const bool p_on = peak_of<0>(on, N, F, f, valid, g.thred_onset, st[ST_RS_ON], st[ST_RE_ON], slots, &e);
   const bool p_off = peak_of<2>(off, N, F, f, valid, g.thred_offset, st[ST_RS_OFF], st[ST_RE_OFF], slots, &e);
-  const bool below = valid && mp[(long)f * N] < g.thred_mpe;
-  const int velocity = p_on ? (int)vel[(long)f * N] : 0;
+  const bool below = valid && t.mp[(long)f * N] < g.thred_mpe;
+  const int velocity = p_on ? (int)t.vel[(long)f * N] : 0;
   const bool kept = p_on && (g.mode_velocity != 0 || velocity > 0);
   block_scan<OpMin, true>(p_on ? f : INT_MAX, slots[4], x_on);
   block_scan<OpMin, true>(p_off ? f : INT_MAX, slots[5], x_off);
@@ -215,7 +230,7 @@ __global__ __launch_bounds__(CH) void notes_emit_kernel(const hftt_notes_desc g,
   block_scan<OpAdd, false>(kept ? 1 : 0, slots[8], rank);
   if (!kept) return;
   const long idx = (long)base + rank;
-  if (idx >= g.cap) return;
+  if (idx < 0 || idx >= g.cap) return;
   const double hop = g.hop_sec;
   const int nxt_on = OpMin::f(x_on, st[ST_NX_ON]), nxt_off = OpMin::f(x_off, st[ST_NX_OFF]);      // first onset / offset peak behind f, F = none
   const int nxt_bl = OpMin::f(x_bl, st[ST_NX_BELOW]), nxt_kp = OpMin::f(x_kp, st[ST_NX_KEPT]);    // first frame >= f + 1 below thred_mpe; next kept onset
@@ -241,13 +256,146 @@ __global__ __launch_bounds__(CH) void notes_emit_kernel(const hftt_notes_desc g,
   else if (g.mode_offset == 1) offset_value = loc_offset >= loc_mpe ? time_offset : time_mpe;
   else offset_value = loc_offset <= loc_mpe ? time_offset : time_mpe;
   if (nxt_kp < F) {                                    // the trim between consecutive kept notes of one pitch
-    const double t = nxt_kp == nxt_on ? time_next : peak_time(on, N, F, nxt_kp, hop, h2);
-    if (t < offset_value) offset_value = t;
+    const double tk = nxt_kp == nxt_on ? time_next : peak_time(on, N, F, nxt_kp, hop, h2);
+    if (tk < offset_value) offset_value = tk;
   }
   ((int*)g.out_pitch)[idx] = j + g.note_min;
   ((int*)g.out_velocity)[idx] = velocity;
   ((double*)g.out_onset)[idx] = time_onset;
   ((double*)g.out_offset)[idx] = offset_value;
+}
+
+// one file: one workgroup per (chunk, pitch)
+__global__ __launch_bounds__(CH) void notes_emit_kernel(const hftt_notes_desc g, int nchunks, float h2) {
+  __shared__ int slots[16][4];
+  const int k = blockIdx.x, j = blockIdx.y;
+  const int* st = (const int*)g.ws + ((long)j * nchunks + k) * ST_INTS;
+  const int base = ((const int*)g.ws)[(long)g.N * nchunks * ST_INTS + (long)j * nchunks + k];
+  notes_emit_body(g, track_of(g, 0, (int)g.F, j), j, k, st, base, h2, slots);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// segmented notes: ws = [chunk table: tbl ints | state: ST_INTS ints per (segment, pitch, chunk) | counts: one int each], the two lists laid
+// out [segment][pitch][chunk]: element N * chunk0[s] + j * nchunks_s + k, with chunk0 the table's exclusive prefix of the chunk counts
+// ---------------------------------------------------------------------------------------------------------------------------------------
+struct seg_args {
+  hftt_notes_desc d;
+  const int* seg_row0;       // device [n_seg + 1]
+  int* seg_notes;            // device [n_seg + 1]
+  int n_seg, tbl, chunks;    // tbl: ints of the table region; chunks: the host table's chunk total (what the workspace holds)
+};
+
+// chunk0[s] = sum over s' < s of ceil(F_s' / CH), s = 0 .. n_seg, from the DEVICE row table.  A negative length counts as none.
+__global__ __launch_bounds__(CH) void notes_seg_table_kernel(const seg_args a) {
+  __shared__ int slot[4];
+  __shared__ int bc;
+  const int tid = threadIdx.x;
+  int* chunk0 = (int*)a.d.ws;
+  int carry = 0;
+  for (int s0 = 0; s0 <= a.n_seg; s0 += CH) {
+    const int s = s0 + tid;
+    int c = 0;
+    if (s < a.n_seg) {
+      const int len = a.seg_row0[s + 1] - a.seg_row0[s];
+      c = len > 0 ? (len + CH - 1) / CH : 0;
+    }
+    int ex;
+    const int inc = block_scan<OpAdd, false>(c, slot, ex);
+    if (s <= a.n_seg) chunk0[s] = carry + ex;
+    if (tid == CH - 1) bc = carry + inc;
+    __syncthreads();
+    carry = bc;
+    __syncthreads();
+  }
+}
+
+// rows and chunks of segment s as the device tables give them; false when they do not lie inside the rolls and the workspace (a device table
+// that differs from the host's checked one): the workgroup then does nothing
+__device__ inline bool seg_of(const seg_args& a, int s, long* row0, int* F, int* c0, int* nch) {
+  const int* chunk0 = (const int*)a.d.ws;
+  const long r0 = a.seg_row0[s], r1 = a.seg_row0[s + 1];
+  *row0 = r0; *F = (int)(r1 - r0); *c0 = chunk0[s]; *nch = chunk0[s + 1] - chunk0[s];
+  return r0 >= 0 && r1 > r0 && r1 <= (long)a.d.F && *c0 >= 0 && *nch == (*F + CH - 1) / CH && *c0 + *nch <= a.chunks;
+}
+
+// one workgroup per (pitch, segment): blockIdx.x = s * N + j
+__global__ __launch_bounds__(CH) void notes_seg_scan_kernel(const seg_args a) {
+  __shared__ int slots[16][4];
+  __shared__ int bc[8];
+  const int N = a.d.N, s = blockIdx.x / N, j = blockIdx.x % N;
+  long row0; int F, c0, nch;
+  if (!seg_of(a, s, &row0, &F, &c0, &nch)) return;
+  const long e = (long)N * c0 + (long)j * nch;
+  int* st = (int*)a.d.ws + a.tbl + e * ST_INTS;
+  int* cnt = (int*)a.d.ws + a.tbl + (long)N * a.chunks * ST_INTS + e;
+  notes_scan_body(a.d, track_of(a.d, row0, F, j), nch, st, cnt, slots, bc);
+}
+
+// seg_notes[s] = the prefix at segment s's first count (an empty segment shares the next one's), the total behind the last
+__global__ __launch_bounds__(CH) void notes_seg_heads_kernel(const seg_args a) {
+  const int s = blockIdx.x * CH + threadIdx.x;
+  if (s > a.n_seg) return;
+  const int* chunk0 = (const int*)a.d.ws;
+  const int* cnt = (const int*)a.d.ws + a.tbl + (long)a.d.N * a.chunks * ST_INTS;
+  const int c = chunk0[s];
+  a.seg_notes[s] = c >= 0 && c < a.chunks ? cnt[(long)a.d.N * c] : *(const int*)a.d.n_notes;
+}
+
+// one workgroup per (chunk of any segment, pitch): the segment is the last one whose first chunk is not behind blockIdx.x
+__global__ __launch_bounds__(CH) void notes_seg_emit_kernel(const seg_args a, float h2) {
+  __shared__ int slots[16][4];
+  const int c = blockIdx.x, j = blockIdx.y, N = a.d.N;
+  const int* chunk0 = (const int*)a.d.ws;
+  int lo = 0, hi = a.n_seg;                            // first s in [0, n_seg] with chunk0[s + 1] > c; n_seg: none
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (chunk0[mid + 1] > c) hi = mid; else lo = mid + 1;
+  }
+  if (lo >= a.n_seg) return;
+  long row0; int F, c0, nch;
+  if (!seg_of(a, lo, &row0, &F, &c0, &nch) || c < c0) return;
+  const int k = c - c0;
+  const long e = (long)N * c0 + (long)j * nch + k;
+  const int* st = (const int*)a.d.ws + a.tbl + e * ST_INTS;
+  const int base = ((const int*)a.d.ws)[a.tbl + (long)N * a.chunks * ST_INTS + e];
+  notes_emit_body(a.d, track_of(a.d, row0, F, j), j, k, st, base, h2, slots);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// clip windows: a tile of TILE frames x TILE bins through LDS, read along the bins, written along the frames
+// ---------------------------------------------------------------------------------------------------------------------------------------
+constexpr int TILE = 64;
+
+__global__ __launch_bounds__(256) void clip_windows_kernel(const hftt_clip_windows_desc d, int tiles_t, int tiles_k) {
+  __shared__ float tile[TILE][TILE + 1];              // + 1 word: the column read below meets 64 different banks
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long blk = blockIdx.x;
+  const int tt = (int)(blk % tiles_t);
+  const int tk = (int)((blk / tiles_t) % tiles_k);
+  const int b = (int)(blk / ((long)tiles_t * tiles_k));
+  const int t0 = tt * TILE, k0 = tk * TILE;
+  const int f = d.win_file[b];
+  const long s = d.win_start[b];
+  long r0 = 0, nf = 0;
+  if (f >= 0 && f < d.n_files) {
+    r0 = d.file_row0[f];
+    nf = (long)d.file_row0[f + 1] - r0;
+    if (r0 < 0 || nf < 0 || r0 + nf > d.R) nf = 0;    // rows outside the feature array: nothing of this file is read
+  }
+  const float* feat = (const float*)d.feature;
+  for (int i = w; i < TILE; i += 4) {                  // a wave reads 64 bins of one frame: 256 contiguous bytes
+    const long fr = s + t0 + i;
+    const int k = k0 + lane;
+    float v = d.fill;
+    if (t0 + i < d.width && k < d.n_bins && fr >= 0 && fr < nf) v = feat[(r0 + fr) * d.n_bins + k];
+    tile[i][lane] = v;
+  }
+  __syncthreads();
+  float* out = (float*)d.out;
+  for (int i = w; i < TILE; i += 4) {                  // a wave writes 64 frames of one bin: 256 contiguous bytes
+    const int k = k0 + i, t = t0 + lane;
+    if (k < d.n_bins && t < d.width) out[((long)b * d.n_bins + k) * d.width + t] = tile[lane][i];
+  }
 }
 
 inline long notes_chunks(long F) { return (F + CH - 1) / CH; }
@@ -292,31 +440,111 @@ extern "C" int64_t hftt_notes_ws_bytes(int64_t F, int32_t N) {
   return 64 + 4 * (int64_t)(ST_INTS + 1) * N * notes_chunks(F);
 }
 
+// the rejections that the one-file and the segmented decode share (everything but the workspace size); 0 = accepted
+static int notes_check(const hftt_notes_desc* d, const char* what) {
+  HFTT_REQUIRE(d->F >= 0, "%s: F=%ld is negative", what, (long)d->F);
+  HFTT_REQUIRE(d->N >= 1 && d->N <= 128, "%s: N=%d outside 1..128", what, d->N);
+  HFTT_REQUIRE((long)d->F * d->N < (1l << 31), "%s: F=%ld frames of N=%d exceed 2^31 elements (the note count is an int32)", what, (long)d->F, d->N);
+  HFTT_REQUIRE(d->cap >= 0, "%s: cap=%d is negative", what, d->cap);
+  HFTT_REQUIRE(d->mode_velocity == 0 || d->mode_velocity == 1, "%s: mode_velocity=%d (0 = ignore_zero, 1 = org)", what, d->mode_velocity);
+  HFTT_REQUIRE(d->mode_offset >= 0 && d->mode_offset <= 2, "%s: mode_offset=%d (0 = shorter, 1 = longer, 2 = offset)", what, d->mode_offset);
+  HFTT_REQUIRE(d->n_notes, "%s: n_notes is null", what);
+  HFTT_REQUIRE(d->cap == 0 || (d->out_pitch && d->out_velocity && d->out_onset && d->out_offset),
+               "%s: null output (out_pitch / out_velocity / out_onset / out_offset) at cap=%d", what, d->cap);
+  HFTT_REQUIRE(d->F == 0 || (d->onset && d->offset && d->mpe && d->velocity), "%s: null roll (onset / offset / mpe / velocity)", what);
+  HFTT_REQUIRE(d->ws, "%s: ws is null", what);
+  return 0;
+}
+
+static int notes_clear(const char* what, void* p, size_t bytes, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(p, 0, bytes, st);
+  if (e != hipSuccess) { hftt_set_error("%s: clearing the counts failed: %s", what, hipGetErrorString(e)); return 2; }
+  return 0;
+}
+
 extern "C" int hftt_notes_decode(const hftt_notes_desc* d, void* stream) {
   HFTT_REQUIRE(d, "notes_decode: null descriptor");
-  HFTT_REQUIRE(d->F >= 0, "notes_decode: F=%ld is negative", (long)d->F);
-  HFTT_REQUIRE(d->N >= 1 && d->N <= 128, "notes_decode: N=%d outside 1..128", d->N);
-  HFTT_REQUIRE((long)d->F * d->N < (1l << 31), "notes_decode: F=%ld frames of N=%d exceed 2^31 elements (the note count is an int32)", (long)d->F, d->N);
-  HFTT_REQUIRE(d->cap >= 0, "notes_decode: cap=%d is negative", d->cap);
-  HFTT_REQUIRE(d->mode_velocity == 0 || d->mode_velocity == 1, "notes_decode: mode_velocity=%d (0 = ignore_zero, 1 = org)", d->mode_velocity);
-  HFTT_REQUIRE(d->mode_offset >= 0 && d->mode_offset <= 2, "notes_decode: mode_offset=%d (0 = shorter, 1 = longer, 2 = offset)", d->mode_offset);
-  HFTT_REQUIRE(d->n_notes, "notes_decode: n_notes is null");
-  HFTT_REQUIRE(d->cap == 0 || (d->out_pitch && d->out_velocity && d->out_onset && d->out_offset),
-               "notes_decode: null output (out_pitch / out_velocity / out_onset / out_offset) at cap=%d", d->cap);
-  HFTT_REQUIRE(d->F == 0 || (d->onset && d->offset && d->mpe && d->velocity), "notes_decode: null roll (onset / offset / mpe / velocity)");
-  HFTT_REQUIRE(d->ws, "notes_decode: ws is null");
+  if (int rc = notes_check(d, "notes_decode")) return rc;
   HFTT_REQUIRE(d->ws_bytes >= hftt_notes_ws_bytes(d->F, d->N), "notes_decode: ws_bytes=%ld below hftt_notes_ws_bytes(F, N)=%ld", (long)d->ws_bytes,
                (long)hftt_notes_ws_bytes(d->F, d->N));
   const int nchunks = (int)notes_chunks(d->F);
   int* cnt = (int*)d->ws + (long)d->N * nchunks * ST_INTS;
   if (d->F == 0) {                                      // no frame, no note, no launch: the total alone is written
     if (hftt_device_guard("notes_decode") != 0) return 3;
-    hipError_t e = hipMemsetAsync(d->n_notes, 0, sizeof(int), (hipStream_t)stream);
-    if (e != hipSuccess) { hftt_set_error("notes_decode: clearing n_notes failed: %s", hipGetErrorString(e)); return 2; }
-    return 0;
+    return notes_clear("notes_decode", d->n_notes, sizeof(int), (hipStream_t)stream);
   }
   if (int rc = hftt_launch<notes_scan_kernel>("notes_decode", dim3((unsigned)d->N), dim3(CH), 0, (hipStream_t)stream, *d, nchunks)) return rc;
   if (int rc = hftt_launch<notes_offsets_kernel>("notes_decode", dim3(1), dim3(CH), 0, (hipStream_t)stream, cnt, d->N * nchunks, (int*)d->n_notes)) return rc;
   return hftt_launch<notes_emit_kernel>("notes_decode", dim3((unsigned)nchunks, (unsigned)d->N), dim3(CH), 0, (hipStream_t)stream, *d, nchunks,
                                         (float)(d->hop_sec * 0.5));
+}
+
+inline long seg_table_ints(long n_seg) { return (n_seg + 1 + 15) / 16 * 16; }
+
+// every segment ends with at most one partial chunk: at most ceil(F / CH) + n_seg chunks whatever the borders are
+extern "C" int64_t hftt_notes_seg_ws_bytes(int64_t F, int32_t N, int32_t n_seg) {
+  if (F < 0 || N < 1 || N > 128 || n_seg < 0) return 0;
+  return 64 + 4 * seg_table_ints(n_seg) + 4 * (int64_t)(ST_INTS + 1) * N * (notes_chunks(F) + n_seg);
+}
+
+extern "C" int hftt_notes_decode_seg(const hftt_notes_seg_desc* s, void* stream) {
+  const char* what = "notes_decode_seg";
+  HFTT_REQUIRE(s, "notes_decode_seg: null descriptor");
+  const hftt_notes_desc* d = &s->notes;
+  if (int rc = notes_check(d, what)) return rc;
+  HFTT_REQUIRE(s->n_seg >= 0, "notes_decode_seg: n_seg=%d is negative", s->n_seg);
+  HFTT_REQUIRE(s->seg_notes, "notes_decode_seg: seg_notes is null");
+  HFTT_REQUIRE(s->n_seg == 0 || (s->seg_row0_host && s->seg_row0), "notes_decode_seg: null table (seg_row0_host / seg_row0) at n_seg=%d", s->n_seg);
+  HFTT_REQUIRE((long)s->n_seg * d->N < (1l << 31), "notes_decode_seg: n_seg=%d segments of N=%d exceed 2^31 workgroups", s->n_seg, d->N);
+  long chunks = 0;
+  if (s->n_seg == 0) {
+    HFTT_REQUIRE(d->F == 0, "notes_decode_seg: seg_row0_host: n_seg=0 covers no row, F=%ld", (long)d->F);
+  } else {
+    const int32_t* t = s->seg_row0_host;
+    HFTT_REQUIRE(t[0] == 0, "notes_decode_seg: seg_row0_host[0]=%d must be 0", t[0]);
+    for (int i = 0; i < s->n_seg; i++) {
+      HFTT_REQUIRE(t[i + 1] >= t[i], "notes_decode_seg: seg_row0_host[%d]=%d below seg_row0_host[%d]=%d (non-decreasing)", i + 1, t[i + 1], i, t[i]);
+      chunks += notes_chunks((long)t[i + 1] - t[i]);
+    }
+    HFTT_REQUIRE(t[s->n_seg] == d->F, "notes_decode_seg: seg_row0_host[n_seg=%d]=%d must be F=%ld", s->n_seg, t[s->n_seg], (long)d->F);
+  }
+  const int64_t need = hftt_notes_seg_ws_bytes(d->F, d->N, s->n_seg);
+  HFTT_REQUIRE(d->ws_bytes >= need, "notes_decode_seg: ws_bytes=%ld below hftt_notes_seg_ws_bytes(F, N, n_seg)=%ld", (long)d->ws_bytes, (long)need);
+  hipStream_t st = (hipStream_t)stream;
+  if (chunks == 0) {                                    // no frame, no note, no launch: the counts alone are written
+    if (hftt_device_guard(what) != 0) return 3;
+    if (int rc = notes_clear(what, d->n_notes, sizeof(int), st)) return rc;
+    return notes_clear(what, s->seg_notes, sizeof(int) * ((size_t)s->n_seg + 1), st);
+  }
+  seg_args a;
+  a.d = *d;
+  a.seg_row0 = (const int*)s->seg_row0;
+  a.seg_notes = (int*)s->seg_notes;
+  a.n_seg = s->n_seg;
+  a.tbl = (int)seg_table_ints(s->n_seg);
+  a.chunks = (int)chunks;
+  int* cnt = (int*)d->ws + a.tbl + (long)d->N * chunks * ST_INTS;
+  // a segment that the device table describes otherwise is skipped by the kernels: its counts must not be read uninitialised
+  if (hftt_device_guard(what) != 0) return 3;
+  if (int rc = notes_clear(what, cnt, sizeof(int) * (size_t)d->N * chunks, st)) return rc;
+  if (int rc = hftt_launch<notes_seg_table_kernel>(what, dim3(1), dim3(CH), 0, st, a)) return rc;
+  if (int rc = hftt_launch<notes_seg_scan_kernel>(what, dim3((unsigned)((long)s->n_seg * d->N)), dim3(CH), 0, st, a)) return rc;
+  if (int rc = hftt_launch<notes_offsets_kernel>(what, dim3(1), dim3(CH), 0, st, cnt, (int)(d->N * chunks), (int*)d->n_notes)) return rc;
+  if (int rc = hftt_launch<notes_seg_heads_kernel>(what, dim3((unsigned)((s->n_seg + 1 + CH - 1) / CH)), dim3(CH), 0, st, a)) return rc;
+  return hftt_launch<notes_seg_emit_kernel>(what, dim3((unsigned)chunks, (unsigned)d->N), dim3(CH), 0, st, a, (float)(d->hop_sec * 0.5));
+}
+
+extern "C" int hftt_clip_windows(const hftt_clip_windows_desc* d, void* stream) {
+  HFTT_REQUIRE(d, "clip_windows: null descriptor");
+  HFTT_REQUIRE(d->feature && d->file_row0 && d->win_file && d->win_start && d->out,
+               "clip_windows: null pointer (feature / file_row0 / win_file / win_start / out)");
+  HFTT_REQUIRE(d->B >= 1, "clip_windows: B=%d must be positive", d->B);
+  HFTT_REQUIRE(d->width >= 1, "clip_windows: width=%d must be positive", d->width);
+  HFTT_REQUIRE(d->n_bins >= 1, "clip_windows: n_bins=%d must be positive", d->n_bins);
+  HFTT_REQUIRE(d->n_files >= 0, "clip_windows: n_files=%d is negative", d->n_files);
+  HFTT_REQUIRE(d->R >= 0, "clip_windows: R=%ld is negative", (long)d->R);
+  HFTT_REQUIRE((long)d->B * d->n_bins < (1l << 31) && (long)d->B * d->n_bins * d->width < (1l << 31), "clip_windows: B=%d windows of n_bins=%d x width=%d exceed 2^31 elements", d->B, d->n_bins, d->width);
+  const int tiles_t = (d->width + TILE - 1) / TILE, tiles_k = (d->n_bins + TILE - 1) / TILE;
+  const long blocks = (long)d->B * tiles_t * tiles_k;  // <= B * width * n_bins < 2^31
+  return hftt_launch<clip_windows_kernel>("clip_windows", dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *d, tiles_t, tiles_k);
 }

@@ -173,6 +173,18 @@ class NotesDesc(C.Structure):
                 ('ws', C.c_void_p), ('ws_bytes', C.c_int64)]
 
 
+class ClipWindowsDesc(C.Structure):
+    _fields_ = [('feature', C.c_void_p), ('file_row0', C.c_void_p), ('win_file', C.c_void_p), ('win_start', C.c_void_p),
+                ('B', C.c_int32), ('width', C.c_int32), ('n_bins', C.c_int32), ('n_files', C.c_int32),
+                ('R', C.c_int64), ('fill', C.c_float), ('pad', C.c_int32),
+                ('out', C.c_void_p)]
+
+
+class NotesSegDesc(C.Structure):
+    _fields_ = [('notes', NotesDesc), ('n_seg', C.c_int32), ('pad', C.c_int32),
+                ('seg_row0_host', C.POINTER(C.c_int32)), ('seg_row0', C.c_void_p), ('seg_notes', C.c_void_p)]
+
+
 LABELS_CHUNK = 256                          # HFTT_LABELS_CHUNK
 LABELS_TRAIN, LABELS_STORE = 0, 1           # HFTT_LABELS_TRAIN / HFTT_LABELS_STORE
 
@@ -241,6 +253,9 @@ SIGNATURES = {
     'hftt_stitch': (C.c_int, [C.POINTER(StitchDesc), C.c_void_p]),
     'hftt_notes_ws_bytes': (C.c_int64, [C.c_int64, C.c_int32]),
     'hftt_notes_decode': (C.c_int, [C.POINTER(NotesDesc), C.c_void_p]),
+    'hftt_clip_windows': (C.c_int, [C.POINTER(ClipWindowsDesc), C.c_void_p]),
+    'hftt_notes_seg_ws_bytes': (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    'hftt_notes_decode_seg': (C.c_int, [C.POINTER(NotesSegDesc), C.c_void_p]),
     'hftt_labels_render': (C.c_int, [C.POINTER(LabelsDesc), C.c_void_p]),
     'hftt_grad_norm_ws_bytes': (C.c_int64, [C.c_int64]),
     'hftt_grad_norm': (C.c_int, [c_f32p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),

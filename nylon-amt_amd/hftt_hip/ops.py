@@ -10,7 +10,7 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (AttnDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry,
+from ._capi import (AttnDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry,
                     LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, STITCH_MAX_CLIPS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
                     ATTN_Q_F16PAIR, ATTN_KV_F16PAIR, check, lib)
@@ -630,31 +630,41 @@ def stitch(onset, offset, mpe, velocity, rolls, dst, src0=0, length=None):
     return rolls
 
 
-def _notes_packed(onset, offset, mpe, velocity, thred_onset, thred_offset, thred_mpe, hop_sec, note_min, mode_velocity, mode_offset, cap):
-    """hftt_notes_decode into ONE device buffer (int8): [n_notes int32, pad to 8 | onset double cap | offset double cap | pitch int32 cap |
-    velocity int32 cap], so that the caller fetches the compact list with a single copy."""
+def _notes_fill(d, onset, offset, mpe, velocity, thred_onset, thred_offset, thred_mpe, hop_sec, note_min, mode_velocity, mode_offset, cap, what):
+    """the fields of a NotesDesc but the outputs and the workspace; returns the bytes of the packed output buffer (int8): [n_notes int32, pad
+    to 8 | onset double cap | offset double cap | pitch int32 cap | velocity int32 cap], so that the caller fetches the compact list with a
+    single copy (_notes_outputs points the descriptor into it)"""
     _need_cuda(onset, offset, mpe, velocity)
     if mode_velocity not in MODE_VELOCITY or mode_offset not in MODE_OFFSET:
-        raise HfttError('notes_decode: mode_velocity %r / mode_offset %r unknown' % (mode_velocity, mode_offset))
+        raise HfttError('%s: mode_velocity %r / mode_offset %r unknown' % (what, mode_velocity, mode_offset))
     F, N = onset.shape
     for t, dt in ((onset, torch.float32), (offset, torch.float32), (mpe, torch.float32), (velocity, torch.int8)):
         if t.dtype != dt or tuple(t.shape) != (F, N) or not t.is_contiguous():
-            raise HfttError('notes_decode: the rolls must be contiguous [F, N] tensors, three fp32 and one int8')
-    L = lib()
-    dev = onset.device
-    ws_bytes = L.hftt_notes_ws_bytes(F, N)
-    ws = torch.empty(ws_bytes, dtype=torch.int8, device=dev)
-    buf = torch.empty(8 + 24 * cap, dtype=torch.int8, device=dev)
-    base = buf.data_ptr()
-    d = NotesDesc()
+            raise HfttError('%s: the rolls must be contiguous [F, N] tensors, three fp32 and one int8' % what)
     d.F, d.N, d.note_min = F, N, int(note_min)
     d.onset, d.offset, d.mpe, d.velocity = onset.data_ptr(), offset.data_ptr(), mpe.data_ptr(), velocity.data_ptr()
     # the host compares a float32 roll with a Python scalar: the scalar is rounded to float32 (NumPy 2 promotion)
     d.thred_onset, d.thred_offset, d.thred_mpe = float(np.float32(thred_onset)), float(np.float32(thred_offset)), float(np.float32(thred_mpe))
     d.mode_velocity, d.mode_offset, d.cap = MODE_VELOCITY[mode_velocity], MODE_OFFSET[mode_offset], cap
     d.hop_sec = float(hop_sec)
+    return 8 + 24 * cap
+
+
+def _notes_outputs(d, base, cap):
     d.n_notes = base
     d.out_onset, d.out_offset, d.out_pitch, d.out_velocity = base + 8, base + 8 + 8 * cap, base + 8 + 16 * cap, base + 8 + 20 * cap
+
+
+def _notes_packed(onset, offset, mpe, velocity, thred_onset, thred_offset, thred_mpe, hop_sec, note_min, mode_velocity, mode_offset, cap):
+    """hftt_notes_decode into ONE device buffer (_notes_fill)"""
+    d = NotesDesc()
+    nbytes = _notes_fill(d, onset, offset, mpe, velocity, thred_onset, thred_offset, thred_mpe, hop_sec, note_min, mode_velocity, mode_offset, cap, 'notes_decode')
+    L = lib()
+    dev = onset.device
+    ws_bytes = L.hftt_notes_ws_bytes(d.F, d.N)
+    ws = torch.empty(ws_bytes, dtype=torch.int8, device=dev)
+    buf = torch.empty(nbytes, dtype=torch.int8, device=dev)
+    _notes_outputs(d, buf.data_ptr(), cap)
     d.ws, d.ws_bytes = ws.data_ptr(), ws_bytes
     check(L.hftt_notes_decode(C.byref(d), _stream(dev)), 'notes_decode')
     return buf
@@ -699,6 +709,81 @@ def notes_decode(onset, offset, mpe, velocity, hop_sec, note_min=21, thred_onset
             buf = buf.cpu()
         total, t_on, t_off, pitch, vel = _notes_unpack(buf, cap)
     return pitch, vel, t_on, t_off
+
+
+def _notes_seg_packed(rolls, seg_host, seg_dev, args, cap):
+    """hftt_notes_decode_seg into ONE device buffer: the list of _notes_fill, then seg_notes int32 [n_seg + 1] behind it"""
+    s = NotesSegDesc()
+    nbytes = _notes_fill(s.notes, *rolls, *args, cap, 'notes_decode_seg')
+    n_seg = len(seg_host) - 1
+    L = lib()
+    dev = rolls[0].device
+    ws_bytes = L.hftt_notes_seg_ws_bytes(s.notes.F, s.notes.N, n_seg)
+    ws = torch.empty(ws_bytes, dtype=torch.int8, device=dev)
+    buf = torch.empty(nbytes + 4 * (n_seg + 1), dtype=torch.int8, device=dev)
+    _notes_outputs(s.notes, buf.data_ptr(), cap)
+    s.notes.ws, s.notes.ws_bytes = ws.data_ptr(), ws_bytes
+    s.n_seg = n_seg
+    table = (C.c_int32 * (n_seg + 1))(*seg_host)
+    s.seg_row0_host = table
+    s.seg_row0 = seg_dev.data_ptr()
+    s.seg_notes = buf.data_ptr() + nbytes
+    check(L.hftt_notes_decode_seg(C.byref(s), _stream(dev)), 'notes_decode_seg')
+    return buf
+
+
+def notes_decode_seg(onset, offset, mpe, velocity, seg_rows, hop_sec, note_min=21, thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5,
+                     mode_velocity='ignore_zero', mode_offset='shorter', capacity=None, host=False):
+    """Rolls that hold n_seg files back to back (device tensors as for notes_decode) -> (pitch, velocity, onset, offset, seg_notes): every
+    segment's notes are those of notes_decode on its rows alone, segment-major; segment s is records seg_notes[s] .. seg_notes[s + 1]
+    (hftt_notes_decode_seg).  seg_rows: the n_seg + 1 row borders on the host (ints; [0] == 0, non-decreasing, [-1] == F), uploaded here.
+    The capacity rule is notes_decode's: notes_default_capacity(F, N), one rerun with the exact count on overflow, HfttError when the caller
+    fixed capacity=.  All five arrays lie in one packed buffer: host=True is ONE device->host copy."""
+    _need_cuda(onset, offset, mpe, velocity)
+    F, N = onset.shape
+    seg_host = [int(x) for x in seg_rows]
+    if len(seg_host) < 1:
+        raise HfttError('notes_decode_seg: seg_rows needs n_seg + 1 row borders')
+    n_seg = len(seg_host) - 1
+    seg_dev = torch.tensor(seg_host, dtype=torch.int32).to(onset.device)
+    cap = notes_default_capacity(F, N) if capacity is None else int(capacity)
+    args = (thred_onset, thred_offset, thred_mpe, hop_sec, note_min, mode_velocity, mode_offset)
+    rolls = (onset, offset, mpe, velocity)
+
+    def run(cap):
+        buf = _notes_seg_packed(rolls, seg_host, seg_dev, args, cap)
+        if host:
+            buf = buf.cpu()
+        return _notes_unpack(buf, cap) + (buf[8 + 24 * cap:8 + 24 * cap + 4 * (n_seg + 1)].view(torch.int32),)
+    total, t_on, t_off, pitch, vel, seg_notes = run(cap)
+    if total > cap:
+        if capacity is not None:
+            raise HfttError('notes_decode_seg: %d notes exist, capacity=%d' % (total, cap))
+        total, t_on, t_off, pitch, vel, seg_notes = run(total)
+    return pitch, vel, t_on, t_off, seg_notes
+
+
+def clip_windows(feature, file_row0, win_file, win_start, width, fill):
+    """B clip windows of a file list -> [B, n_bins, width] fp32 in ONE launch (hftt_clip_windows): feature [R, n_bins] fp32 holds the files'
+    rows concatenated (device tensor), file f = rows file_row0[f] .. file_row0[f + 1]; window b shows frames win_start[b] .. + width of file
+    win_file[b], counted from the file's frame 0, transposed (model/amt.py a_input[i:i+width].T); frames outside the file are `fill`, a
+    neighbouring file's frames never show.  file_row0 / win_file / win_start: int32 device tensors (or anything torch.as_tensor takes)."""
+    _need_cuda(feature)
+    dev = feature.device
+    if feature.dim() != 2 or feature.dtype != torch.float32 or not feature.is_contiguous():
+        raise HfttError('clip_windows: feature must be a contiguous fp32 [R, n_bins] tensor')
+    file_row0, win_file, win_start = (torch.as_tensor(t, device=dev).to(torch.int32).contiguous() for t in (file_row0, win_file, win_start))
+    if file_row0.dim() != 1 or file_row0.numel() < 1 or win_file.dim() != 1 or win_start.shape != win_file.shape:
+        raise HfttError('clip_windows: file_row0 must be [n_files + 1], win_file and win_start [B]')
+    R, n_bins = feature.shape
+    B, width = win_file.numel(), int(width)
+    keep = feature if R else torch.empty(1, dtype=torch.float32, device=dev)          # no row: nothing is read, the pointer is only non-null
+    out = torch.empty((B, n_bins, max(width, 0)), dtype=torch.float32, device=dev)    # an empty request is the library's to refuse
+    d = ClipWindowsDesc()
+    d.feature, d.file_row0, d.win_file, d.win_start, d.out = (t.data_ptr() for t in (keep, file_row0, win_file, win_start, out))
+    d.B, d.width, d.n_bins, d.n_files, d.R, d.fill = B, width, n_bins, file_row0.numel() - 1, R, float(fill)
+    check(lib().hftt_clip_windows(C.byref(d), _stream(dev)), 'clip_windows')
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

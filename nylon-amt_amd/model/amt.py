@@ -2,7 +2,8 @@
 
 Same surface as hftt_code/model/amt.py: ``AMT(config, model_path, batch_size=1, verbose_flag=False)``,
 ``wav2feature`` (:34), ``transcript`` (:66), ``transcript_stride`` (:121), ``mpe2note`` (:179), ``note2midi`` (:347).
-One addition: ``transcript_notes`` = ``mpe2note(*transcript(...))`` with the rolls and the decoding kept on the device (csrc/notes.hip).
+Two additions: ``transcript_notes`` = ``mpe2note(*transcript(...))`` with the rolls and the decoding kept on the device (csrc/notes.hip).
+and ``transcript_notes_files``, the same for a list of files in one pass (the file loop of evaluation/m_inference.py:77-165).
 Differences in mechanism, not in results:
   * wav2feature runs the log-mel kernel of libhftt_hip.so (STFT + sparse mel + log on the GPU) instead of torchaudio;
   * transcript/transcript_stride gather ALL clip windows of a file and run them through the model in batches of
@@ -263,6 +264,100 @@ class AMT():
         pitch, velocity, onset, offset = pitch.numpy(), velocity.numpy(), onset.numpy(), offset.numpy()
         order = np.lexsort((pitch, onset))                                      # stable: by onset, then pitch, then the order of a_note (amt.py:343)
         return [{'pitch': int(pitch[i]), 'onset': float(onset[i]), 'offset': float(offset[i]), 'velocity': int(velocity[i])} for i in order]
+
+    def transcript_notes_files(self, a_features, n_offset=None, output='B', thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5,
+                               mode_velocity='ignore_zero', mode_offset='shorter'):
+        """``transcript_notes`` for a list of files in one pass (the file loop of evaluation/m_inference.py:77-165): one sorted note list per
+        file; with output='AB' one ``(notes_A, notes_B)`` pair per file from a SINGLE model pass (both head sets, what m_inference.py writes).
+        a_features: a sequence of [n_i, n_bins] arrays, numpy arrays and device tensors (``wave2feature(..., on_device=True)``) mixed freely.
+        The features are concatenated on the device once and the clip table (file, start) of all files is built on the host with the
+        arithmetic of transcript / transcript_stride and uploaded once.  Every ``batch_size`` clips -- ACROSS file borders, so only the last
+        batch of the list is short -- are cut by hftt_clip_windows (padding with min_value per window: a window never shows a neighbouring
+        file's frames), run through one model call and stitched into rolls that hold all files back to back.  One hftt_notes_decode_seg
+        decodes every file on its own rows alone, one device->host copy fetches all lists, and the stable (onset, pitch) sort (amt.py:343) per
+        file runs on the host.
+        The result is that of ``[transcript_notes(f, ...) for f in a_features]``, bit for bit: the decode is exact per file, and the eval
+        forward gives a clip the same outputs whatever else its batch holds (tests/test_notes_files_gpu.py holds both, and the packed call to
+        the host path at equal batches).
+        Memory: the whole list's features and rolls are resident at once, 1,024 + 13 * num_note bytes per frame at 256 bins (twice the 13 *
+        num_note with 'AB'); a caller with more than the device holds splits the list.
+        One process, one GPU (world > 1 raises HfttError); there is no CPU fallback.  An empty list gives []; a file of zero frames []."""
+        from hftt_hip import ops
+        if self.world > 1:
+            raise HfttError('transcript_notes_files runs on one GPU (world = %d): sharded inference uses transcript / transcript_stride + mpe2note' % self.world)
+        if output not in ('A', 'B', 'AB'):
+            raise HfttError("output must be 'A' (heads 0-3), 'B' (heads 5-8) or 'AB' (both, one model pass)")
+        if not str(self.device).startswith('cuda'):
+            raise HfttError('transcript_notes_files decodes on the device: a ROCm device is required (there is no CPU fallback)')
+        cin, cf, cm = self.config['input'], self.config['feature'], self.config['midi']
+        T, N = cin['num_frame'], cm['num_note']
+        n_files = len(a_features)
+        if n_files == 0:
+            return []
+        # the features on the device, file after file: the host arrays travel as ONE block
+        host_idx = [i for i, a in enumerate(a_features) if not torch.is_tensor(a)]
+        host = [np.array(a_features[i], dtype=np.float32).reshape(-1, cf['n_bins']) for i in host_idx]
+        pieces = [None] * n_files
+        if host:
+            block = torch.from_numpy(np.concatenate(host, axis=0)).to(self.device)
+            r = 0
+            for i, a in zip(host_idx, host):
+                pieces[i] = block[r:r + a.shape[0]]
+                r += a.shape[0]
+        for i, a in enumerate(a_features):
+            if torch.is_tensor(a):
+                ops._need_cuda(a)
+                pieces[i] = a.to(device=self.device, dtype=torch.float32).reshape(-1, cf['n_bins'])
+        feature = block if len(host) == n_files else torch.cat(pieces, dim=0)
+        lens = [int(p.shape[0]) for p in pieces]
+        # the clip table of all files, file-major with ascending start (transcript amt.py:66-118, transcript_stride :121-176)
+        if n_offset is None:
+            step, src0, front = T, 0, cin['margin_b']
+        else:
+            step, src0, front = int(T / 2), int(n_offset), cin['margin_b'] + int(n_offset)
+        file_row0, roll_row0, win_file, win_start, dst = [0], [0], [], [], []
+        for f, n in enumerate(lens):
+            if n_offset is None:
+                len_s = int(np.ceil(n / T) * T) - n
+            else:
+                tmp_len = n + cin['margin_b'] + cin['margin_f'] + step
+                len_s = int(np.ceil(tmp_len / step) * step) - tmp_len
+            for i in range(0, n, step):
+                win_file.append(f)
+                win_start.append(i - front)                                     # a_input row i is the file's frame i - front
+                dst.append(roll_row0[f] + i)
+            file_row0.append(file_row0[f] + n)
+            roll_row0.append(roll_row0[f] + (n + len_s if n else 0))
+        F = roll_row0[n_files]
+        sets = (0, 5) if output == 'AB' else ((0,) if output == 'A' else (5,))
+        width = cin['margin_b'] + T + cin['margin_f']
+        rolls = tuple(torch.zeros(len(sets) * F, N, dtype=torch.int8 if k == 3 else torch.float32, device=self.device) for k in range(4))
+        if win_file:
+            n_win = len(win_file)
+            table = torch.tensor(file_row0 + win_file + win_start, dtype=torch.int32).to(self.device)   # file rows + the clip table: one upload
+            rows, wf, ws = table[:n_files + 1], table[n_files + 1:n_files + 1 + n_win], table[n_files + 1 + n_win:]
+            self.model.eval()
+            for b0 in range(0, len(dst), self.batch_size):
+                b1 = min(b0 + self.batch_size, len(dst))
+                spec = ops.clip_windows(feature, rows, wf[b0:b1], ws[b0:b1], width, cin['min_value'])
+                with torch.no_grad():
+                    o = self.model(spec)
+                for q, h0 in enumerate(sets):
+                    ops.stitch(o[h0], o[h0 + 1], o[h0 + 2], o[h0 + 3], rolls, [q * F + x for x in dst[b0:b1]], src0=src0, length=step)
+        seg_rows = [q * F + x for q in range(len(sets)) for x in roll_row0[:n_files]] + [len(sets) * F]
+        hop_sec = float(cf['hop_sample'] / cf['sr'])
+        pitch, velocity, onset, offset, seg_notes = (x.numpy() for x in ops.notes_decode_seg(
+            *rolls, seg_rows, hop_sec, note_min=cm['note_min'], thred_onset=thred_onset, thred_offset=thred_offset, thred_mpe=thred_mpe,
+            mode_velocity=mode_velocity, mode_offset=mode_offset, host=True))
+
+        def notes_of(s):
+            a, b = int(seg_notes[s]), int(seg_notes[s + 1])
+            p, v, t0, t1 = pitch[a:b], velocity[a:b], onset[a:b], offset[a:b]
+            order = np.lexsort((p, t0))                                         # stable: by onset, then pitch, then the order of a_note (amt.py:343)
+            return [{'pitch': int(p[i]), 'onset': float(t0[i]), 'offset': float(t1[i]), 'velocity': int(v[i])} for i in order]
+        if output == 'AB':
+            return [(notes_of(f), notes_of(n_files + f)) for f in range(n_files)]
+        return [notes_of(f) for f in range(n_files)]
 
     # ------------------------------------------------------------------ posteriorgram -> notes (amt.py:179-344)
     def mpe2note(self, a_onset=None, a_offset=None, a_mpe=None, a_velocity=None, thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5,
