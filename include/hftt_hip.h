@@ -693,6 +693,47 @@ int hftt_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t
                            double lr, double beta1, double beta2, double eps, double grad_scale,
                            double weight_decay, const hftt_guard_ctl* ctl, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Parameter groups for the guarded step (csrc/guard.hip): per-group learning rate and decoupled decay, and frozen groups, in ONE launch over
+ * the flat buffer (fine-tuning: a frozen encoder, no decay on biases and LayerNorm parameters).  ADDED at ABI 8 like the section above;
+ * HFTT_ABI_VERSION stays 8 and hftt_adam_step / hftt_grad_norm / hftt_adam_step_guarded are untouched.
+ *
+ * The group map: one uint8 per QUAD (4 consecutive fp32 elements) of the flat buffer, in device memory: the index of the quad's group,
+ * n / 4 entries.  Parameter offsets in the flat buffer are multiples of 8 elements, so a quad never straddles two parameters; a quad in the
+ * alignment gap behind a parameter takes that parameter's group (its p, g, m, v are zero and stay zero).  Values >= n_groups are the
+ * caller's error.
+ *
+ * hftt_adam_step_groups: hftt_adam_step_guarded's update per quad with the constants of the quad's group,
+ *     lr_c[k] = (float)(lr[k] / (1 - b1^t)),   d[k] = (float)(1 - lr[k] * weight_decay[k])        (formed in double, rounded once)
+ * through the record `ctl` (apply == 0: nothing is stored; gr = g * ((float)grad_scale * coef)).  ctl == NULL: unguarded -- always applied,
+ * clip factor 1.  A quad whose group has frozen[k] != 0 is neither loaded nor stored: p, m, v keep their bits and the step's traffic drops
+ * with the frozen share.  With one group and nothing frozen the result is bit-identical to hftt_adam_step_guarded (and hence, with clip
+ * factor 1 and no decay, to hftt_adam_step).  Same grid rule as the guarded kernel.
+ * Refused in front of the launch: what hftt_adam_step_guarded refuses, per group (weight_decay NaN or negative, lr * weight_decay >= 1);
+ * n % 4 != 0; n_groups outside 1..HFTT_ADAM_MAX_GROUPS; a null map; ctl given but not 16-byte aligned.
+ *
+ * hftt_grad_norm_groups: hftt_grad_norm with the quads of the groups in frozen_mask (bit k: group k) left out of the sum -- the norm of
+ * torch.nn.utils.clip_grad_norm_ over the parameters that HAVE a gradient.  Same two launches, same fixed orders, same record; with
+ * frozen_mask == 0 the record equals hftt_grad_norm's bit for bit.  Consequence: an Inf or NaN in a frozen range does not skip the step.
+ * Refused in front of the launch: what hftt_grad_norm refuses; n % 4 != 0; a null map; a frozen_mask bit beyond HFTT_ADAM_MAX_GROUPS.
+ * --------------------------------------------------------------------------------------------- */
+#define HFTT_ADAM_MAX_GROUPS 8
+typedef struct {
+  float* p; const float* g; float* m; float* v;      /* flat parameters, gradients, first and second moments: n fp32 each, 16-byte aligned */
+  int64_t n;                                          /* elements, a multiple of 4 */
+  const uint8_t* quad_group;                          /* [n / 4] device bytes: group index of every quad */
+  int32_t n_groups;                                   /* 1..HFTT_ADAM_MAX_GROUPS */
+  int32_t step;                                       /* number of calls so far, >= 1 (bias corrections) */
+  double beta1, beta2, eps, grad_scale;               /* shared by all groups */
+  double lr[HFTT_ADAM_MAX_GROUPS];
+  double weight_decay[HFTT_ADAM_MAX_GROUPS];          /* decoupled */
+  int32_t frozen[HFTT_ADAM_MAX_GROUPS];               /* != 0: the group's quads are neither loaded nor stored */
+  const hftt_guard_ctl* ctl;                          /* the guard record; NULL: unguarded */
+} hftt_adam_groups_desc;
+int hftt_adam_step_groups(const hftt_adam_groups_desc* d, void* stream);
+int hftt_grad_norm_groups(const float* g, int64_t n, const uint8_t* quad_group, uint32_t frozen_mask, double grad_scale, double max_norm,
+                          void* ws, hftt_guard_ctl* ctl, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,8 @@
 // finite, scales the gradient by the clip factor on the fly and applies decoupled weight decay.  No float atomics, no cross-workgroup
 // tickets: every sum has one fixed order, so the record is bitwise reproducible.  Entry points and the torch definitions they restate:
 // include/hftt_hip.h.  The unguarded step (hftt_adam_step / adam_kernel, csrc/elementwise.hip) is untouched and stays the default path.
+// The grouped forms (hftt_grad_norm_groups, hftt_adam_step_groups) read a per-quad group map: per-group learning rate and decay, and frozen
+// groups whose quads are neither loaded nor stored (fine-tuning).
 #include "hftt_common.h"
 #include "hftt_launch.h"
 #include "../../include/hftt_hip.h"
@@ -120,6 +122,59 @@ __global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restri
   }
 }
 
+// ------------------------------------------------------------------ parameter groups (fine-tuning)
+// One uint8 per quad of the flat buffer names the quad's group; parameter offsets are multiples of 8 elements, so a quad never straddles two
+// parameters.  The per-group constants arrive by value and are staged in LDS with constant indices, so that the dynamic index gi never
+// reaches a register array (ScratchSize 0).  A quad of a frozen group is neither loaded nor stored.
+struct adam_group_consts {
+  float lr_c[HFTT_ADAM_MAX_GROUPS];       // lr / (1 - beta1^t) per group
+  float d[HFTT_ADAM_MAX_GROUPS];          // 1 - lr * weight_decay per group
+  unsigned frozen_mask;                   // bit k: group k keeps its bits
+};
+
+__global__ __launch_bounds__(GN_THREADS) void grad_sqsum_groups_kernel(const float* __restrict__ g, long n4, const uint8_t* __restrict__ quad_group,
+                                                                       unsigned frozen_mask, double* __restrict__ ws) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  double acc = 0.0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    if ((frozen_mask >> (quad_group[i] & (HFTT_ADAM_MAX_GROUPS - 1))) & 1u) continue;
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    const double x = gg.x, y = gg.y, z = gg.z, w = gg.w;
+    acc += x * x; acc += y * y; acc += z * z; acc += w * w;
+  }
+  const double s = block_sum64(acc);
+  if (threadIdx.x == 0) ws[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(GN_THREADS) void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                 float* __restrict__ v, long n4, const uint8_t* __restrict__ quad_group,
+                                                                 adam_group_consts c, float beta1, float beta2, float omb1, float omb2, float eps,
+                                                                 float inv_sqrt_bc2, float grad_scale, const hftt_guard_ctl* __restrict__ ctl) {
+  if (ctl != nullptr && ctl->apply == 0u) return;          // (uniform, as in adam_guarded_kernel)
+  __shared__ float s_lr[HFTT_ADAM_MAX_GROUPS], s_d[HFTT_ADAM_MAX_GROUPS];
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < HFTT_ADAM_MAX_GROUPS; k++) { s_lr[k] = c.lr_c[k]; s_d[k] = c.d[k]; }
+  }
+  __syncthreads();
+  const float s = grad_scale * (ctl != nullptr ? ctl->coef : 1.f);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const unsigned gi = quad_group[i] & (HFTT_ADAM_MAX_GROUPS - 1);      // (values >= n_groups are the caller's error; the LDS index stays in range)
+    if ((c.frozen_mask >> gi) & 1u) continue;
+    const float lr_c = s_lr[gi], d = s_d[gi];
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    float4 mm = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    float* pe = &pp.x; const float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
+#pragma unroll
+    for (int e = 0; e < 4; e++) adam_guarded_update<true>(pe[e], ge[e], me[e], ve[e], s, d, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(m)[i] = mm;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+}
+
 // workgroups over n elements read four at a time: adam_kernel's grid (ceil((n / 4 + 1) / 256), at most GN_MAX_WGS)
 inline int guard_grid(long n) {
   long b = (n / 4 + 1 + GN_THREADS - 1) / GN_THREADS;
@@ -161,4 +216,48 @@ extern "C" int hftt_adam_step_guarded(float* p, const float* g, float* m, float*
   return hftt_launch<adam_guarded_kernel>("adam_step_guarded", dim3(guard_grid((long)n)), dim3(GN_THREADS), 0, (hipStream_t)stream, p, g, m, v, (long)n,
                                                                 lr_c, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, inv_sqrt_bc2,
                                                                 (float)grad_scale, d, ctl);
+}
+
+extern "C" int hftt_grad_norm_groups(const float* g, int64_t n, const uint8_t* quad_group, uint32_t frozen_mask, double grad_scale, double max_norm,
+                                     void* ws, hftt_guard_ctl* ctl, void* stream) {
+  HFTT_REQUIRE(g && ws && ctl, "grad_norm_groups: null operand");
+  HFTT_REQUIRE(n > 0, "grad_norm_groups: n=%ld must be positive", (long)n);
+  HFTT_REQUIRE(n % 4 == 0, "grad_norm_groups: n=%ld must be a multiple of 4 (one map entry per quad)", (long)n);
+  HFTT_REQUIRE(quad_group != nullptr, "grad_norm_groups: the group map is null");
+  HFTT_REQUIRE((frozen_mask >> HFTT_ADAM_MAX_GROUPS) == 0, "grad_norm_groups: frozen_mask names a group beyond %d", HFTT_ADAM_MAX_GROUPS);
+  HFTT_REQUIRE((((uintptr_t)g | (uintptr_t)ws | (uintptr_t)ctl) & 15) == 0, "grad_norm_groups: g, ws and ctl must be 16-byte aligned");
+  HFTT_REQUIRE(isfinite(grad_scale), "grad_norm_groups: grad_scale must be finite");
+  HFTT_REQUIRE(max_norm > 0.0, "grad_norm_groups: max_norm must be positive (+inf: no clipping)");
+  const int wgs = guard_grid((long)n);
+  if (int rc = hftt_launch<grad_sqsum_groups_kernel>("grad_norm_groups(1)", dim3(wgs), dim3(GN_THREADS), 0, (hipStream_t)stream, g, (long)(n / 4), quad_group,
+                                                     (unsigned)frozen_mask, (double*)ws)) return rc;
+  return hftt_launch<grad_norm_finalize_kernel>("grad_norm_groups(2)", dim3(1), dim3(GN_THREADS), 0, (hipStream_t)stream, (const double*)ws, wgs, fabs(grad_scale), max_norm, ctl);
+}
+
+extern "C" int hftt_adam_step_groups(const hftt_adam_groups_desc* dsc, void* stream) {
+  HFTT_REQUIRE(dsc != nullptr, "adam_step_groups: null descriptor");
+  const hftt_adam_groups_desc& a = *dsc;
+  HFTT_REQUIRE(a.p && a.g && a.m && a.v && a.n > 0 && a.step >= 1, "adam_step_groups: bad arguments");
+  HFTT_REQUIRE((((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0, "adam_step_groups: buffers must be 16-byte aligned");
+  HFTT_REQUIRE(a.n % 4 == 0, "adam_step_groups: n=%ld must be a multiple of 4 (one map entry per quad)", (long)a.n);
+  HFTT_REQUIRE(a.n_groups >= 1 && a.n_groups <= HFTT_ADAM_MAX_GROUPS, "adam_step_groups: n_groups=%d must be in 1..%d", (int)a.n_groups, HFTT_ADAM_MAX_GROUPS);
+  HFTT_REQUIRE(a.quad_group != nullptr, "adam_step_groups: the group map is null");
+  HFTT_REQUIRE(((uintptr_t)a.ctl & 15) == 0, "adam_step_groups: ctl must be 16-byte aligned (NULL: unguarded)");
+  // as hftt_adam_step_guarded: everything that is a function of the hyper-parameters alone is formed in double and rounded once
+  const double bc1 = 1.0 - pow(a.beta1, (double)a.step);
+  const double bc2 = 1.0 - pow(a.beta2, (double)a.step);
+  adam_group_consts c;
+  c.frozen_mask = 0u;
+  for (int k = 0; k < HFTT_ADAM_MAX_GROUPS; k++) {
+    c.lr_c[k] = 0.f; c.d[k] = 1.f;
+    if (k >= a.n_groups) continue;
+    HFTT_REQUIRE(a.weight_decay[k] >= 0.0, "adam_step_groups: group %d: weight_decay must be >= 0", k);                  // (false for NaN too)
+    HFTT_REQUIRE(a.lr[k] * a.weight_decay[k] < 1.0, "adam_step_groups: group %d: lr * weight_decay must be below 1", k);
+    c.lr_c[k] = (float)(a.lr[k] / bc1);
+    c.d[k] = (float)(1.0 - a.lr[k] * a.weight_decay[k]);
+    if (a.frozen[k]) c.frozen_mask |= 1u << k;
+  }
+  return hftt_launch<adam_groups_kernel>("adam_step_groups", dim3(guard_grid((long)a.n)), dim3(GN_THREADS), 0, (hipStream_t)stream, a.p, a.g, a.m, a.v,
+                                         (long)(a.n / 4), a.quad_group, c, (float)a.beta1, (float)a.beta2, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2),
+                                         (float)a.eps, (float)(1.0 / sqrt(bc2)), (float)a.grad_scale, a.ctl);
 }

@@ -202,6 +202,17 @@ class LabelsDesc(C.Structure):
                 ('onset', C.c_void_p), ('offset', C.c_void_p), ('mpe', C.c_void_p), ('velocity', C.c_void_p)]
 
 
+ADAM_MAX_GROUPS = 8                         # HFTT_ADAM_MAX_GROUPS
+
+
+class AdamGroupsDesc(C.Structure):          # hftt_adam_groups_desc: the grouped Adam step (per-group lr / decay / frozen, one launch)
+    _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('n', C.c_int64), ('quad_group', C.c_void_p),
+                ('n_groups', C.c_int32), ('step', C.c_int32),
+                ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double), ('grad_scale', C.c_double),
+                ('lr', C.c_double * ADAM_MAX_GROUPS), ('weight_decay', C.c_double * ADAM_MAX_GROUPS), ('frozen', C.c_int32 * ADAM_MAX_GROUPS),
+                ('ctl', C.c_void_p)]
+
+
 class GuardCtl(C.Structure):                # hftt_guard_ctl: 32 bytes of device memory (the host only reads it back)
     _fields_ = [('norm', C.c_float), ('coef', C.c_float), ('apply', C.c_uint32), ('skipped', C.c_uint32), ('clipped', C.c_uint32),
                 ('pad', C.c_uint32 * 3)]
@@ -261,6 +272,8 @@ SIGNATURES = {
     'hftt_grad_norm': (C.c_int, [c_f32p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hftt_adam_step_guarded': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32,
                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    'hftt_adam_step_groups': (C.c_int, [C.POINTER(AdamGroupsDesc), C.c_void_p]),
+    'hftt_grad_norm_groups': (C.c_int, [c_f32p, C.c_int64, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -2,6 +2,8 @@
 
 This is the compatibility path (``loss.backward()`` of training/train.py:158 works unchanged with any torch
 optimizer).  The fast path used by ``training.train`` / bench.py drives the same engine plans without autograd.
+This path always runs the whole backward plan: a frozen stage (``FusedAdam`` groups, ``requires_grad_(False)``) saves the optimizer's traffic
+here, not the backward's -- the pruned backward belongs to ``TrainStep``.
 """
 import torch
 

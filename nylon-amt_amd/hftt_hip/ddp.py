@@ -53,14 +53,21 @@ class FlatGradSync:
         self.slices = [(i, min(n, i + step)) for i in range(0, n, step)]
         self.scale = 1.0 / world
         self.launched = []                     # flat ranges already reduced (or in flight) for the current step
+        self.lo = 0                            # first flat element this step's backward produces (begin_step)
         # timing=True: an event behind every bucket's all-reduce (side stream) and one at the end of the backward (compute stream), so a
         # caller can check that the early buckets really finish under the rest of the backward (overlap_report; bench.py, the rehearsal test)
         self.timing = False
         self._bucket_events, self._bwd_end_event, self._last_report = [], None, None
 
-    def begin_step(self):
+    def begin_step(self, lo=0):
         """called before every backward: ranges reported by a backward that was never followed by __call__ (gradient accumulation,
-        an exception) must not be mistaken for this step's"""
+        an exception) must not be mistaken for this step's.  lo: the flat offset below which this step's backward writes nothing (a frozen
+        prefix, HfttEngine.backward(frozen_stages=...)): the ready ranges are expected to cover [lo, n) and only that is reduced -- [0, lo) keeps
+        each rank's own bits.  lo = 0: the whole buffer, as ever."""
+        n = self.engine.flat_grads.numel()
+        if not 0 <= lo < n:
+            raise RuntimeError('FlatGradSync.begin_step: lo=%d outside the flat gradient [0, %d)' % (lo, n))
+        self.lo = int(lo)
         self.launched = []
         self._bucket_events, self._bwd_end_event = [], None
 
@@ -98,7 +105,7 @@ class FlatGradSync:
                     self._bwd_end_event = torch.cuda.Event(enable_timing=True)
                     self._bwd_end_event.record(torch.cuda.current_stream(flat_grads.device))
                 torch.cuda.current_stream(flat_grads.device).wait_stream(self.stream)
-            pos = 0
+            pos = self.lo
             for lo, hi in done:
                 if lo != pos:
                     raise RuntimeError('FlatGradSync: gradient range [%d, %d) was never reported ready' % (pos, lo))
@@ -106,14 +113,15 @@ class FlatGradSync:
             if pos != flat_grads.numel():
                 raise RuntimeError('FlatGradSync: gradient range [%d, %d) was never reported ready' % (pos, flat_grads.numel()))
             return self.scale
+        slices = [(max(a, self.lo), b) for a, b in self.slices if b > self.lo]
         if not self.cuda:                      # gloo / CPU tensors (tests): same bucketing, no streams
-            for a, b in self.slices:
+            for a, b in slices:
                 dist.all_reduce(flat_grads[a:b], op=dist.ReduceOp.SUM)
             return self.scale
         cur = torch.cuda.current_stream(flat_grads.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            for a, b in self.slices:
+            for a, b in slices:
                 _all_reduce_sum(flat_grads[a:b])
         cur.wait_stream(self.stream)
         return self.scale

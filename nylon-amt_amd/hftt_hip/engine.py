@@ -365,12 +365,37 @@ class HfttEngine:
         ws['generation'] = self.generation
         return tuple(outs)
 
-    def backward(self, B, generation=None, on_ready=None):
+    def frozen_border(self, frozen_stages):
+        """flat offset below which backward(frozen_stages=...) writes nothing: 0, the frequency decoder's first parameter, the time decoder's"""
+        dd = 'decoder_spec2midi.'
+        return (0, self.poff[dd + 'pos_embedding_freq.weight'], self.poff[dd + 'pos_embedding_time.weight'])[frozen_stages]
+
+    def backward_plan(self, B, frozen_stages=0):
+        """(launch list, marks) of the backward with the first `frozen_stages` stages of the flat layout frozen.  0: the workspace's full plan
+        (the same object as ever).  2: its prefix up to the first mark (time decoder + heads B).  1: a second plan, built on first use by the
+        same builder code: the full plan up to the second mark without the launches that form the encoder-output gradient."""
+        ws = self.workspace(B)
+        if frozen_stages == 0:
+            return ws['bwd'], ws['bwd_marks']
+        if frozen_stages == 2:
+            marks = ws['bwd_marks'][:1]
+            return ws['bwd'][:marks[0][0]], marks
+        if frozen_stages != 1:
+            raise _capi.HfttError('frozen_stages=%r must be 0, 1 (encoder) or 2 (encoder + frequency decoder)' % (frozen_stages,))
+        if 'bwd_dec' not in ws:
+            with torch.cuda.device(self.device):
+                PlanBuilder(self, B, ws).build_decoder_backward()
+        return ws['bwd_dec'], ws['bwd_dec_marks']
+
+    def backward(self, B, generation=None, on_ready=None, frozen_stages=0):
         """Backward through the most recent forward of batch size B; the gradients of the 8 outputs must be in
         the 'd.*' workspace buffers.  Fills flat_grads (every parameter written exactly once).
         on_ready(lo, hi), if given, is called three times, each as soon as every launch that writes flat_grads[lo:hi] has
         been enqueued (time decoder, frequency decoder, encoder): the data-parallel all-reduce of that range can then
-        overlap the rest of the backward (hftt_hip/ddp.py)."""
+        overlap the rest of the backward (hftt_hip/ddp.py).
+        frozen_stages = 1 (encoder) / 2 (encoder + frequency decoder): the backward stops where nothing trainable remains (backward_plan).
+        flat_grads below frozen_border(frozen_stages) is not written -- it keeps what it held -- and on_ready is called for the ranges that were
+        produced only.  The forward plan is the same either way."""
         ws = self._ws.get(B)
         if ws is None or 'outs' not in ws:
             raise _capi.HfttError('backward called without a forward')
@@ -381,13 +406,14 @@ class HfttEngine:
         self._cur_ws = ws
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
+            plan, marks = self.backward_plan(B, frozen_stages)     # (in front of the patch: a plan built just now brings new descriptors)
             self._patch(ws, ws['p'], ws['seed'])
             if on_ready is None:
-                self._run(ws, ws['bwd'], stream, outs=ws['outs'], seed=ws['seed'], p=ws['p'])
+                self._run(ws, plan, stream, outs=ws['outs'], seed=ws['seed'], p=ws['p'])
                 return
             start = 0
-            for end, lo, hi in ws['bwd_marks']:
-                self._run(ws, ws['bwd'][start:end], stream, outs=ws['outs'], seed=ws['seed'], p=ws['p'])
+            for end, lo, hi in marks:
+                self._run(ws, plan[start:end], stream, outs=ws['outs'], seed=ws['seed'], p=ws['p'])
                 on_ready(lo, hi)
                 start = end
 

@@ -10,7 +10,7 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (AttnDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry,
+from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry,
                     LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, STITCH_MAX_CLIPS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
                     ATTN_Q_F16PAIR, ATTN_KV_F16PAIR, check, lib)
@@ -478,6 +478,56 @@ def adam_step_guarded(p, g, m, v, step, ctl, lr=1e-4, beta1=0.9, beta2=0.999, ep
     _need_cuda(p, g, m, v, ctl)
     check(lib().hftt_adam_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), step, lr, beta1, beta2, eps,
                                        grad_scale, weight_decay, ctl.data_ptr(), _stream(p.device)), 'adam_step_guarded')
+
+
+def adam_group_map(entries, total, device=None):
+    """The per-quad group map of the grouped step: entries = (offset, numel, group) of every parameter in the flat buffer of `total` elements
+    (offsets multiples of 8, ascending, as layout.flat_offsets hands them out; total a multiple of 4).  A uint8 tensor [total / 4]: every quad
+    of a parameter carries its group, a quad in the alignment gap behind a parameter carries that parameter's group.  Built on the host with
+    numpy (it is index bookkeeping, not arithmetic on tensors) and copied to `device` once."""
+    entries = sorted((int(o), int(k), int(gi)) for o, k, gi in entries)
+    if total % 4 != 0 or not entries or entries[0][0] != 0:
+        raise HfttError('adam_group_map: the flat buffer must be a multiple of 4 elements and start with a parameter')
+    qmap = np.zeros(total // 4, dtype=np.uint8)
+    for i, (o, k, gi) in enumerate(entries):
+        end = entries[i + 1][0] if i + 1 < len(entries) else total
+        if o % 4 != 0 or o + k > end or not 0 <= gi < ADAM_MAX_GROUPS:
+            raise HfttError('adam_group_map: parameter at offset %d (%d elements, group %d) overlaps its neighbour, is not quad-aligned or names a group beyond %d'
+                            % (o, k, gi, ADAM_MAX_GROUPS - 1))
+        qmap[o // 4:end // 4] = gi
+    t = torch.from_numpy(qmap)
+    return t if device is None else t.to(device)
+
+
+def grad_norm_groups(g, quad_group, frozen_mask, ctl, ws, grad_scale=1.0, max_norm=math.inf):
+    """grad_norm with the quads of the groups in frozen_mask (bit k: group k) left out of the sum"""
+    _need_cuda(g, quad_group, ctl, ws)
+    if quad_group.dtype != torch.uint8 or quad_group.numel() * 4 != g.numel() or not quad_group.is_contiguous():
+        raise HfttError('grad_norm_groups: the group map must be a contiguous uint8 tensor with one entry per quad of g')
+    check(lib().hftt_grad_norm_groups(g.data_ptr(), g.numel(), quad_group.data_ptr(), int(frozen_mask), grad_scale, max_norm, ws.data_ptr(), ctl.data_ptr(),
+                                      _stream(g.device)), 'grad_norm_groups')
+
+
+def adam_step_groups(p, g, m, v, step, quad_group, lr, weight_decay=None, frozen=None, ctl=None, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
+    """One launch over the flat buffers with per-group constants: lr, weight_decay (decoupled) and frozen are sequences of one value per
+    group (1..8 groups).  ctl: the guard record (None: unguarded).  Quads of a frozen group are neither read nor written."""
+    _need_cuda(p, g, m, v, quad_group, ctl)
+    lr = [float(x) for x in lr]
+    k = len(lr)
+    weight_decay = [0.0] * k if weight_decay is None else [float(x) for x in weight_decay]
+    frozen = [False] * k if frozen is None else [bool(x) for x in frozen]
+    if len(weight_decay) != k or len(frozen) != k:
+        raise HfttError('adam_step_groups: lr, weight_decay and frozen must have one entry per group')
+    if quad_group.dtype != torch.uint8 or quad_group.numel() * 4 != p.numel() or not quad_group.is_contiguous():
+        raise HfttError('adam_step_groups: the group map must be a contiguous uint8 tensor with one entry per quad of p')
+    dsc = AdamGroupsDesc()
+    dsc.p, dsc.g, dsc.m, dsc.v, dsc.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    dsc.quad_group, dsc.n_groups, dsc.step = quad_group.data_ptr(), k, step
+    dsc.beta1, dsc.beta2, dsc.eps, dsc.grad_scale = beta1, beta2, eps, grad_scale
+    for i in range(min(k, ADAM_MAX_GROUPS)):
+        dsc.lr[i], dsc.weight_decay[i], dsc.frozen[i] = lr[i], weight_decay[i], 1 if frozen[i] else 0
+    dsc.ctl = None if ctl is None else ctl.data_ptr()
+    check(lib().hftt_adam_step_groups(C.byref(dsc), _stream(p.device)), 'adam_step_groups')
 
 
 # ------------------------------------------------------------------------------------------------

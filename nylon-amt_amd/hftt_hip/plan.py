@@ -148,9 +148,11 @@ def attn_meta(npass, bwd, n_seq, H, Lq, Lk, d, flags, planes, probs, dm):
 
 
 class PlanBuilder:
-    def __init__(self, eng, B):
+    def __init__(self, eng, B, ws=None):
+        """ws: a finished workspace of this engine and batch size, to write one more plan into it (build_decoder_backward); the builder is
+        not kept by the workspace -- a reference from there would tie the engine into a cycle and its device memory to the garbage collector"""
         self.eng, self.lib = eng, eng.lib
-        self.ws = {'bufs': {}, 'drop': [], 'keep': [], 'tn': [], 'ln': [], 'B': B}
+        self.ws = ws if ws is not None else {'bufs': {}, 'drop': [], 'keep': [], 'tn': [], 'ln': [], 'B': B}
         self.plan = None
         self.site = 0
         # The x3 strip kernels take whole 32-token strips (hftt_x3_strip_linear / hftt_x3_strip_mlp: M % 32 == 0).  A batch whose token counts
@@ -165,7 +167,8 @@ class PlanBuilder:
         # masked-in-consumers: the LayerNorm backward writes no masked copy; its consumers apply the dropout mask while they load dr
         # (x3 strip plans at d = 256, dropout on)
         self.mic = bool(self.strip and eng.x3 and not eng.strip_small and not eng.g8 and eng.ln_mask_in_consumers_opt and eng.dropout > 0.0)
-        self._spans = []                            # (first address, end address, stored as bf16) of every workspace tensor
+        # (first address, end address, stored as bf16) of every workspace tensor
+        self._spans = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), t.dtype == torch.bfloat16) for t in self.ws['bufs'].values()]
         self._bf16_content = set()                  # fp32-declared tensors that hold bf16 at this point of the plan (HFTT_BF16_GRAD)
 
     # ------------------------------------------------------------------ tensors
@@ -492,6 +495,22 @@ class PlanBuilder:
         ws['ln_ws_ptr'] = lnb.data_ptr()
         return ws
 
+    def build_decoder_backward(self):
+        """The frozen-encoder backward plan of a finished workspace (PlanBuilder(eng, B, ws)), built on first use by the same builder code
+        (build_backward(enc_grad=False)): it declares no new tensor and its products are shapes the full plan already has, so the two workspaces are shared as they are."""
+        ws = self.ws
+        if 'bwd_dec' in ws:
+            return
+        need, n_tn, n_ln, n_buf = (ws.get('tn_need'), ws.get('ln_need')), len(ws['tn']), len(ws['ln']), len(ws['bufs'])
+        self.backward = True
+        self.build_backward(enc_grad=False)
+        assert (ws.get('tn_need'), ws.get('ln_need')) == need and len(ws['bufs']) == n_buf
+        tnb, lnb = ws['bufs']['tn_ws'], ws['bufs']['ln_ws']
+        for dsc in ws['tn'][n_tn:]:
+            dsc.ws, dsc.ws_bytes = tnb.data_ptr(), tnb.numel() * 4
+        for dsc in ws['ln'][n_ln:]:
+            dsc.ws = lnb.data_ptr()
+
     def forward(self, save=True):
         """save=True: the training plan (everything a backward needs is written); save=False (strip mode only): the inference plan --
         no pre-LayerNorm sums, statistics or hidden activations are stored."""
@@ -622,7 +641,9 @@ class PlanBuilder:
             i += 1
         return out
 
-    def build_backward(self):
+    def build_backward(self, enc_grad=True):
+        """enc_grad=False: the backward of a model whose encoder is frozen -- the same layers, without the launches that form the encoder-output
+        gradient, ending where the frequency decoder's range is final (ws['bwd_dec'], two marks); nothing below the decoder is written"""
         e, ws = self.eng, self.ws
         B, T, F, N, V, d, p = ws['B'], e.T, e.F, e.N, e.V, e.d, e.p
         Se, Sn, BT, BN = B * T * F, B * T * N, B * T, B * N
@@ -675,8 +696,10 @@ class PlanBuilder:
         for i in reversed(range(e.Ld)):
             self.enc_layer_bwd(f'time{i}', f'{dd}layers_time.{i}.', Sn, BN, T, H, ws['time_in'][i], Gn)
         # ---- heads A, then the time-embedding transpose back onto the note-major gradient ----
+        # (heads A's weight-gradient product writes the FREQUENCY range of flat_grads: it is emitted behind the first mark below, so that the
+        #  plan's prefix up to that mark writes the time range and nothing else -- the backward of frozen_stages = 2.  Same launch, same
+        #  operands: dlog is not written again in this backward)
         plan.append(('heads_bwd', ('A', dlog, 0), 'heads_split_bwd', None))
-        self.tn(Sn, e.NHp, d, dlog, e.NHp, ws['dec_out'][-1], d, head_segs('freq'))
         self.nt(Sn, d, e.NHp, dlog, e.NHp, e.Wp('heads_f_t'), 0, nGD, d)
         plan.append(('time_embed_bwd', (nGA, nGD, nGB if use_drop else 0, ws['sites']['time_embed'], 7 if bs else 0), 'time_embed_bwd', None))
         plan.append(('colsum', (nGB if use_drop else nGA, BN, T * d, T * d, e.G(dd + 'pos_embedding_time.weight'), 0.0, cs_ws, 1 if bs else 0), 'colsum', None))
@@ -684,6 +707,7 @@ class PlanBuilder:
         # frequency decoder + heads A, time decoder + heads B): (plan length when final, flat lo, flat hi)
         o_dec, o_time, o_end = e.poff[dd + 'pos_embedding_freq.weight'], e.poff[dd + 'pos_embedding_time.weight'], e.flat_grads.numel()
         marks = [(len(plan), o_time, o_end)]
+        self.tn(Sn, e.NHp, d, dlog, e.NHp, ws['dec_out'][-1], d, head_segs('freq'))
         # ---- frequency decoder layers, last to first.  Gradient stream lives in A (= nGD), per-sequence dq in Q1 (= nGA);
         #      the encoder-output gradient accumulates in eGA ----
         A, Bf, Q1 = nGD, nGB, nGA
@@ -734,13 +758,15 @@ class PlanBuilder:
                         pcj = dd + ('layer_zero_freq.' if jj == 0 else f'layers_freq.{jj - 1}.') + 'encoder_attention.'
                         segs += [(2 * jj * d, d, e.G(pcj + 'fc_k.weight'), e.G(pcj + 'fc_k.bias')), ((2 * jj + 1) * d, d, e.G(pcj + 'fc_v.weight'), e.G(pcj + 'fc_v.bias'))]
                     self.tn(Se, ldg, d, gall, ldg, enc, d, segs)
-                    self.sl(Se, d, 3 * d, gall, ldg, 'dec.ca.kv_all_t0', 0, eGA, d)
-                    self.sl(Se, d, 3 * d, gall + 3 * d * 4, ldg, 'dec.ca.kv_all_t1', 0, eGA, d, residual=eGA, ldr=d)
+                    if enc_grad:
+                        self.sl(Se, d, 3 * d, gall, ldg, 'dec.ca.kv_all_t0', 0, eGA, d)
+                        self.sl(Se, d, 3 * d, gall + 3 * d * 4, ldg, 'dec.ca.kv_all_t1', 0, eGA, d, residual=eGA, ldr=d)
             else:
                 self.tn(Se, 2 * d, d, eGq, 2 * d, enc, d, [(0, d, e.G(pc + 'fc_k.weight'), e.G(pc + 'fc_k.bias')), (d, d, e.G(pc + 'fc_v.weight'), e.G(pc + 'fc_v.bias'))])
                 # (strip kernels: in place -- a lane reads exactly the residual elements it then overwrites; their descriptor carries ldr either way)
-                self.linear(Se, d, 2 * d, eGq, 2 * d, tag + '.ca.kv_t', 0, eGA, d, residual=0 if first_enc_grad else eGA,
-                            ldr=d if (st or not first_enc_grad) else 0)
+                if enc_grad:
+                    self.linear(Se, d, 2 * d, eGq, 2 * d, tag + '.ca.kv_t', 0, eGA, d, residual=0 if first_enc_grad else eGA,
+                                ldr=d if (st or not first_enc_grad) else 0)
                 first_enc_grad = False
             if j > 0:
                 # q projection of the cross attention (input x1, which is also the residual of this block)
@@ -756,6 +782,9 @@ class PlanBuilder:
                 self.tn(N, d, d, dq0s, d, e.P(dd + 'pos_embedding_freq.weight'), d, [(0, d, e.G(pc + 'fc_q.weight'), e.G(pc + 'fc_q.bias'))])
                 self.nt(N, d, d, dq0s, d, e.Wp(tag + '.ca.q_t'), 0, gpos, d, residual=gpos, ldr=d)
         marks.append((len(plan), o_dec, o_time))
+        if not enc_grad:                             # frozen encoder: no encoder layer backward, no embedding backward
+            ws['bwd_dec'], ws['bwd_dec_marks'] = plan, marks
+            return
         # ---- encoder layers ----
         Ge = (eGA, eGB, eGC, eGh, eGq, eGx)
         for i in reversed(range(e.Le)):

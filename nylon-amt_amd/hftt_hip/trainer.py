@@ -9,10 +9,17 @@ from __future__ import annotations
 import math
 import weakref
 
+import numpy as np
 import torch
 
 from . import ops
-from ._capi import HfttError
+from ._capi import ADAM_MAX_GROUPS, HfttError
+from .layout import flat_offsets
+
+# the two parameters at which the flat layout changes stage (encoder | frequency decoder + heads A | time decoder + heads B): the offsets
+# PlanBuilder.build_backward uses for its marks
+STAGE_BORDERS = ('decoder_spec2midi.pos_embedding_freq.weight', 'decoder_spec2midi.pos_embedding_time.weight')
+STAGES = ('encoder', 'freq', 'time')
 
 # parameter -> engine whose flat buffer it is a view of (filled by HfttEngine.bind): lets FusedAdam(model.parameters()) find the engine
 # although m_training.py:146 builds the optimizer before the first forward has bound anything
@@ -35,6 +42,29 @@ def engine_of(p):
     return ent[1]()
 
 
+def stage_groups(model, encoder=None, freq=None, time=None, no_decay_1d=False):
+    """Parameter groups for ``FusedAdam`` split by the three stages of the flat layout: the encoder, the frequency decoder with heads A, the
+    time decoder with heads B (borders: ``STAGE_BORDERS``, in ``model.named_parameters()`` order, which is the flat order).  Each stage
+    argument is a dict of group options, e.g. ``encoder=dict(frozen=True)``, ``time=dict(lr=1e-3)``; what it leaves out comes from the
+    optimizer's defaults.  ``no_decay_1d=True`` splits every stage once more: biases and LayerNorm parameters (every tensor with at most one
+    dimension) go into a twin group with ``weight_decay=0`` -- at most 6 groups.  Every group carries its name as ``'stage'``."""
+    named = list(model.named_parameters())
+    names = [n for n, _ in named]
+    if any(b not in names for b in STAGE_BORDERS):
+        raise HfttError('stage_groups: the model has no %s / %s (not an hFT-Transformer?)' % STAGE_BORDERS)
+    cut = [names.index(b) for b in STAGE_BORDERS]
+    groups = []
+    for stage, opts, lo, hi in zip(STAGES, (encoder, freq, time), [0] + cut, cut + [len(named)]):
+        opts = dict(opts or {})
+        ps = [p for _, p in named[lo:hi]]
+        if not no_decay_1d:
+            groups.append(dict(opts, params=ps, stage=stage))
+            continue
+        groups.append(dict(opts, params=[p for p in ps if p.dim() > 1], stage=stage))
+        groups.append(dict(opts, params=[p for p in ps if p.dim() <= 1], stage=stage + '.no_decay', weight_decay=0.0))
+    return [g for g in groups if g['params']]
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam(params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0) as ONE kernel over the engine's flat buffers.
 
@@ -53,28 +83,60 @@ class FusedAdam(torch.optim.Optimizer):
                      their bits.  Any of the three options turns the guard on.  ``state[p]['step']`` counts calls, so a skipped step still
                      advances it (``GradScaler`` does not count skipped steps; here the bias correction is slightly smaller for the first few
                      hundred steps after a skip, and checkpoints keep their layout).
-    ``weight_decay``   decoupled (``torch.optim.AdamW``: ``p *= 1 - lr * weight_decay`` before the update; ``param_groups[0]`` then says
-                     ``decoupled_weight_decay=True``).  The optimizer has ONE group, so the decay acts on every parameter, LayerNorm gains
-                     and biases included.  The L2 form (decay added to the gradient) is not implemented and a state that asks for it is refused.
+    ``weight_decay``   decoupled (``torch.optim.AdamW``: ``p *= 1 - lr * weight_decay`` before the update; the group then says
+                     ``decoupled_weight_decay=True``).  It is a per-group option: ``stage_groups(model, no_decay_1d=True)`` keeps biases and
+                     LayerNorm parameters in zero-decay groups, as AdamW recipes do.  The L2 form (decay added to the gradient) is not
+                     implemented and a state that asks for it is refused.
+
+    Parameter groups (fine-tuning): ``FusedAdam([{'params': ..., 'lr': ..., 'weight_decay': ..., 'frozen': True}, ...], lr=...)``, torch's
+    ordinary form, 1 to 8 groups which together hold exactly the bound model's parameters, each once (``stage_groups`` builds the usual
+    split).  ``lr``, ``weight_decay`` and ``frozen`` are per group; ``betas``, ``eps``, ``max_grad_norm`` and ``guard`` are shared and groups
+    that disagree on them are refused.  A frozen group's parameters and moments keep every bit: the kernel neither loads nor stores them.  A
+    parameter with ``requires_grad == False`` is frozen whatever its group says.  The step stays one launch (norm + step when guarded): a
+    per-quad group map in device memory says which constants a quad takes.  The map is rebuilt when a ``frozen`` option or a
+    ``requires_grad`` flag changes (a host-side signature is compared per step); learning rates travel in the launch descriptor, so a
+    scheduler's write to ``param_groups[i]['lr']`` costs nothing.  The guarded norm leaves frozen ranges out (``clip_grad_norm_`` over the
+    parameters that have a gradient), so an Inf in a frozen range does not skip the step.  ``frozen_stages()`` says how much of the flat
+    layout's front is frozen; ``TrainStep`` hands it to the engine, whose backward then stops where nothing trainable remains.  One group
+    with nothing frozen launches exactly the kernels described above.  ``state_dict()`` keeps torch's layout with several ``param_groups``
+    (``frozen`` is a group option like any other); a state whose group structure differs from the optimizer's is refused by torch
+    (``ValueError``), as for any torch optimizer.
 
     The decision is taken on the device: ``grad_norm`` and ``clip_coef`` are 0-dim device views of the kernel's record (reading them does
     not synchronise); ``skipped_steps`` and ``clipped_steps`` are Python ints, and reading them DOES synchronise.  ``state_dict()`` carries
     the two counters as ``hftt_guard``; a state without that key (older checkpoints, the reference's ``.dat``) loads."""
 
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, guard=False, weight_decay=0.0):
-        model = params if hasattr(params, 'hftt_engine') else None
-        if model is not None:
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, guard=False, weight_decay=0.0, model=None):
+        """model: the module whose parameters the groups hold -- needed only where the group map is wanted before an engine has bound them
+        (``frozen_stages()`` on a host without a GPU); with a bound engine the layout is the engine's."""
+        if hasattr(params, 'hftt_engine'):
+            model = params
             params = model.parameters()
+        params = list(params)
+        if params and isinstance(params[0], dict):
+            if not 1 <= len(params) <= ADAM_MAX_GROUPS:
+                raise HfttError('FusedAdam takes 1 to %d parameter groups, got %d' % (ADAM_MAX_GROUPS, len(params)))
+            params = [dict(g, params=list(g['params'])) for g in params]
+            seen = set()
+            for g in params:
+                for p in g['params']:
+                    if id(p) in seen:
+                        raise HfttError('FusedAdam: a parameter appears in more than one group (or twice in one)')
+                    seen.add(id(p))
+                if not float(g.get('weight_decay', weight_decay)) >= 0.0:
+                    raise HfttError('FusedAdam: weight_decay=%r must be >= 0' % (g.get('weight_decay', weight_decay),))
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise HfttError('FusedAdam: max_grad_norm=%r must be positive (None: no clipping)' % (max_grad_norm,))
         if not float(weight_decay) >= 0.0:
             raise HfttError('FusedAdam: weight_decay=%r must be >= 0' % (weight_decay,))
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None, capturable=False,
                                       differentiable=False, fused=None, decoupled_weight_decay=weight_decay != 0,
-                                      max_grad_norm=None if max_grad_norm is None else float(max_grad_norm), guard=bool(guard)))
-        if len(self.param_groups) != 1:
-            raise HfttError('FusedAdam takes one parameter group (the whole model), as m_training.py:146 builds it')
+                                      max_grad_norm=None if max_grad_norm is None else float(max_grad_norm), guard=bool(guard), frozen=False))
+        for g in self.param_groups:
+            g['decoupled_weight_decay'] = g['weight_decay'] != 0
+        self._check_shared()
         self._model = model
+        self._map = None                          # the group map and what it was built from (_group_map)
         self.engine = None
         self.step_count = 0
         self.exp_avg = self.exp_avg_sq = None
@@ -83,15 +145,87 @@ class FusedAdam(torch.optim.Optimizer):
 
     # ---- binding to the engine's flat buffers (lazy: the engine binds at the model's first forward)
     def _params(self):
-        return self.param_groups[0]['params']
+        if len(self.param_groups) == 1:
+            return self.param_groups[0]['params']
+        return [p for g in self.param_groups for p in g['params']]
+
+    def _check_shared(self):
+        g0 = self.param_groups[0]
+        for g in self.param_groups[1:]:
+            for k in ('betas', 'eps', 'max_grad_norm', 'guard'):
+                a, b = g0.get(k), g.get(k)
+                if (tuple(a) != tuple(b)) if k == 'betas' else (a != b):
+                    raise HfttError('FusedAdam: parameter groups disagree on %s (%r against %r): it is shared by all groups' % (k, a, b))
+
+    # ---- parameter groups: the per-quad map of the grouped kernels
+    def _layout(self):
+        """[(name, parameter, flat offset, numel)] and the flat length: the bound engine's, or the model's by the same rule"""
+        if self.engine is not None:
+            return self.engine._bound, self.engine.flat_params.numel()
+        if self._model is None:
+            raise HfttError('FusedAdam: the group map needs the flat layout: bind the parameters to an engine (a forward on the GPU) or pass model=')
+        named = list(self._model.named_parameters())
+        offs, total = flat_offsets((n, p.numel()) for n, p in named)
+        return [(n, p, o, p.numel()) for (n, p), o in zip(named, offs)], total
+
+    def _signature(self, layout):
+        return (id(self.engine), tuple(bool(g.get('frozen', False)) for g in self.param_groups), tuple(p.requires_grad for _, p, _, _ in layout))
+
+    def _group_map(self):
+        """The map state, rebuilt when a group's ``frozen`` or a parameter's ``requires_grad`` changed: dict(trivial, qmap (device uint8 or None
+        without an engine), frozen (one flag per kernel group), mask, stages).  trivial: one group, nothing frozen -- today's kernels run."""
+        layout, total = self._layout()
+        sig = self._signature(layout)
+        if self._map is not None and self._map['sig'] == sig:
+            return self._map
+        groups = self.param_groups
+        gi_of = {id(p): i for i, g in enumerate(groups) for p in g['params']}
+        if len(gi_of) != len(layout) or any(id(p) not in gi_of for _, p, _, _ in layout):
+            raise HfttError('FusedAdam: the parameter groups must together hold exactly the parameters of the bound model, each once '
+                            '(%d in the groups, %d in the model)' % (len(gi_of), len(layout)))
+        frozen = [bool(g.get('frozen', False)) for g in groups]
+        no_grad = [not p.requires_grad for _, p, _, _ in layout]
+        sink = None
+        if any(ng and not frozen[gi_of[id(p)]] for ng, (_, p, _, _) in zip(no_grad, layout)):
+            # requires_grad == False inside a trainable group: such a tensor moves to a frozen group -- a frozen quad reads none of its
+            # group's constants, so any frozen group serves, and a new one is opened only when there is none
+            sink = frozen.index(True) if True in frozen else len(frozen)
+            if sink == len(frozen):
+                if sink >= ADAM_MAX_GROUPS:
+                    raise HfttError('FusedAdam: %d groups and parameters with requires_grad=False inside trainable groups: no group index is '
+                                    'left for them (mark one of the groups frozen)' % len(groups))
+                frozen.append(True)
+        entries = [(o, n, sink if (ng and not frozen[gi_of[id(p)]]) else gi_of[id(p)]) for ng, (_, p, o, n) in zip(no_grad, layout)]
+        host = ops.adam_group_map(entries, total)
+        fq = np.asarray(frozen, dtype=bool)[host.numpy()]
+        off = {name: o for name, _, o, _ in layout}
+        borders = [off.get(b) for b in STAGE_BORDERS]
+        stages = 0
+        if None not in borders:
+            if fq[:borders[0] // 4].all():
+                stages = 2 if fq[borders[0] // 4:borders[1] // 4].all() else 1
+        self._map = dict(sig=sig, trivial=len(groups) == 1 and not any(frozen), frozen=frozen, mask=sum(1 << i for i, f in enumerate(frozen) if f),
+                         qmap=None if self.engine is None else host.to(self.engine.flat_params.device), stages=stages,
+                         borders=(0,) + tuple(b or 0 for b in borders), frozen_elements=int(fq.sum()) * 4, host=host)
+        return self._map
+
+    def frozen_stages(self):
+        """How many leading stages of the flat layout (encoder | frequency decoder + heads A | time decoder + heads B) are frozen as a whole:
+        0, 1 (the whole encoder range) or 2 (encoder and frequency decoder).  Derived from the group map; no device work."""
+        return self._group_map()['stages']
 
     def attach(self, engine):
         if self.engine is engine and self.exp_avg is not None and self.exp_avg.numel() == engine.flat_params.numel():
             return
         ps = self._params()
         bound = [p for _, p, _, _ in engine._bound]
-        if len(ps) != len(bound) or any(a is not b for a, b in zip(ps, bound)):
-            raise HfttError('FusedAdam must hold exactly model.parameters() of the bound model, in order')
+        if len(self.param_groups) == 1:
+            if len(ps) != len(bound) or any(a is not b for a, b in zip(ps, bound)):
+                raise HfttError('FusedAdam must hold exactly model.parameters() of the bound model, in order')
+        elif len(ps) != len(bound) or {id(p) for p in ps} != {id(p) for p in bound}:
+            raise HfttError('FusedAdam: the parameter groups must together hold exactly the parameters of the bound model, each once '
+                            '(%d in the groups, %d in the model)' % (len(ps), len(bound)))
+        ps = bound
         old = {p: dict(self.state[p]) for p in ps if p in self.state and 'exp_avg' in self.state[p]}
         self.engine = engine
         self.exp_avg = torch.zeros_like(engine.flat_params)
@@ -129,8 +263,11 @@ class FusedAdam(torch.optim.Optimizer):
                 loss = closure()
         self.attach(self._find_engine())
         g = self.param_groups[0]
+        mp = self._group_map()
         self.step_count += 1
-        if self._guarded(g):
+        if not mp['trivial']:
+            self._step_groups(mp, grad_scale)
+        elif self._guarded(g):
             mg = g.get('max_grad_norm')
             ops.grad_norm(self.engine.flat_grads, self._ctl, self._ws, grad_scale=grad_scale, max_norm=math.inf if mg is None else float(mg))
             ops.adam_step_guarded(self.engine.flat_params, self.engine.flat_grads, self.exp_avg, self.exp_avg_sq, self.step_count, self._ctl,
@@ -144,7 +281,23 @@ class FusedAdam(torch.optim.Optimizer):
             self.state[p]['step'].fill_(self.step_count)
         return loss
 
-    # ---- the guarded step: options in param_groups[0], the verdict and the counters in the device record
+    def _step_groups(self, mp, grad_scale):
+        """the grouped kernels: one launch unguarded, norm + step guarded"""
+        self._check_shared()
+        groups, g0, eng = self.param_groups, self.param_groups[0], self.engine
+        extra = len(mp['frozen']) - len(groups)     # (the group opened for requires_grad == False tensors: its constants are never read)
+        ctl = None
+        if any(self._guarded(g) for g in groups):
+            mg = g0.get('max_grad_norm')
+            ops.grad_norm_groups(eng.flat_grads, mp['qmap'], mp['mask'], self._ctl, self._ws, grad_scale=grad_scale,
+                                 max_norm=math.inf if mg is None else float(mg))
+            ctl = self._ctl
+        ops.adam_step_groups(eng.flat_params, eng.flat_grads, self.exp_avg, self.exp_avg_sq, self.step_count, mp['qmap'],
+                             lr=[float(g['lr']) for g in groups] + [0.0] * extra,
+                             weight_decay=[float(g.get('weight_decay', 0)) for g in groups] + [0.0] * extra, frozen=mp['frozen'], ctl=ctl,
+                             beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'], grad_scale=grad_scale)
+
+    # ---- the guarded step: options in the parameter groups, the verdict and the counters in the device record
     @staticmethod
     def _guarded(g):
         return bool(g.get('guard', False)) or g.get('max_grad_norm') is not None or g.get('weight_decay', 0) != 0
@@ -203,8 +356,9 @@ class FusedAdam(torch.optim.Optimizer):
             if l2 or g.get('amsgrad', False) or g.get('maximize', False):
                 raise HfttError('FusedAdam: the loaded state asks for weight_decay / amsgrad / maximize, which the fused Adam kernel does not do '
                                 '(reference: optim.Adam(model.parameters(), lr), m_training.py:146)')
-            for k in ('max_grad_norm', 'guard'):     # a state written without the options keeps the ones this optimizer was built with
+            for k in ('max_grad_norm', 'guard', 'frozen'):     # a state written without the options keeps the ones this optimizer was built with
                 g.setdefault(k, self.defaults[k])
+        self._map = None
         eng, self.engine, self.exp_avg = self.engine, None, None
         self._pending_counter = None
         self._pending_guard = None if guard is None else (int(guard['skipped']), int(guard['clipped']))
@@ -230,6 +384,7 @@ class TrainStep:
             self.opt._pending_counter = None
         self.weight_A, self.weight_B = weight_A, weight_B
         self.grad_sync = grad_sync          # callable(flat_grads) -> None (DDP all-reduce), or None
+        self._prune = 0                     # frozen stages of the last backward (flat_grads below its border was zeroed when it changed)
 
     def forward_backward(self, spec, label_onset, label_offset, label_mpe, label_velocity):
         eng = self.model.hftt_engine()
@@ -239,9 +394,19 @@ class TrainStep:
         with torch.cuda.device(eng.device):
             eng.forward(spec, training=self.model.training, save=True)
             loss = eng.loss(B, (label_onset, label_offset, label_mpe, label_velocity), self.weight_A, self.weight_B, with_grad=True)
+            # fine-tuning: the backward stops where nothing trainable remains (FusedAdam.frozen_stages; other optimizers: the whole backward).
+            # The pruned backward does not write flat_grads below the border: zeroed once per change, so that p.grad views read zeros
+            k = self.opt.frozen_stages() if hasattr(self.opt, 'frozen_stages') else 0
+            lo = eng.frozen_border(k)
+            if k != self._prune:
+                eng.flat_grads[:lo].zero_()
+                self._prune = k
             if self.grad_sync is not None:
-                self.grad_sync.begin_step()
-            eng.backward(B, on_ready=getattr(self.grad_sync, 'bucket_ready', None))
+                if lo:
+                    self.grad_sync.begin_step(lo=lo)
+                else:
+                    self.grad_sync.begin_step()
+            eng.backward(B, on_ready=getattr(self.grad_sync, 'bucket_ready', None), frozen_stages=k)
         return loss
 
     def __call__(self, spec, label_onset, label_offset, label_mpe, label_velocity):

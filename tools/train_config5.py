@@ -87,20 +87,26 @@ def lr_at(step, lr, warmup=0, total=0, final_frac=1.0):
 
 
 def train_loop(model, clips, dev, precision, lr, steps=0, minutes=0.0, batch=8, seed=77, warmup=0, final_frac=1.0, clip=0.0, log_every=250,
-               on_step=None, tag='', guard=False, weight_decay=0.0):
+               on_step=None, tag='', guard=False, weight_decay=0.0, groups=None):
     """the product's own training step until `steps` (or the time budget); returns (TrainStep, steps done, epochs started, loss curve, seconds).
-    clip > 0 / guard / weight_decay > 0 are FusedAdam's max_grad_norm / guard / weight_decay: the same TrainStep call, a guarded optimizer."""
-    from hftt_hip.trainer import FusedAdam, TrainStep
+    clip > 0 / guard / weight_decay > 0 are FusedAdam's max_grad_norm / guard / weight_decay: the same TrainStep call, a guarded optimizer.
+    groups: keyword arguments of hftt_hip.trainer.stage_groups (fine-tuning: frozen stages, per-stage rates, no decay on 1-D tensors); every
+    group's rate follows the schedule from its own base rate."""
+    from hftt_hip.trainer import FusedAdam, TrainStep, stage_groups
     model.hftt_precision = precision
     model.train()
-    ts = TrainStep(model, optimizer=FusedAdam(model, lr=lr, max_grad_norm=clip if clip > 0.0 else None, guard=guard, weight_decay=weight_decay))
+    params = model if not groups else stage_groups(model, **groups)
+    ts = TrainStep(model, optimizer=FusedAdam(params, lr=lr, max_grad_norm=clip if clip > 0.0 else None, guard=guard, weight_decay=weight_decay,
+                                              model=model))
     group = ts.opt.param_groups[0]
+    base = [g['lr'] for g in ts.opt.param_groups]
     t0, step, epoch, curve = time.time(), 0, 0, []
     acc = torch.zeros(9, device=dev)
     done = False
     while not done:
         for b in clips.loader(batch, shuffle=True, seed=seed + epoch, drop_last=True):
-            group['lr'] = lr_at(step + 1, lr, warmup, steps, final_frac)
+            for g, lr_g in zip(ts.opt.param_groups, base):
+                g['lr'] = lr_at(step + 1, lr_g, warmup, steps, final_frac)
             acc += ts(b[0], *b[1:])
             step += 1
             if on_step is not None:
@@ -179,7 +185,21 @@ def main():
     ap.add_argument('--out', default='gpurun_out/config5_tiny.pkl')
     ap.add_argument('--score-only', default='', help='skip training: score this pickled model')
     ap.add_argument('--init', default='', help='start from this pickled model (weights only: the optimizer state starts afresh) -- chains runs that are each bounded by the GPU call limit')
+    ap.add_argument('--freeze', default='', choices=['', 'encoder', 'encoder+freq'],
+                    help='fine-tuning (with --init): keep these stages\' bits; the backward stops where nothing trainable remains')
+    ap.add_argument('--lr-encoder', type=float, default=None, help='learning rate of the encoder (default: --lr)')
+    ap.add_argument('--lr-freq', type=float, default=None, help='learning rate of the frequency decoder and heads A (default: --lr)')
+    ap.add_argument('--lr-time', type=float, default=None, help='learning rate of the time decoder and heads B (default: --lr)')
+    ap.add_argument('--no-decay-1d', action='store_true', help='with --weight-decay: none on biases and LayerNorm parameters')
     args = ap.parse_args()
+    if args.freeze and not args.init:
+        ap.error('--freeze keeps pretrained weights fixed: it needs --init')
+    groups = None
+    if args.freeze or args.no_decay_1d or any(x is not None for x in (args.lr_encoder, args.lr_freq, args.lr_time)):
+        frozen = {'': (), 'encoder': ('encoder',), 'encoder+freq': ('encoder', 'freq')}[args.freeze]
+        groups = {st: dict(lr=args.lr if rate is None else rate, **({'frozen': True} if st in frozen else {}))
+                  for st, rate in (('encoder', args.lr_encoder), ('freq', args.lr_freq), ('time', args.lr_time))}
+        groups['no_decay_1d'] = args.no_decay_1d
     dev = torch.device('cuda:0')
     config = SA.default_config()
     cfg = bench.CONFIGS[args.config]
@@ -204,11 +224,13 @@ def main():
                     save_state(ts, step, args.save_state % step)
         ts, step, epoch, curve, secs = train_loop(model, clips, dev, args.precision, args.lr, steps=args.steps, minutes=args.minutes, batch=args.batch,
                                                    seed=args.seed, warmup=args.warmup, final_frac=args.final_frac, clip=args.clip, on_step=saver,
-                                                   guard=args.guard, weight_decay=args.weight_decay)
+                                                   guard=args.guard, weight_decay=args.weight_decay, groups=groups)
         if curve and curve[-1][1] != curve[-1][1]:
             log['diverged_at_step'] = step
         log['training'] = {'steps': step, 'epochs_started': epoch, 'seconds': round(secs, 1), 'lr': args.lr, 'warmup': args.warmup, 'final_frac': args.final_frac,
                            'clip': args.clip, 'guard': args.guard, 'weight_decay': args.weight_decay,
+                           'groups': [{k: v for k, v in g.items() if k in ('stage', 'lr', 'weight_decay', 'frozen')} for g in ts.opt.param_groups] if groups else None,
+                           'frozen_stages': ts.opt.frozen_stages(),
                            'skipped_steps': ts.opt.skipped_steps, 'clipped_steps': ts.opt.clipped_steps, 'pos_scale': args.pos_scale, 'batch': args.batch, 'dropout': 0.1, 'seed': args.seed,
                            'clips_per_s': round(step * args.batch / secs, 1), 'loss_curve': curve[:: max(1, len(curve) // 24)]}
         model.eval()
