@@ -644,6 +644,53 @@ typedef struct {
 int hftt_labels_render(const hftt_labels_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Clip log-mel (csrc/clip_logmel.hip): the spectrogram windows of a training batch computed from a resident WAVEFORM corpus when the batch is
+ * gathered -- what the clip windows above cut out of stored features, without the stored features.  ADDED at ABI 8; HFTT_ABI_VERSION stays 8.
+ *
+ * Corpus (device memory): `wave` holds the files' samples at the feature rate, concatenated without padding, as fp32 (wave_i16 = 0) or int16
+ * (wave_i16 = 1: the sample value is (float)s * (1 / 32768), exact); file f owns samples file_samp0[f] .. file_samp0[f + 1] (n of them, 0
+ * allowed).  Request: B windows of `width` frames; window b shows frames win_start[b] .. win_start[b] + width of file f = win_file[b], counted
+ * from the file's frame 0 (the start may be negative or lie behind the file: the convention of the clip windows and the label renderer).
+ *     out[b, m, c] = log-mel bin m of frame t = win_start[b] + c of THAT FILE'S waveform alone       when 0 <= t < 1 + n / hop
+ *                  = fill (to the bit)                                                               otherwise
+ * with the frame as the log-mel front end above defines it: samples t * hop - n_fft / 2 .. + n_fft, zeros outside [0, n) -- a neighbouring
+ * file's samples never enter -- times the window, |rDFT|^2, CSR mel sum, logf(. + log_offset); the tables have the formats of
+ * hftt_logmel_desc.  A window whose file index is outside 0 .. n_files, or whose file does not lie inside 0 .. total_samples, is fill.
+ *
+ * Augmentation, per window, on the sample in front of the window product (both pointers may be NULL; with both NULL the sample is untouched):
+ *     gain [B]       x <- fmul(x, gain[b])                                              (one rounding)
+ *     noise_std [B]  x <- fadd(x, fmul((float)(b0 + b1 + b2 + b3 - 510), fmul(noise_std[b], C)))        (one rounding each, never an fma)
+ * b0 .. b3 = the four bytes of the library's counter hash (csrc/hftt_common.h) of (seed, site = file, index = the sample's position inside its
+ * file); C = 1 / sqrt(21845) rounded to fp32 (the sum of four uniform bytes has mean 510 and variance 21845, so the term has standard
+ * deviation noise_std[b]).  The noise is keyed on the sample: the frames that overlap it, and two windows of one call that overlap, see the same
+ * noisy waveform.  The zeros outside the file stay zeros.
+ *
+ * One launch: a workgroup owns a window and HFTT_CLIP_LOGMEL_RUN consecutive frames, stages the (RUN - 1) * hop + n_fft samples they cover once
+ * in LDS, transforms frame after frame, and stores its [n_mels, RUN] tile along the frame axis (64 contiguous bytes per row).  One writer per
+ * element, no atomics, no workspace, 64-bit sample indices.
+ * Refused in front of the launch: null pointers (gain / noise_std excepted); wave_i16 outside 0 / 1; n_fft != 2048; B, width, hop or n_files
+ * < 1; n_mels outside 1 .. HFTT_CLIP_LOGMEL_MAX_MELS; total_samples < 0; a hop whose staged samples pass 64 KB of LDS (hop <= 324 fits).
+ * --------------------------------------------------------------------------------------------- */
+#define HFTT_CLIP_LOGMEL_RUN 16
+#define HFTT_CLIP_LOGMEL_MAX_MELS 256
+typedef struct {
+  const void* wave;                                              /* fp32 or int16 [total_samples] */
+  const int64_t* file_samp0;                                     /* [n_files + 1] */
+  const int32_t* win_file; const int32_t* win_start;             /* [B] */
+  int64_t total_samples;
+  int32_t wave_i16, n_files, B, width;
+  int32_t n_fft, hop, n_mels;
+  float log_offset;
+  const float* window; const float* twiddle;                     /* as hftt_logmel_desc */
+  const int32_t* fb_start; const int32_t* fb_len; const int32_t* fb_off; const float* fb_w;
+  float fill; int32_t pad;     /* fill: the config's min_value */
+  const float* gain; const float* noise_std;                     /* [B] or NULL */
+  uint64_t seed;
+  void* out;                                                     /* fp32 [B, n_mels, width] */
+} hftt_clip_logmel_desc;
+int hftt_clip_logmel(const hftt_clip_logmel_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Guarded optimizer step (csrc/guard.hip): global-norm gradient clipping, a non-finite guard and decoupled weight decay around the fused
  * Adam.  Like the note decoder and the label renderer these entry points were ADDED at ABI 8 and HFTT_ABI_VERSION stays 8: nothing that an
  * ABI-8 caller binds changed (hftt_adam_step above is untouched and remains the default step); a caller that needs them looks the symbols up.

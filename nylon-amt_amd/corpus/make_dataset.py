@@ -57,6 +57,26 @@ def assemble_note_store(features, notes_per_file, config):
     return {'feature': store['feature'], 'idx': store['idx'], 'file_row0': file_row0, 'table': table}
 
 
+def assemble_wave_store(waves, notes_per_file, config):
+    """waves: one mono waveform per file at the feature rate (1-d int16 or floating-point arrays); notes_per_file as assemble_note_store
+    takes it.  The corpus of training.dataset.WaveClipStore: nothing is padded and no feature is computed -- dict(waves: the samples as
+    given; file_nsamp int64 [n_files]; table: the host note table; clip_file int32 / clip_frame int32: every frame 0 .. nf - 1 of every
+    file, nf = max(1 + n_samp // hop, label frames) (make_dataset.py:52) -- the clips that assemble_note_store's idx lists for the
+    features 1 + n_samp // hop frames long, in the same order)."""
+    from hftt_hip.ops import labels_table_host
+    if len(waves) != len(notes_per_file):
+        raise ValueError('assemble_wave_store: %d waveforms, %d note lists' % (len(waves), len(notes_per_file)))
+    table = labels_table_host(notes_per_file, config)
+    hop = config['feature']['hop_sample']
+    file_nsamp = np.array([np.shape(w)[0] for w in waves], np.int64)
+    nf = np.maximum(1 + file_nsamp // hop, table['file_nframe'].astype(np.int64))
+    if int(nf.sum()) >= 1 << 31:
+        raise ValueError('assemble_wave_store: %d clips exceed the int32 index' % int(nf.sum()))
+    clip_file = np.repeat(np.arange(len(waves), dtype=np.int32), nf)
+    clip_frame = np.concatenate([np.arange(n, dtype=np.int32) for n in nf])
+    return {'waves': list(waves), 'file_nsamp': file_nsamp, 'table': table, 'clip_file': clip_file, 'clip_frame': clip_frame}
+
+
 def prepare_config(config, max_value=0.0):
     """What the reference's make_dataset.py __main__ sets BEFORE assembling (:274-278): input.max_value from the command line and
     input.min_value = log(log_offset) as a float32 (or log_offset itself when that is not positive).  In place; returns config."""

@@ -202,6 +202,22 @@ class LabelsDesc(C.Structure):
                 ('onset', C.c_void_p), ('offset', C.c_void_p), ('mpe', C.c_void_p), ('velocity', C.c_void_p)]
 
 
+CLIP_LOGMEL_RUN = 16                        # HFTT_CLIP_LOGMEL_RUN
+CLIP_LOGMEL_MAX_MELS = 256                  # HFTT_CLIP_LOGMEL_MAX_MELS
+
+
+class ClipLogmelDesc(C.Structure):
+    _fields_ = [('wave', C.c_void_p), ('file_samp0', C.c_void_p), ('win_file', C.c_void_p), ('win_start', C.c_void_p),
+                ('total_samples', C.c_int64),
+                ('wave_i16', C.c_int32), ('n_files', C.c_int32), ('B', C.c_int32), ('width', C.c_int32),
+                ('n_fft', C.c_int32), ('hop', C.c_int32), ('n_mels', C.c_int32), ('log_offset', C.c_float),
+                ('window', c_f32p), ('twiddle', c_f32p),
+                ('fb_start', C.c_void_p), ('fb_len', C.c_void_p), ('fb_off', C.c_void_p), ('fb_w', c_f32p),
+                ('fill', C.c_float), ('pad', C.c_int32),
+                ('gain', c_f32p), ('noise_std', c_f32p), ('seed', C.c_uint64),
+                ('out', C.c_void_p)]
+
+
 ADAM_MAX_GROUPS = 8                         # HFTT_ADAM_MAX_GROUPS
 
 
@@ -268,6 +284,7 @@ SIGNATURES = {
     'hftt_notes_seg_ws_bytes': (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     'hftt_notes_decode_seg': (C.c_int, [C.POINTER(NotesSegDesc), C.c_void_p]),
     'hftt_labels_render': (C.c_int, [C.POINTER(LabelsDesc), C.c_void_p]),
+    'hftt_clip_logmel': (C.c_int, [C.POINTER(ClipLogmelDesc), C.c_void_p]),
     'hftt_grad_norm_ws_bytes': (C.c_int64, [C.c_int64]),
     'hftt_grad_norm': (C.c_int, [c_f32p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hftt_adam_step_guarded': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32,

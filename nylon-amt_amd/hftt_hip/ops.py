@@ -10,7 +10,7 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry,
+from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry,
                     LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, STITCH_MAX_CLIPS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
                     ATTN_Q_F16PAIR, ATTN_KV_F16PAIR, check, lib)
@@ -833,6 +833,83 @@ def clip_windows(feature, file_row0, win_file, win_start, width, fill):
     d.feature, d.file_row0, d.win_file, d.win_start, d.out = (t.data_ptr() for t in (keep, file_row0, win_file, win_start, out))
     d.B, d.width, d.n_bins, d.n_files, d.R, d.fill = B, width, n_bins, file_row0.numel() - 1, R, float(fill)
     check(lib().hftt_clip_windows(C.byref(d), _stream(dev)), 'clip_windows')
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Clip log-mel (hftt_clip_logmel): the corpus keeps the WAVEFORMS, a batch's spectrogram windows are computed when it is gathered
+WAVE_DTYPES = {'int16': torch.int16, 'float32': torch.float32}
+
+
+class WaveTable:
+    """The waveform corpus of clip_logmel on one device, uploaded once: the files' samples (1-d arrays / tensors at the feature rate, int16 or
+    floating point) concatenated without padding as `dtype` ('int16': 2 bytes per sample, value s / 32768; 'float32'), and file_samp0 int64
+    [n_files + 1].  Floating-point samples stored as int16 are round(x * 32768) clipped to the int16 range; int16 samples stored as float32
+    are s / 32768 (exact)."""
+
+    def __init__(self, waves, device, dtype='int16'):
+        if dtype not in WAVE_DTYPES:
+            raise HfttError('WaveTable: dtype %r (int16 / float32)' % (dtype,))
+        if len(waves) < 1:
+            raise HfttError('WaveTable: no files')
+        self.device = torch.device(device)
+        self.dtype = dtype
+        parts = []
+        for i, w in enumerate(waves):
+            w = torch.as_tensor(w)
+            if w.dim() != 1:
+                raise HfttError('WaveTable: file %d: a waveform is 1-d (mono), got shape %s' % (i, tuple(w.shape)))
+            if w.dtype == torch.int16:
+                parts.append(w if dtype == 'int16' else w.float() * (1.0 / 32768.0))
+            elif w.dtype.is_floating_point:
+                parts.append(w.float() if dtype == 'float32' else torch.round(w.double() * 32768.0).clamp(-32768, 32767).to(torch.int16))
+            else:
+                raise HfttError('WaveTable: file %d: samples are int16 or floating point, got %s' % (i, w.dtype))
+        self.file_nsamp_host = np.array([p.numel() for p in parts], np.int64)
+        samp0 = np.concatenate([[0], np.cumsum(self.file_nsamp_host)]).astype(np.int64)
+        self.n_files, self.total_samples = len(parts), int(samp0[-1])
+        wave = torch.cat(parts) if self.total_samples else torch.zeros(1, dtype=WAVE_DTYPES[dtype])      # (a pointer that is only non-null)
+        self.wave = wave.contiguous().to(self.device)
+        self.file_samp0 = torch.from_numpy(samp0).to(self.device)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.wave, self.file_samp0))
+
+
+def clip_logmel(table, logmel, win_file, win_start, width, fill, gain=None, noise_std=None, seed=0):
+    """B clip windows of a waveform corpus -> spec [B, n_mels, width] fp32 in ONE launch (hftt_clip_logmel): window b shows log-mel frames
+    win_start[b] .. + width of file win_file[b] of `table` (a WaveTable), each frame computed from that file's samples alone with the device
+    tables of `logmel` (an ops.LogMel); frames outside the file are `fill`.  gain / noise_std: fp32 [B] device tensors or None (per-window
+    gain factor; standard deviation of additive noise keyed on (seed, file, sample)).  Nothing is read back to the host."""
+    dev = table.device
+    win_file = torch.as_tensor(win_file, device=dev).to(torch.int32).contiguous()
+    win_start = torch.as_tensor(win_start, device=dev).to(torch.int32).contiguous()
+    _need_cuda(table.wave, table.file_samp0, logmel.window, win_file, win_start)
+    if logmel.device != dev:
+        raise HfttError('clip_logmel: the LogMel tables live on %s, the corpus on %s' % (logmel.device, dev))
+    if win_file.dim() != 1 or win_start.shape != win_file.shape:
+        raise HfttError('clip_logmel: win_file and win_start must be [B]')
+    B, width = win_file.numel(), int(width)
+    aug = []
+    for name, t in (('gain', gain), ('noise_std', noise_std)):
+        if t is not None:
+            t = torch.as_tensor(t, device=dev).to(torch.float32).contiguous()
+            _need_cuda(t)
+            if t.shape != win_file.shape:
+                raise HfttError('clip_logmel: %s must be [B]' % name)
+        aug.append(t)
+    out = torch.empty((B, logmel.n_mels, max(width, 0)), dtype=torch.float32, device=dev)      # an empty request is the library's to refuse
+    d = ClipLogmelDesc()
+    d.wave, d.file_samp0, d.win_file, d.win_start = table.wave.data_ptr(), table.file_samp0.data_ptr(), win_file.data_ptr(), win_start.data_ptr()
+    d.total_samples, d.wave_i16, d.n_files, d.B, d.width = table.total_samples, int(table.dtype == 'int16'), table.n_files, B, width
+    d.n_fft, d.hop, d.n_mels, d.log_offset = logmel.n_fft, logmel.hop, logmel.n_mels, logmel.log_offset
+    d.window, d.twiddle = logmel.window.data_ptr(), logmel.twiddle.data_ptr()
+    d.fb_start, d.fb_len, d.fb_off, d.fb_w = logmel.fb_start.data_ptr(), logmel.fb_len.data_ptr(), logmel.fb_off.data_ptr(), logmel.fb_w.data_ptr()
+    d.fill = float(fill)
+    d.gain, d.noise_std = (t.data_ptr() if t is not None else None for t in aug)
+    d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    d.out = out.data_ptr()
+    check(lib().hftt_clip_logmel(C.byref(d), _stream(dev)), 'clip_logmel')
     return out
 
 

@@ -1,0 +1,95 @@
+#!/usr/bin/env python3
+"""Time a training batch from WaveClipStore (int16 waveforms + notes resident; log-mel windows by hftt_clip_logmel, labels by
+hftt_labels_render) against the same clips from NoteClipStore (fp32 log-mel features + notes resident), and count the bytes both keep in HBM
+(GPU box).
+
+  python tools/bench_wave_store.py --files 2 --out profiles/wave_store.json [--step-ms 27.5]
+
+Corpus: `--files` synthetic minutes of corpus.synth_audio (pluck_notes / pluck_wave) at the paper clip geometry (128 frames + 2 x 32 margin,
+256 mel bins, 88 pitches); the note store's features are ops.LogMel of the same waveforms.  Three stores gather the SAME shuffled batches of
+`--batch` clips: the note store, the wave store without augmentation, the wave store with both augmentations (gain and noise drawn per clip).  A
+call is timed with one device event on each side, after a warm-up, the stores alternating; the median of `--calls` calls is reported.
+--step-ms: the benchmark's median step time on the same box (bench.py --gpus 1), to state the extra time of a batch as a share of a step."""
+import argparse, json, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'nylon-amt_amd'))
+import numpy as np
+import torch
+from corpus import synth_audio as SA
+from corpus.make_dataset import assemble_note_store, assemble_wave_store, finalize_config, prepare_config
+from hftt_hip import ops
+from training.dataset import NoteClipStore, WaveAugment, WaveClipStore
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--files', type=int, default=2, help='synthetic one-minute files')
+    ap.add_argument('--batch', type=int, default=8)
+    ap.add_argument('--calls', type=int, default=300)
+    ap.add_argument('--warmup', type=int, default=30)
+    ap.add_argument('--step-ms', type=float, default=0.0)
+    ap.add_argument('--out', default='profiles/wave_store.json')
+    args = ap.parse_args()
+    dev = torch.device('cuda:0')
+    config = finalize_config(prepare_config(SA.default_config()))
+    notes = [SA.pluck_notes(2000 + i) for i in range(args.files)]
+    waves = [SA.pluck_wave(a, device=dev) for a in notes]
+    lm = ops.LogMel(dev)
+    feats = [lm(w).cpu().numpy() for w in waves]
+    waves = [w.cpu().numpy() for w in waves]
+    old = NoteClipStore(assemble_note_store(feats, notes, config), config, dev)
+    wstore = assemble_wave_store(waves, notes, config)
+    new = WaveClipStore(wstore, config, dev, wave_dtype='int16')
+    aug = WaveClipStore(wstore, config, dev, wave_dtype='int16', augment=WaveAugment(gain_db=(-6.0, 6.0), noise_dbfs=(-60.0, -40.0), seed=1))
+    assert len(old) == len(new) == len(aug)
+    chunks = old.loader(args.batch, shuffle=True, seed=1, drop_last=True).chunks
+    chunks = [c.to(dev) for c in chunks[:args.warmup + args.calls]]
+    assert len(chunks) == args.warmup + args.calls, 'corpus too small for %d calls' % (args.warmup + args.calls)
+    t_old, t_new, t_aug, t_kernel = [], [], [], []
+    cin = config['input']
+    width = cin['margin_b'] + cin['num_frame'] + cin['margin_f']
+    for i, c in enumerate(chunks):
+        ms_old, a = timed(lambda: old.batch(c))
+        ms_new, b = timed(lambda: new.batch(c))
+        ms_aug, _ = timed(lambda: aug.batch(c))
+        file, start = new.clip_file[c], new.clip_frame[c] - cin['margin_b']
+        ms_k, _ = timed(lambda: ops.clip_logmel(new.waves, new.logmel, file, start, width, new.fill))
+        if i == 0:
+            assert all(torch.equal(x, y) for x, y in zip(a[1:], b[1:])), 'the labels of the two stores disagree'
+            worst = float((a[0] - b[0]).abs().max())            # int16 audio against fp32 audio: reported, the tests hold the kernel to fp64
+        if i >= args.warmup:
+            t_old.append(ms_old); t_new.append(ms_new); t_aug.append(ms_aug); t_kernel.append(ms_k)
+    med = lambda v: float(np.median(v))
+    p = lambda v: [float(np.percentile(v, 10)), float(np.percentile(v, 90))]
+    frames = sum(f.shape[0] for f in feats)
+    res = {'what': 'WaveClipStore.batch (int16 waveforms; plain and with gain + noise) against NoteClipStore.batch on the same clip ids (device events around each call, median)',
+           'device': torch.cuda.get_device_name(0), 'files': args.files, 'audio_frames': frames, 'samples': int(wstore['file_nsamp'].sum()), 'clips': len(old),
+           'notes': int(new.table.n_notes), 'batch': args.batch, 'window_frames': width, 'mel_bins': config['feature']['mel_bins'], 'calls': args.calls, 'warmup': args.warmup,
+           'note_store_batch_ms': med(t_old), 'wave_store_batch_ms': med(t_new), 'wave_store_augmented_batch_ms': med(t_aug), 'clip_logmel_call_ms': med(t_kernel),
+           'extra_ms_per_batch': med(t_new) - med(t_old), 'extra_ms_per_batch_augmented': med(t_aug) - med(t_old),
+           'spread_ms': {'note_store_p10_p90': p(t_old), 'wave_store_p10_p90': p(t_new), 'wave_store_augmented_p10_p90': p(t_aug)},
+           'first_batch_max_abs_spec_difference_int16_audio': worst,
+           'note_store_resident_bytes': int(old.resident_bytes()), 'wave_store_resident_bytes': int(new.resident_bytes()),
+           'note_store_bytes_per_frame': old.resident_bytes() / frames, 'wave_store_bytes_per_frame': new.resident_bytes() / frames}
+    if args.step_ms > 0.0:
+        res['benchmark_step_ms_median'] = args.step_ms
+        res['extra_share_of_step'] = res['extra_ms_per_batch'] / args.step_ms
+        res['extra_share_of_step_augmented'] = res['extra_ms_per_batch_augmented'] / args.step_ms
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()

@@ -6,7 +6,9 @@
 Corpus: `--files` one-minute files from corpus.synth_audio (seeds 2000.., never the scored file's seed 1234) -> HIP log-mel
 (model.amt.AMT.wave2feature) -> frame labels (corpus.conv_note2label.note2label_arrays, the reference's label recipe) -> one MAESTRO-format
 store (corpus.make_dataset.assemble_store) resident in HBM (training.dataset.DeviceClipStore); with --note-store the corpus keeps the NOTES
-instead of the label tracks (assemble_note_store, NoteClipStore) and every batch's labels are rendered on the device.  Training: the product's own step
+instead of the label tracks (assemble_note_store, NoteClipStore) and every batch's labels are rendered on the device; with --wave-store it keeps the
+WAVEFORMS (int16) and the notes (assemble_wave_store, WaveClipStore): no feature pass, every batch's log-mel windows are computed on the device,
+optionally under --aug-gain-db LO HI / --aug-noise-dbfs LO HI (per-clip gain and additive noise, new for every batch).  Training: the product's own step
 (hftt_hip.trainer.TrainStep: forward + fused loss + backward + fused Adam) in the chosen precision mode, dropout 0.1, batch 8, until the
 time budget is spent.  The model is pickled the way m_training.py:372-373 does it (whole module, protocol 4).
 
@@ -20,17 +22,23 @@ import torch
 import bench
 from corpus import synth_audio as SA
 from corpus.conv_note2label import note2label_arrays
-from corpus.make_dataset import assemble_note_store, assemble_store
-from training.dataset import MyDataset, DeviceClipStore, NoteClipStore
+from corpus.make_dataset import assemble_note_store, assemble_store, assemble_wave_store
+from training.dataset import MyDataset, DeviceClipStore, NoteClipStore, WaveAugment, WaveClipStore
 from model.amt import AMT
 from evaluation.metrics import note_metrics, frame_metrics
 
 
-def build_corpus(config, files, dev, n_slice=8, note_store=False):
+def build_corpus(config, files, dev, n_slice=8, note_store=False, wave_store=False, augment=None):
     """`files` one-minute plucked-string files (seeds 2000..) -> HIP log-mel -> reference-recipe labels -> one MAESTRO-format store in HBM;
     note_store: features + note table in HBM instead, labels rendered per batch (a file is then as long as its label track, not cut to its
-    feature array)"""
+    feature array); wave_store: waveforms (int16) + note table in HBM, no feature pass, `augment` a WaveAugment or None"""
     t0 = time.time()
+    if wave_store:
+        note_lists = [SA.pluck_notes(2000 + i) for i in range(files)]
+        store = assemble_wave_store([SA.pluck_wave(notes, device=dev).cpu().numpy() for notes in note_lists], note_lists, config)
+        clips = WaveClipStore(store, config, dev, n_slice, wave_dtype='int16', augment=augment)
+        return clips, {'files': files, 'samples': int(store['file_nsamp'].sum()), 'clips': len(clips), 'notes': clips.table.n_notes,
+                       'resident_bytes': clips.resident_bytes(), 'seconds_to_build': round(time.time() - t0, 1)}
     tmp = tempfile.mkdtemp()
     with open(os.path.join(tmp, 'init.pkl'), 'wb') as fh:
         pickle.dump(bench.build_model(bench.CONFIGS['tiny'], 1, 0.1, 'cpu'), fh, protocol=4)
@@ -182,6 +190,9 @@ def main():
     ap.add_argument('--save-state', default='', help='pattern with one %%d: write the full training state there at the steps of --save-state-at')
     ap.add_argument('--save-state-at', default='')
     ap.add_argument('--note-store', action='store_true', help='keep notes instead of label tracks in HBM and render every batch\'s labels on the device (NoteClipStore)')
+    ap.add_argument('--wave-store', action='store_true', help='keep int16 waveforms and notes in HBM and compute every batch\'s log-mel windows and labels on the device (WaveClipStore)')
+    ap.add_argument('--aug-gain-db', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --wave-store: per-clip gain, uniform in dB, new for every batch')
+    ap.add_argument('--aug-noise-dbfs', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --wave-store: per-clip additive noise level, uniform in dB re full scale')
     ap.add_argument('--out', default='gpurun_out/config5_tiny.pkl')
     ap.add_argument('--score-only', default='', help='skip training: score this pickled model')
     ap.add_argument('--init', default='', help='start from this pickled model (weights only: the optimizer state starts afresh) -- chains runs that are each bounded by the GPU call limit')
@@ -213,7 +224,12 @@ def main():
             with open(args.init, 'rb') as fh:
                 model.load_state_dict(pickle.load(fh).state_dict())
             log['init'] = args.init
-        clips, log['corpus'] = build_corpus(config, args.files, dev, note_store=args.note_store)
+        if (args.aug_gain_db or args.aug_noise_dbfs) and not args.wave_store:
+            ap.error('--aug-gain-db / --aug-noise-dbfs act on the waveform: they need --wave-store')
+        augment = WaveAugment(gain_db=args.aug_gain_db, noise_dbfs=args.aug_noise_dbfs, seed=args.seed) if (args.aug_gain_db or args.aug_noise_dbfs) else None
+        clips, log['corpus'] = build_corpus(config, args.files, dev, note_store=args.note_store, wave_store=args.wave_store, augment=augment)
+        if args.wave_store:
+            log['augment'] = {'gain_db': args.aug_gain_db, 'noise_dbfs': args.aug_noise_dbfs}
         # ---- training ----
         model = model.to(dev)
         saver = None
