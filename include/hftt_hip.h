@@ -691,6 +691,93 @@ typedef struct {
 int hftt_clip_logmel(const hftt_clip_logmel_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Pitch-shift and timing augmentation (csrc/wave_warp.h, csrc/wave_warp.hip, csrc/clip_logmel.hip, csrc/labels.hip): a clip played back at
+ * rate r = 2^((k + c) / 12) -- every pitch moves by k semitones plus a detune c, every note time scales by 1 / r -- resampled while the clip's
+ * samples are staged, and the labels rendered under the matching map.  Three entry points ADDED at ABI 8; HFTT_ABI_VERSION stays 8 and every
+ * descriptor above keeps its layout.
+ *
+ * The warp of one window b -- fixed point, no floating-point positions:
+ *     step_q24[b]   int32, r * 2^24, HFTT_WARP_STEP_MIN <= step <= HFTT_WARP_STEP_MAX (2^23 .. 2^25: one octave either way)
+ *     delay_q24[b]  int64, source samples * 2^24, 0 <= delay <= HFTT_WARP_DELAY_MAX (2^48): a DELAY, so warped note times never go negative
+ *     cut[b]        float, the cutoff relative to the source's Nyquist rate: 0.99 * min(1, 2^24 / step), supplied by the host
+ * A window whose step or delay lies outside these ranges, or whose cut lies outside 0.25 .. 1 (a NaN included), is treated as a window
+ * without a file (fill / zeros).
+ * Warped sample j of a file with n source samples reads source position pos = j * step - delay (int64, Q24).  The warped file has
+ *     n' = 0 for n = 0, else floor((((n - 1) << 24) + delay) / step) + 1 samples       and 1 + n' / hop frames;
+ * warped samples outside [0, n') are zeros.  Inside, with `#pragma clang fp contract(off)` (every operation below is one fp32 rounding):
+ *     acc = 0; for i = (pos >> 24) - H .. (pos >> 24) + H + 1 in INCREASING order, skipping i outside [0, n) (zeros outside the file: a
+ *     neighbouring file's samples never enter), with d = |pos - (i << 24)| (int64):
+ *         q = fmul((float)d, cut[b])                     (int64 -> fp32 round-to-nearest, then one product)
+ *         skipped unless q <= Z * 2^24                   (Z = HFTT_WARP_ZEROS = 6 zero crossings either side)
+ *         x = fmul(q, L / 2^24)                          (L = HFTT_WARP_TABLE_L = 512 entries per zero crossing: a power of two, exact)
+ *         e = (int)x; f = x - (float)e                   (truncation; the difference is exact)
+ *         w = fadd(T[e], fmul(f, fsub(T[e + 1], T[e])))  (the prototype, linearly interpolated)
+ *         acc = fadd(acc, fmul(fmul(w, cut[b]), s_i))    (s_i: the source sample, an int16 one dequantised first as (float)s * (1 / 32768))
+ * H = (int)(Z / cut[b]) + 2 only has to cover every i that passes the test on q (at most 2 Z / cut + 1 <= 26 of them do).
+ * T = the prototype sinc(u) * cos^2(pi u / 2Z) at u = e / L, e = 0 .. Z L, built by the host in fp64 and rounded once to fp32
+ * (HFTT_WARP_TABLE_LEN = Z L + 2 entries; the last two are exact zeros).  This is a Hann-windowed sinc with the published defaults
+ * (lowpass_filter_width 6, rolloff 0.99) scaled to the cutoff.
+ * Identity bypass: a window with step == 2^24 and delay a multiple of 2^24 takes source sample j - (delay >> 24) directly (zero outside
+ * [0, n)).  The condition is uniform per window.
+ *
+ * hftt_wave_warp: out[b, c] (fp32 [B, len]) = warped sample win_start[b] + c (win_start int64) of file win_file[b] under window b's warp, BEFORE
+ * gain and noise; 0 outside [0, n') and for a window without a (valid) file.  It makes the interpolation observable and writes an augmented copy
+ * of a file.  One thread per output sample; the sample is the ONE device function (csrc/wave_warp.h) that the staging loop below calls.
+ * Refused: null pointers; wave_i16 outside 0 / 1; B, len or n_files < 1; total_samples outside 0 .. 2^38; B * ceil(len / 256) >= 2^31.
+ *
+ * hftt_clip_logmel_warp: hftt_clip_logmel (`base`: outputs, fill rule, tile store and refusals as there) with win_start counted in frames of
+ * the WARPED file (1 + n' / hop of them) and the staged sample j = the warped sample j.  Gain and noise are applied to the warped sample by
+ * the same two operations, the noise keyed on (seed, file, j): it stays white and does not pass through the filter.  A window that takes the
+ * identity bypass is bit-identical to hftt_clip_logmel on the file with delay >> 24 zeros put in front: with delay = 0 the same window, with
+ * delay = m * hop samples (and no noise, which is keyed on j) the window at win_start - m.  The taps are read from global memory (neighbouring lanes
+ * read overlapping spans); the LDS arrays are hftt_clip_logmel's.  Also refused: null step_q24 / delay_q24 / cut / proto; total_samples > 2^38.
+ *
+ * hftt_labels_render_warp: hftt_labels_render (`base`) under the map of the same warp:
+ *     output pitch j of window b walks group file * N + (j - shift[b]); a source pitch outside 0 .. N gives an all-zero column
+ *     every note time t becomes t' = fmul(fadd(t, t_delay[b]), t_scale[b]) (fp64, two roundings, never an fma); the arithmetic of
+ *     hftt_labels_render then runs on t' unchanged
+ *     file_nframe' = (int)(fmul(fmul(fadd(file_end_sec[file], t_delay[b]), t_scale[b]), fps) + 0.5) + 1, and 1 for a file without notes
+ *     (row_ptr[file * N] == row_ptr[file * N + N]); file_end_sec[file] = the largest offset over ALL the file's notes, 0 without notes
+ *     flags bit 0 is the table's, that is, the unwarped list's; win_start counts frames of the warped file; base.file_nframe is not read
+ * with t_scale = 2^24 / step and t_delay = delay / 2^24 / sr formed by the caller in fp64.  Also refused: null shift / t_delay / t_scale /
+ * file_end_sec.
+ * --------------------------------------------------------------------------------------------- */
+#define HFTT_WARP_ZEROS 6
+#define HFTT_WARP_TABLE_L 512
+#define HFTT_WARP_TABLE_LEN (HFTT_WARP_ZEROS * HFTT_WARP_TABLE_L + 2)
+#define HFTT_WARP_STEP_MIN (1 << 23)
+#define HFTT_WARP_STEP_MAX (1 << 25)
+#define HFTT_WARP_DELAY_MAX ((int64_t)1 << 48)
+typedef struct {
+  const int32_t* step_q24;     /* [B] */
+  const int64_t* delay_q24;    /* [B] */
+  const float* cut;            /* [B] */
+  const float* proto;          /* [HFTT_WARP_TABLE_LEN] */
+} hftt_warp_args;
+typedef struct {
+  hftt_clip_logmel_desc base;
+  hftt_warp_args warp;
+} hftt_clip_logmel_warp_desc;
+int hftt_clip_logmel_warp(const hftt_clip_logmel_warp_desc* d, void* stream);
+typedef struct {
+  const void* wave;                                              /* fp32 or int16 [total_samples] */
+  const int64_t* file_samp0;                                     /* [n_files + 1] */
+  const int32_t* win_file; const int64_t* win_start;             /* [B]; win_start in warped samples */
+  int64_t total_samples;
+  int32_t wave_i16, n_files, B, len;
+  hftt_warp_args warp;
+  void* out;                                                     /* fp32 [B, len] */
+} hftt_wave_warp_desc;
+int hftt_wave_warp(const hftt_wave_warp_desc* d, void* stream);
+typedef struct {
+  hftt_labels_desc base;
+  const int32_t* shift;                                          /* [B] semitones */
+  const double* t_delay; const double* t_scale;                  /* [B] */
+  const double* file_end_sec;                                    /* [n_files] */
+} hftt_labels_warp_desc;
+int hftt_labels_render_warp(const hftt_labels_warp_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Guarded optimizer step (csrc/guard.hip): global-norm gradient clipping, a non-finite guard and decoupled weight decay around the fused
  * Adam.  Like the note decoder and the label renderer these entry points were ADDED at ABI 8 and HFTT_ABI_VERSION stays 8: nothing that an
  * ABI-8 caller binds changed (hftt_adam_step above is untouched and remains the default step); a caller that needs them looks the symbols up.

@@ -1,5 +1,6 @@
 // Clip log-mel (gfx950): the spectrogram windows of a training batch straight from a resident WAVEFORM corpus, one launch.
-//   hftt_clip_logmel  B windows [width frames] of the files' concatenated samples (fp32 or int16) -> spec [B, n_mels, width] fp32
+//   hftt_clip_logmel       B windows [width frames] of the files' concatenated samples (fp32 or int16) -> spec [B, n_mels, width] fp32
+//   hftt_clip_logmel_warp  the same of the files played back at a per-window rate and delay: the staged sample is wave_warp.h's warp_sample
 // A workgroup owns one window and a run of RUN consecutive frames.  It stages the (RUN - 1) * hop + n_fft samples those frames cover once in
 // LDS -- converted, gained, noised, zeros outside the file: consecutive frames share 7/8 of them at hop = n_fft / 8 -- transforms frame after
 // frame with the arithmetic of logmel_kernel (logmel.hip: packed 1024-point radix-4 Stockham transform, split pass, |X|^2, sequential CSR mel
@@ -8,6 +9,7 @@
 // The frame transform is written a second time here on purpose: tests/frontend_emul.py cites logmel.hip by line.
 #include "hftt_common.h"
 #include "hftt_launch.h"
+#include "wave_warp.h"
 #include "../../include/hftt_hip.h"
 
 namespace {
@@ -35,8 +37,10 @@ __device__ __forceinline__ float mix(float s, bool has_gain, float gain, bool ha
   return s;
 }
 
-template <int NFFT>
-__global__ __launch_bounds__(256) void clip_logmel_kernel(const hftt_clip_logmel_desc g, int nruns) {
+// WARP: only the staging loop differs -- the window's frames are counted in the warped file and a staged sample is interpolated from the
+// source in global memory (up to 26 taps; neighbouring lanes read overlapping spans).  The LDS arrays and the frame transform are the same.
+template <int NFFT, bool WARP>
+__global__ __launch_bounds__(256) void clip_logmel_kernel(const hftt_clip_logmel_desc g, const hftt_warp_args wa, int nruns) {
   static_assert(NFFT == 2048, "the stage count below is for 1024 complex points");
   constexpr int N = NFFT / 2, Q = N / 4;              // complex points, butterflies per stage (= threads)
   __shared__ float2 bufA[N];
@@ -56,7 +60,14 @@ __global__ __launch_bounds__(256) void clip_logmel_kernel(const hftt_clip_logmel
     n = g.file_samp0[file + 1] - samp0;
     if (samp0 < 0 || n < 0 || samp0 + n > g.total_samples) n = -1;       // a table that leaves the corpus: nothing is read there
   }
-  const long nframe = n >= 0 ? 1 + n / hop : 0;
+  warp_win w = {};
+  long np = n;                                        // samples of the file as the frames see it
+  if constexpr (WARP) {
+    w = warp_load(wa, b);
+    if (!w.ok) n = -1;
+    np = n >= 0 ? warp_len(n, w) : -1;
+  }
+  const long nframe = n >= 0 ? 1 + np / hop : 0;
   const long t0 = (long)g.win_start[b] + c0;          // file frame of column c0
   const bool any = t0 < nframe && t0 + ncol > 0;      // (the same for every thread: the barriers below are met by all or by none)
   if (any) {
@@ -67,8 +78,9 @@ __global__ __launch_bounds__(256) void clip_logmel_kernel(const hftt_clip_logmel
     for (int j = tid; j < slen; j += 256) {
       const long i = i0 + j;
       float s = 0.f;                                  // outside [0, n): zeros, never a neighbouring file's samples
-      if (i >= 0 && i < n) {
-        s = g.wave_i16 ? (float)((const short*)g.wave)[samp0 + i] * (1.f / 32768.f) : ((const float*)g.wave)[samp0 + i];
+      if (i >= 0 && i < np) {
+        if constexpr (WARP) s = warp_sample(g.wave, g.wave_i16 != 0, samp0, n, np, wa.proto, w, i);
+        else s = g.wave_i16 ? (float)((const short*)g.wave)[samp0 + i] * (1.f / 32768.f) : ((const float*)g.wave)[samp0 + i];
         s = mix(s, g.gain != nullptr, gain, g.noise_std != nullptr, nstd, g.seed, (uint32_t)file, (uint64_t)i);
       }
       stage[j] = s;
@@ -146,8 +158,8 @@ __global__ __launch_bounds__(256) void clip_logmel_kernel(const hftt_clip_logmel
 
 }  // namespace
 
-extern "C" int hftt_clip_logmel(const hftt_clip_logmel_desc* d, void* stream) {
-  HFTT_REQUIRE(d, "clip_logmel: null descriptor");
+// the refusals of both entry points and the launch; wa == nullptr: the unwarped instantiation
+static int clip_logmel_launch(const hftt_clip_logmel_desc* d, const hftt_warp_args* wa, void* stream) {
   HFTT_REQUIRE(d->wave, "clip_logmel: wave is null");
   HFTT_REQUIRE(d->file_samp0, "clip_logmel: file_samp0 is null");
   HFTT_REQUIRE(d->win_file && d->win_start, "clip_logmel: null window table (win_file / win_start)");
@@ -161,9 +173,25 @@ extern "C" int hftt_clip_logmel(const hftt_clip_logmel_desc* d, void* stream) {
   HFTT_REQUIRE(d->hop >= 1, "clip_logmel: hop=%d must be positive", d->hop);
   HFTT_REQUIRE(d->n_files >= 1, "clip_logmel: n_files=%d must be positive", d->n_files);
   HFTT_REQUIRE(d->total_samples >= 0, "clip_logmel: total_samples=%ld is negative", (long)d->total_samples);
+  if (wa) {
+    HFTT_REQUIRE(wa->step_q24 && wa->delay_q24 && wa->cut && wa->proto, "clip_logmel: null warp table (step_q24 / delay_q24 / cut / proto)");
+    HFTT_REQUIRE(d->total_samples <= (1l << 38), "clip_logmel: total_samples=%ld beyond 2^38 (Q24 positions)", (long)d->total_samples);
+  }
   const long lds = ((long)(RUN - 1) * d->hop + d->n_fft) * 4;
   HFTT_REQUIRE(lds + STATIC_LDS <= 64 * 1024, "clip_logmel: hop=%d: the %d frames of a workgroup cover %ld samples, beyond 64 KB of LDS", d->hop, RUN, lds / 4);
   const int nruns = hftt_ceil_div(d->width, RUN);
   HFTT_REQUIRE((long)d->B * nruns < (1l << 31), "clip_logmel: B=%d windows of width=%d exceed 2^31 workgroups", d->B, d->width);
-  return hftt_launch<clip_logmel_kernel<2048>>("clip_logmel", dim3((unsigned)((long)d->B * nruns)), dim3(256), (int)lds, (hipStream_t)stream, *d, nruns);
+  const dim3 grid((unsigned)((long)d->B * nruns));
+  if (wa) return hftt_launch<clip_logmel_kernel<2048, true>>("clip_logmel_warp", grid, dim3(256), (int)lds, (hipStream_t)stream, *d, *wa, nruns);
+  return hftt_launch<clip_logmel_kernel<2048, false>>("clip_logmel", grid, dim3(256), (int)lds, (hipStream_t)stream, *d, hftt_warp_args{}, nruns);
+}
+
+extern "C" int hftt_clip_logmel(const hftt_clip_logmel_desc* d, void* stream) {
+  HFTT_REQUIRE(d, "clip_logmel: null descriptor");
+  return clip_logmel_launch(d, nullptr, stream);
+}
+
+extern "C" int hftt_clip_logmel_warp(const hftt_clip_logmel_warp_desc* d, void* stream) {
+  HFTT_REQUIRE(d, "clip_logmel: null descriptor");
+  return clip_logmel_launch(&d->base, &d->warp, stream);
 }

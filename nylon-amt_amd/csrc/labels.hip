@@ -1,7 +1,8 @@
 // Label rendering on the device (gfx950): note lists -> the frame labels that training consumes, the reference's corpus/conv_note2label.py:8-111
 // (note2label) restated per output element.  The reference walks the notes and paints frames; every rule it applies to a frame reads only that
 // frame's own state, so one thread can own frame f of one pitch and walk that pitch's notes in list order instead:
-//   hftt_labels_render  B windows [len frames] of a corpus-wide note table -> onset / offset / mpe / velocity [B, len, N], one launch
+//   hftt_labels_render       B windows [len frames] of a corpus-wide note table -> onset / offset / mpe / velocity [B, len, N], one launch
+//   hftt_labels_render_warp  the same under a per-window pitch shift and time map t' = (t + t_delay) * t_scale (the labels of a warped clip)
 // See include/hftt_hip.h for the contract.  One writer per element, no atomics; the survivors of the note filter keep their list order through a
 // prefix sum, so a result is bit-identical from launch to launch.
 #include <math.h>
@@ -34,9 +35,22 @@ struct survivors {
   int on_f[CH], off_f[CH], sharp[CH], vel[CH];   // sharp < 0: no offset target
 };
 
+// the per-window map of hftt_labels_render_warp (null pointers for hftt_labels_render, which never reads them)
+struct label_warp {
+  const int32_t* shift;
+  const double* t_delay;
+  const double* t_scale;
+  const double* file_end_sec;
+};
+
 // One workgroup per (pitch, chunk of CH frames, window), pitch fastest so that workgroups in flight together fill whole output rows.
+// Under a warp (lw.shift != nullptr: the same for every thread of the launch, so the branches below do not diverge and the unwarped launch
+// executes the operations it always did) output pitch j walks source pitch j - shift[b], every note time t is (t + t_delay[b]) * t_scale[b]
+// (two roundings: this file is compiled without contraction), and the file's frame count follows from its last offset under the same map.
+// The map is a launch argument, not a template parameter: both forms stay the two kernels whose registers and occupancy
+// tests/test_labels_capi.py pins.
 template <bool TRAIN>
-__global__ __launch_bounds__(CH) void labels_render_kernel(const hftt_labels_desc g, int nchunks) {
+__global__ __launch_bounds__(CH) void labels_render_kernel(const hftt_labels_desc g, const label_warp lw, int nchunks) {
   __shared__ survivors s;
   __shared__ int slot[4];
   __shared__ int total;
@@ -47,19 +61,33 @@ __global__ __launch_bounds__(CH) void labels_render_kernel(const hftt_labels_des
   const int t = k * CH + tid;                  // frame inside the window
   const int file = g.win_file[b];
   const bool known = file >= 0 && file < g.n_files;
-  const long nframe = known ? g.file_nframe[file] : 0;
+  const double hop_ms = g.hop_ms, fps = g.fps;
+  int jsrc = j;                                // the pitch whose notes this column shows
+  double t_delay = 0.0, t_scale = 1.0;
+  long nframe = 0;
+  const bool warp = lw.shift != nullptr;
+  if (warp) {
+    jsrc = j - lw.shift[b];
+    t_delay = lw.t_delay[b];
+    t_scale = lw.t_scale[b];
+    if (known) {
+      const bool empty = g.row_ptr[(long)file * N] == g.row_ptr[(long)file * N + N];
+      nframe = empty ? 1 : (long)frame_of((lw.file_end_sec[file] + t_delay) * t_scale, fps) + 1;
+    }
+  } else {
+    nframe = known ? g.file_nframe[file] : 0;
+  }
   const long f0 = (long)g.win_start[b] + (long)k * CH;           // file frame of thread 0; this workgroup renders [f0, f1)
   const long f1 = f0 + (g.len - k * CH < CH ? g.len - k * CH : CH);
   const long f = f0 + tid;
   const bool inside = t < g.len && f >= 0 && f < nframe;
   int beg = 0, end = 0;
-  if (known && f1 > 0 && f0 < nframe) {        // (the same for every thread: the barriers below are met by all or by none)
-    beg = g.row_ptr[(long)file * N + j];
-    end = g.row_ptr[(long)file * N + j + 1];
+  if (known && f1 > 0 && f0 < nframe && jsrc >= 0 && jsrc < N) {       // (the same for every thread: the barriers below are met by all or by none)
+    beg = g.row_ptr[(long)file * N + jsrc];
+    end = g.row_ptr[(long)file * N + jsrc + 1];
     beg = beg < 0 ? 0 : beg;
     end = end > g.n_notes ? g.n_notes : end;
   }
-  const double hop_ms = g.hop_ms, fps = g.fps;
   const int tol = g.tol;
   const double on_den = (double)tol * hop_ms;
   float o = 0.f, off = 0.f;
@@ -71,10 +99,15 @@ __global__ __launch_bounds__(CH) void labels_render_kernel(const hftt_labels_des
     int on_f = 0, off_f = 0, sharp = -1, v = 0;
     if (c0 + tid < end) {
       const hftt_label_note n = g.notes[c0 + tid];
-      on_f = frame_of(n.onset_sec, fps);
-      off_f = frame_of(n.offset_sec, fps);
-      on_ms = n.onset_sec * 1000.0;
-      off_ms = n.offset_sec * 1000.0;
+      double on_sec = n.onset_sec, off_sec = n.offset_sec;
+      if (warp) {
+        on_sec = (on_sec + t_delay) * t_scale;
+        off_sec = (off_sec + t_delay) * t_scale;
+      }
+      on_f = frame_of(on_sec, fps);
+      off_f = frame_of(off_sec, fps);
+      on_ms = on_sec * 1000.0;
+      off_ms = off_sec * 1000.0;
       v = n.velocity;
       long lo = (long)on_f - tol, hi = (long)on_f + tol;
       if (off_f > hi) hi = off_f;              // mpe: on_f .. off_f
@@ -128,8 +161,8 @@ __global__ __launch_bounds__(CH) void labels_render_kernel(const hftt_labels_des
 
 }  // namespace
 
-extern "C" int hftt_labels_render(const hftt_labels_desc* d, void* stream) {
-  HFTT_REQUIRE(d, "labels_render: null descriptor");
+// the refusals of both entry points and the launch; w == nullptr: no warp
+static int labels_launch(const hftt_labels_desc* d, const hftt_labels_warp_desc* w, void* stream) {
   HFTT_REQUIRE(d->n_files >= 1, "labels_render: n_files=%d must be positive", d->n_files);
   HFTT_REQUIRE(d->n_notes >= 0, "labels_render: n_notes=%d is negative", d->n_notes);
   HFTT_REQUIRE(d->B >= 1, "labels_render: B=%d must be positive", d->B);
@@ -141,14 +174,29 @@ extern "C" int hftt_labels_render(const hftt_labels_desc* d, void* stream) {
   HFTT_REQUIRE(d->form == HFTT_LABELS_TRAIN || d->form == HFTT_LABELS_STORE, "labels_render: form=%d (0 = train, 1 = store)", d->form);
   HFTT_REQUIRE(d->notes || d->n_notes == 0, "labels_render: notes is null at n_notes=%d", d->n_notes);
   HFTT_REQUIRE(d->row_ptr, "labels_render: row_ptr is null");
-  HFTT_REQUIRE(d->file_nframe, "labels_render: file_nframe is null");
+  HFTT_REQUIRE(w || d->file_nframe, "labels_render: file_nframe is null");
   HFTT_REQUIRE(d->win_file, "labels_render: win_file is null");
   HFTT_REQUIRE(d->win_start, "labels_render: win_start is null");
   HFTT_REQUIRE(d->onset && d->offset && d->mpe && d->velocity, "labels_render: null output (onset / offset / mpe / velocity)");
   HFTT_REQUIRE((long)d->B * d->len * d->N < (1l << 31), "labels_render: B=%d windows of len=%d frames and N=%d exceed 2^31 elements", d->B, d->len, d->N);
   const int nchunks = hftt_ceil_div(d->len, CH);
   const dim3 grid((unsigned)((long)d->B * nchunks * d->N));      // < 2^31: at most one workgroup per element
-  if (d->form == HFTT_LABELS_TRAIN)
-    return hftt_launch<labels_render_kernel<true>>("labels_render", grid, dim3(CH), 0, (hipStream_t)stream, *d, nchunks);
-  return hftt_launch<labels_render_kernel<false>>("labels_render", grid, dim3(CH), 0, (hipStream_t)stream, *d, nchunks);
+  label_warp lw = {};
+  if (w) {
+    HFTT_REQUIRE(w->shift && w->t_delay && w->t_scale && w->file_end_sec, "labels_render: null warp table (shift / t_delay / t_scale / file_end_sec)");
+    lw = {w->shift, w->t_delay, w->t_scale, w->file_end_sec};
+  }
+  const char* what = w ? "labels_render_warp" : "labels_render";
+  if (d->form == HFTT_LABELS_TRAIN) return hftt_launch<labels_render_kernel<true>>(what, grid, dim3(CH), 0, (hipStream_t)stream, *d, lw, nchunks);
+  return hftt_launch<labels_render_kernel<false>>(what, grid, dim3(CH), 0, (hipStream_t)stream, *d, lw, nchunks);
+}
+
+extern "C" int hftt_labels_render(const hftt_labels_desc* d, void* stream) {
+  HFTT_REQUIRE(d, "labels_render: null descriptor");
+  return labels_launch(d, nullptr, stream);
+}
+
+extern "C" int hftt_labels_render_warp(const hftt_labels_warp_desc* d, void* stream) {
+  HFTT_REQUIRE(d, "labels_render: null descriptor");
+  return labels_launch(&d->base, d, stream);
 }

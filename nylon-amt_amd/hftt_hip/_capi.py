@@ -218,6 +218,30 @@ class ClipLogmelDesc(C.Structure):
                 ('out', C.c_void_p)]
 
 
+WARP_ZEROS, WARP_TABLE_L = 6, 512           # HFTT_WARP_ZEROS, HFTT_WARP_TABLE_L
+WARP_TABLE_LEN = WARP_ZEROS * WARP_TABLE_L + 2                  # HFTT_WARP_TABLE_LEN
+WARP_STEP_MIN, WARP_STEP_MAX, WARP_DELAY_MAX = 1 << 23, 1 << 25, 1 << 48
+
+
+class WarpArgs(C.Structure):                # hftt_warp_args: one window's step, delay and cutoff, and the prototype table
+    _fields_ = [('step_q24', C.c_void_p), ('delay_q24', C.c_void_p), ('cut', c_f32p), ('proto', c_f32p)]
+
+
+class ClipLogmelWarpDesc(C.Structure):
+    _fields_ = [('base', ClipLogmelDesc), ('warp', WarpArgs)]
+
+
+class WaveWarpDesc(C.Structure):
+    _fields_ = [('wave', C.c_void_p), ('file_samp0', C.c_void_p), ('win_file', C.c_void_p), ('win_start', C.c_void_p),
+                ('total_samples', C.c_int64),
+                ('wave_i16', C.c_int32), ('n_files', C.c_int32), ('B', C.c_int32), ('len', C.c_int32),
+                ('warp', WarpArgs), ('out', C.c_void_p)]
+
+
+class LabelsWarpDesc(C.Structure):
+    _fields_ = [('base', LabelsDesc), ('shift', C.c_void_p), ('t_delay', C.c_void_p), ('t_scale', C.c_void_p), ('file_end_sec', C.c_void_p)]
+
+
 ADAM_MAX_GROUPS = 8                         # HFTT_ADAM_MAX_GROUPS
 
 
@@ -285,6 +309,9 @@ SIGNATURES = {
     'hftt_notes_decode_seg': (C.c_int, [C.POINTER(NotesSegDesc), C.c_void_p]),
     'hftt_labels_render': (C.c_int, [C.POINTER(LabelsDesc), C.c_void_p]),
     'hftt_clip_logmel': (C.c_int, [C.POINTER(ClipLogmelDesc), C.c_void_p]),
+    'hftt_clip_logmel_warp': (C.c_int, [C.POINTER(ClipLogmelWarpDesc), C.c_void_p]),
+    'hftt_wave_warp': (C.c_int, [C.POINTER(WaveWarpDesc), C.c_void_p]),
+    'hftt_labels_render_warp': (C.c_int, [C.POINTER(LabelsWarpDesc), C.c_void_p]),
     'hftt_grad_norm_ws_bytes': (C.c_int64, [C.c_int64]),
     'hftt_grad_norm': (C.c_int, [c_f32p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hftt_adam_step_guarded': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32,

@@ -10,7 +10,8 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry,
+from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelWarpDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
+                    WARP_TABLE_L, WARP_TABLE_LEN, WARP_ZEROS,
                     LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, STITCH_MAX_CLIPS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
                     ATTN_Q_F16PAIR, ATTN_KV_F16PAIR, check, lib)
@@ -876,12 +877,104 @@ class WaveTable:
         return sum(t.numel() * t.element_size() for t in (self.wave, self.file_samp0))
 
 
-def clip_logmel(table, logmel, win_file, win_start, width, fill, gain=None, noise_std=None, seed=0):
+def warp_table_host():
+    """the prototype of hftt_wave_warp's filter as fp32 [WARP_TABLE_LEN]: sinc(u) cos^2(pi u / 2Z) at u = e / L, e = 0 .. Z L, in fp64, rounded
+    once; the two entries behind u = Z are exact zeros"""
+    Z, L = WARP_ZEROS, WARP_TABLE_L
+    u = np.arange(WARP_TABLE_LEN, dtype=np.float64) / L
+    t = np.sinc(u) * np.cos(np.pi * u / (2 * Z)) ** 2
+    t[Z * L:] = 0.0
+    return t.astype(np.float32)
+
+
+class WarpTable:
+    """the prototype table of the warp kernels on one device (uploaded once)"""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.proto = torch.from_numpy(warp_table_host()).to(self.device)
+
+
+_WARP_TABLES = {}
+
+
+def warp_table(device):
+    """the WarpTable of `device`, built at the first call"""
+    key = str(torch.device(device))
+    if key not in _WARP_TABLES:
+        _WARP_TABLES[key] = WarpTable(device)
+    return _WARP_TABLES[key]
+
+
+class Warp:
+    """The warp of B windows as device tensors: step_q24 int32 [B] (rate * 2^24), delay_q24 int64 [B] (source samples * 2^24) and shift int32
+    [B] (semitones the labels move by; None = 0).  What the kernels take besides is derived here, on the device, and nowhere else:
+        cut      fp32   (float)(0.99 * min(1, 2^24 / step))          the quotient and the product in fp64, rounded once to fp32
+        t_scale  fp64   2^24 / step
+        t_delay  fp64   delay / 2^24 / sr                            (the first quotient is exact)"""
+
+    def __init__(self, step_q24, delay_q24, shift=None):
+        self.step_q24 = torch.as_tensor(step_q24).to(torch.int32).contiguous()
+        dev = self.step_q24.device
+        self.delay_q24 = torch.as_tensor(delay_q24, device=dev).to(torch.int64).contiguous()
+        self.shift = (torch.zeros_like(self.step_q24) if shift is None else torch.as_tensor(shift, device=dev).to(torch.int32).contiguous())
+        if self.step_q24.dim() != 1 or self.delay_q24.shape != self.step_q24.shape or self.shift.shape != self.step_q24.shape:
+            raise HfttError('Warp: step_q24, delay_q24 and shift must be [B]')
+
+    def cut(self):
+        return (0.99 * torch.clamp(float(1 << 24) / self.step_q24.double(), max=1.0)).float()
+
+    def t_scale(self):
+        return float(1 << 24) / self.step_q24.double()
+
+    def t_delay(self, sr):
+        return self.delay_q24.double() / float(1 << 24) / float(sr)
+
+    def _args(self, what, B, dev):
+        """(WarpArgs, the tensors it points to) for a launch on `dev` with B windows"""
+        if self.step_q24.device != dev or self.step_q24.numel() != B:
+            raise HfttError('%s: the warp holds %d windows on %s, the request %d on %s' % (what, self.step_q24.numel(), self.step_q24.device, B, dev))
+        _need_cuda(self.step_q24, self.delay_q24)
+        cut, proto = self.cut().contiguous(), warp_table(dev).proto
+        a = WarpArgs()
+        a.step_q24, a.delay_q24 = self.step_q24.data_ptr(), self.delay_q24.data_ptr()
+        a.cut, a.proto = cut.data_ptr(), proto.data_ptr()
+        return a, (cut, proto)
+
+
+def wave_warp(table, win_file, win_start, length, warp):
+    """B windows of `length` WARPED samples of a waveform corpus -> fp32 [B, length] in ONE launch (hftt_wave_warp): window b shows warped
+    samples win_start[b] .. + length (int64, counted from the warped file's sample 0) of file win_file[b] of `table` (a WaveTable) under
+    `warp` (a Warp), before gain and noise; zeros outside the warped file.  No CPU fallback."""
+    dev = table.device
+    win_file = torch.as_tensor(win_file, device=dev).to(torch.int32).contiguous()
+    win_start = torch.as_tensor(win_start, device=dev).to(torch.int64).contiguous()
+    if not isinstance(warp, Warp):
+        raise HfttError('wave_warp: warp must be an ops.Warp')
+    if win_file.dim() != 1 or win_start.shape != win_file.shape:
+        raise HfttError('wave_warp: win_file and win_start must be [B]')
+    B, length = win_file.numel(), int(length)
+    wa, keep = warp._args('wave_warp', B, dev)
+    _need_cuda(table.wave, table.file_samp0, win_file, win_start)
+    out = torch.empty((B, max(length, 0)), dtype=torch.float32, device=dev)
+    d = WaveWarpDesc()
+    d.wave, d.file_samp0, d.win_file, d.win_start = table.wave.data_ptr(), table.file_samp0.data_ptr(), win_file.data_ptr(), win_start.data_ptr()
+    d.total_samples, d.wave_i16, d.n_files, d.B, d.len = table.total_samples, int(table.dtype == 'int16'), table.n_files, B, length
+    d.warp, d.out = wa, out.data_ptr()
+    check(lib().hftt_wave_warp(C.byref(d), _stream(dev)), 'wave_warp')
+    return out
+
+
+def clip_logmel(table, logmel, win_file, win_start, width, fill, gain=None, noise_std=None, seed=0, warp=None):
     """B clip windows of a waveform corpus -> spec [B, n_mels, width] fp32 in ONE launch (hftt_clip_logmel): window b shows log-mel frames
     win_start[b] .. + width of file win_file[b] of `table` (a WaveTable), each frame computed from that file's samples alone with the device
     tables of `logmel` (an ops.LogMel); frames outside the file are `fill`.  gain / noise_std: fp32 [B] device tensors or None (per-window
-    gain factor; standard deviation of additive noise keyed on (seed, file, sample)).  Nothing is read back to the host."""
+    gain factor; standard deviation of additive noise keyed on (seed, file, sample)).  warp: an ops.Warp or None -- with one, the files are
+    played back at each window's rate and delay (hftt_clip_logmel_warp), win_start counts frames of the warped file and the noise is keyed on
+    the warped sample.  Nothing is read back to the host."""
     dev = table.device
+    if warp is not None and not isinstance(warp, Warp):
+        raise HfttError('clip_logmel: warp must be an ops.Warp')
     win_file = torch.as_tensor(win_file, device=dev).to(torch.int32).contiguous()
     win_start = torch.as_tensor(win_start, device=dev).to(torch.int32).contiguous()
     _need_cuda(table.wave, table.file_samp0, logmel.window, win_file, win_start)
@@ -909,6 +1002,12 @@ def clip_logmel(table, logmel, win_file, win_start, width, fill, gain=None, nois
     d.gain, d.noise_std = (t.data_ptr() if t is not None else None for t in aug)
     d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     d.out = out.data_ptr()
+    if warp is not None:
+        w = ClipLogmelWarpDesc()
+        w.base = d
+        w.warp, keep = warp._args('clip_logmel', B, dev)
+        check(lib().hftt_clip_logmel_warp(C.byref(w), _stream(dev)), 'clip_logmel_warp')
+        return out
     check(lib().hftt_clip_logmel(C.byref(d), _stream(dev)), 'clip_logmel')
     return out
 
@@ -930,7 +1029,9 @@ def labels_grid(config):
 def labels_table_host(notes_per_file, config):
     """The note table of hftt_labels_render as numpy arrays: notes_per_file = one note list per file (dicts with 'pitch', 'onset', 'offset' in
     seconds and 'velocity', as note2label takes them) -> dict(notes [n] LABEL_NOTE records grouped by (file, pitch) and inside a group in LIST
-    order, row_ptr int32 [n_files * N + 1], file_nframe int32 [n_files], N, hop_ms, fps, tol).  Raises HfttError for a note outside the
+    order, row_ptr int32 [n_files * N + 1], file_nframe int32 [n_files], N, hop_ms, fps, tol; for the warped render: file_end_sec fp64
+    [n_files] (the largest offset, 0 without notes), pitch_min / pitch_max int32 [n_files] (the lowest and highest sounding pitch index;
+    N - 1 and 0 for a file without notes: no shift moves anything out of range) and sr).  Raises HfttError for a note outside the
     reference's working domain (there it indexes out of range or overflows int8)."""
     cm = config['midi']
     N, note_min = int(cm['num_note']), int(cm['note_min'])
@@ -978,7 +1079,12 @@ def labels_table_host(notes_per_file, config):
     max_offset = np.zeros(n_files, np.float64)
     np.maximum.at(max_offset, file, offset)
     file_nframe = ((max_offset * fps + 0.5).astype(np.int64) + 1).astype(np.int32)      # conv_note2label.py:20-27
-    return {'notes': notes, 'row_ptr': row_ptr, 'file_nframe': file_nframe, 'N': N, 'hop_ms': hop_ms, 'fps': fps, 'tol': tol}
+    pidx = pitch.astype(np.int64) - note_min
+    pitch_min, pitch_max = np.full(n_files, N - 1, np.int64), np.zeros(n_files, np.int64)
+    np.minimum.at(pitch_min, file, pidx)
+    np.maximum.at(pitch_max, file, pidx)
+    return {'notes': notes, 'row_ptr': row_ptr, 'file_nframe': file_nframe, 'N': N, 'hop_ms': hop_ms, 'fps': fps, 'tol': tol,
+            'file_end_sec': max_offset, 'pitch_min': pitch_min.astype(np.int32), 'pitch_max': pitch_max.astype(np.int32), 'sr': config['feature']['sr']}
 
 
 class LabelsTable:
@@ -992,9 +1098,14 @@ class LabelsTable:
         self.notes = torch.from_numpy(np.ascontiguousarray(host['notes']).view(np.uint8).reshape(-1)).to(self.device)
         self.row_ptr = torch.from_numpy(host['row_ptr']).to(self.device)
         self.file_nframe = torch.from_numpy(host['file_nframe']).to(self.device)
+        # the warped render's per-file columns (a host table from before they existed renders unwarped only)
+        self.sr = host.get('sr')
+        self.file_end_sec, self.pitch_min, self.pitch_max = (torch.from_numpy(host[k]).to(self.device) if k in host else None
+                                                             for k in ('file_end_sec', 'pitch_min', 'pitch_max'))
 
     def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in (self.notes, self.row_ptr, self.file_nframe))
+        return sum(t.numel() * t.element_size() for t in (self.notes, self.row_ptr, self.file_nframe, self.file_end_sec, self.pitch_min, self.pitch_max)
+                   if t is not None)
 
 
 def labels_table(notes_per_file, config, device):
@@ -1002,14 +1113,21 @@ def labels_table(notes_per_file, config, device):
     return LabelsTable(labels_table_host(notes_per_file, config), device)
 
 
-def labels_render(table, win_file, win_start, length, form='train', duration_tolerance=False):
+def labels_render(table, win_file, win_start, length, form='train', duration_tolerance=False, warp=None):
     """B windows of `length` frames -> (onset, offset, mpe, velocity) [B, length, N] device tensors in ONE launch (hftt_labels_render).
     win_file / win_start: int32 [B] device tensors (file index; first frame counted from the file's frame 0, may be negative or behind the file:
     frames outside the file are zero) -- nothing is read back to the host.  form 'train': fp32, fp32, fp32, int64 (what engine.loss takes);
-    'store': fp32, fp32, bool, int8 (the dtypes of corpus.conv_note2label.note2label_arrays)."""
+    'store': fp32, fp32, bool, int8 (the dtypes of corpus.conv_note2label.note2label_arrays).  warp: an ops.Warp or None -- with one
+    (hftt_labels_render_warp) window b shows the labels of the file played back under it: pitches moved by shift[b], note times
+    (t + t_delay) * t_scale, win_start in frames of the warped file."""
     if form not in LABELS_FORM:
         raise HfttError('labels_render: form %r (train / store)' % (form,))
     dev = table.device
+    if warp is not None:
+        if not isinstance(warp, Warp):
+            raise HfttError('labels_render: warp must be an ops.Warp')
+        if table.file_end_sec is None or table.sr is None:
+            raise HfttError('labels_render: the note table carries no file_end_sec / sr (built before the warped render): rebuild it with labels_table_host')
     win_file = torch.as_tensor(win_file, device=dev).to(torch.int32).contiguous()
     win_start = torch.as_tensor(win_start, device=dev).to(torch.int32).contiguous()
     _need_cuda(table.notes, table.row_ptr, table.file_nframe, win_file, win_start)
@@ -1030,5 +1148,15 @@ def labels_render(table, win_file, win_start, length, form='train', duration_tol
     d.duration_tolerance, d.form = int(bool(duration_tolerance)), LABELS_FORM[form]
     d.hop_ms, d.fps = table.hop_ms, table.fps
     d.onset, d.offset, d.mpe, d.velocity = onset.data_ptr(), offset.data_ptr(), mpe.data_ptr(), velocity.data_ptr()
-    check(lib().hftt_labels_render(C.byref(d), _stream(dev)), 'labels_render')
+    if warp is not None:
+        if warp.step_q24.device != dev or warp.step_q24.numel() != B:
+            raise HfttError('labels_render: the warp holds %d windows on %s, the request %d on %s' % (warp.step_q24.numel(), warp.step_q24.device, B, dev))
+        t_delay, t_scale = warp.t_delay(table.sr).contiguous(), warp.t_scale().contiguous()
+        _need_cuda(warp.shift, t_delay, t_scale, table.file_end_sec)
+        w = LabelsWarpDesc()
+        w.base = d
+        w.shift, w.t_delay, w.t_scale, w.file_end_sec = warp.shift.data_ptr(), t_delay.data_ptr(), t_scale.data_ptr(), table.file_end_sec.data_ptr()
+        check(lib().hftt_labels_render_warp(C.byref(w), _stream(dev)), 'labels_render_warp')
+    else:
+        check(lib().hftt_labels_render(C.byref(d), _stream(dev)), 'labels_render')
     return onset, offset, (mpe if train else mpe.view(torch.bool)), velocity

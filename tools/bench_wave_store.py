@@ -7,7 +7,8 @@ hftt_labels_render) against the same clips from NoteClipStore (fp32 log-mel feat
 
 Corpus: `--files` synthetic minutes of corpus.synth_audio (pluck_notes / pluck_wave) at the paper clip geometry (128 frames + 2 x 32 margin,
 256 mel bins, 88 pitches); the note store's features are ops.LogMel of the same waveforms.  Three stores gather the SAME shuffled batches of
-`--batch` clips: the note store, the wave store without augmentation, the wave store with both augmentations (gain and noise drawn per clip).  A
+`--batch` clips: the note store, the wave store without augmentation, the wave store with gain and noise drawn per clip, and the wave store
+under the warp (pitch shift -2 .. 2 semitones, 20 cents detune, time offset: hftt_clip_logmel_warp + hftt_labels_render_warp, every clip warped).  A
 call is timed with one device event on each side, after a warm-up, the stores alternating; the median of `--calls` calls is reported.
 --step-ms: the benchmark's median step time on the same box (bench.py --gpus 1), to state the extra time of a batch as a share of a step."""
 import argparse, json, os, sys
@@ -50,11 +51,12 @@ def main():
     wstore = assemble_wave_store(waves, notes, config)
     new = WaveClipStore(wstore, config, dev, wave_dtype='int16')
     aug = WaveClipStore(wstore, config, dev, wave_dtype='int16', augment=WaveAugment(gain_db=(-6.0, 6.0), noise_dbfs=(-60.0, -40.0), seed=1))
-    assert len(old) == len(new) == len(aug)
+    warped = WaveClipStore(wstore, config, dev, wave_dtype='int16', augment=WaveAugment(pitch_semitones=(-2, 2), detune_cents=20.0, shift=True, seed=1))
+    assert len(old) == len(new) == len(aug) == len(warped)
     chunks = old.loader(args.batch, shuffle=True, seed=1, drop_last=True).chunks
     chunks = [c.to(dev) for c in chunks[:args.warmup + args.calls]]
     assert len(chunks) == args.warmup + args.calls, 'corpus too small for %d calls' % (args.warmup + args.calls)
-    t_old, t_new, t_aug, t_kernel = [], [], [], []
+    t_old, t_new, t_aug, t_kernel, t_warp, t_kernel_warp = [], [], [], [], [], []
     cin = config['input']
     width = cin['margin_b'] + cin['num_frame'] + cin['margin_f']
     for i, c in enumerate(chunks):
@@ -63,11 +65,14 @@ def main():
         ms_aug, _ = timed(lambda: aug.batch(c))
         file, start = new.clip_file[c], new.clip_frame[c] - cin['margin_b']
         ms_k, _ = timed(lambda: ops.clip_logmel(new.waves, new.logmel, file, start, width, new.fill))
+        ms_warp, _ = timed(lambda: warped.batch(c))
+        w = warped.augment.draw_warp(len(c), new.logmel.hop)         # (the kernel alone under a fresh draw; the source-frame window, which is as long)
+        ms_kw, _ = timed(lambda: ops.clip_logmel(new.waves, new.logmel, file, start, width, new.fill, warp=w))
         if i == 0:
             assert all(torch.equal(x, y) for x, y in zip(a[1:], b[1:])), 'the labels of the two stores disagree'
             worst = float((a[0] - b[0]).abs().max())            # int16 audio against fp32 audio: reported, the tests hold the kernel to fp64
         if i >= args.warmup:
-            t_old.append(ms_old); t_new.append(ms_new); t_aug.append(ms_aug); t_kernel.append(ms_k)
+            t_old.append(ms_old); t_new.append(ms_new); t_aug.append(ms_aug); t_kernel.append(ms_k); t_warp.append(ms_warp); t_kernel_warp.append(ms_kw)
     med = lambda v: float(np.median(v))
     p = lambda v: [float(np.percentile(v, 10)), float(np.percentile(v, 90))]
     frames = sum(f.shape[0] for f in feats)
@@ -75,8 +80,9 @@ def main():
            'device': torch.cuda.get_device_name(0), 'files': args.files, 'audio_frames': frames, 'samples': int(wstore['file_nsamp'].sum()), 'clips': len(old),
            'notes': int(new.table.n_notes), 'batch': args.batch, 'window_frames': width, 'mel_bins': config['feature']['mel_bins'], 'calls': args.calls, 'warmup': args.warmup,
            'note_store_batch_ms': med(t_old), 'wave_store_batch_ms': med(t_new), 'wave_store_augmented_batch_ms': med(t_aug), 'clip_logmel_call_ms': med(t_kernel),
+           'wave_store_warped_batch_ms': med(t_warp), 'clip_logmel_warp_call_ms': med(t_kernel_warp), 'extra_ms_per_batch_warped': med(t_warp) - med(t_new),
            'extra_ms_per_batch': med(t_new) - med(t_old), 'extra_ms_per_batch_augmented': med(t_aug) - med(t_old),
-           'spread_ms': {'note_store_p10_p90': p(t_old), 'wave_store_p10_p90': p(t_new), 'wave_store_augmented_p10_p90': p(t_aug)},
+           'spread_ms': {'note_store_p10_p90': p(t_old), 'wave_store_p10_p90': p(t_new), 'wave_store_augmented_p10_p90': p(t_aug), 'wave_store_warped_p10_p90': p(t_warp)},
            'first_batch_max_abs_spec_difference_int16_audio': worst,
            'note_store_resident_bytes': int(old.resident_bytes()), 'wave_store_resident_bytes': int(new.resident_bytes()),
            'note_store_bytes_per_frame': old.resident_bytes() / frames, 'wave_store_bytes_per_frame': new.resident_bytes() / frames}
@@ -84,6 +90,7 @@ def main():
         res['benchmark_step_ms_median'] = args.step_ms
         res['extra_share_of_step'] = res['extra_ms_per_batch'] / args.step_ms
         res['extra_share_of_step_augmented'] = res['extra_ms_per_batch_augmented'] / args.step_ms
+        res['extra_share_of_step_warped'] = res['extra_ms_per_batch_warped'] / args.step_ms
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as fh:
         json.dump(res, fh, indent=1)
