@@ -778,6 +778,68 @@ typedef struct {
 int hftt_labels_render_warp(const hftt_labels_warp_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Clip mixing (csrc/clip_logmel_kernel.h, csrc/clip_mix.hip, csrc/labels_walk.h, csrc/labels_mix.hip): two clips summed while the samples are
+ * staged, and the labels of the sum -- the one augmentation that changes the polyphony.  Three entry points ADDED at ABI 8; HFTT_ABI_VERSION
+ * stays 8 and every descriptor above keeps its layout and its results.
+ *
+ * Window b has its PRIMARY (win_file[b], win_start[b]) with its optional warp entry, exactly as above, and an optional PARTNER:
+ *     mix_file[b]   int32: an index outside 0 .. n_files (negative included), or a file that leaves the corpus, contributes nothing
+ *     mix_start[b]  int32: column c shows primary frame win_start[b] + c and partner frame mix_start[b] + c, each counted in its own (warped) file
+ *     mix_gain[b]   float
+ *     under the warp forms the partner's own step_q24 / delay_q24 / cut (a partner whose warp lies outside the ranges above contributes
+ *     nothing) and its own label map shift / t_delay / t_scale
+ *
+ * hftt_clip_logmel_mix / hftt_clip_logmel_mix_warp: hftt_clip_logmel / hftt_clip_logmel_warp (`base`, `warp`: outputs, fill rule, tile store and
+ * refusals as there) with the staged sample at primary position i, 0 <= i < n'_A (n' = n without a warp), formed as
+ *     s = sA;  s = fmul(s, gain[b]) when gain is given;  s = fadd(s, fmul(sB, mix_gain[b])) when the window has a partner;  then the noise term
+ *     as above, keyed on (seed, PRIMARY file, i)                              (one rounding per operation, never an fma)
+ * sB = the partner's (warped) sample at i + (mix_start[b] - win_start[b]) * hop (int64), zero outside [0, n'_B).  Outside [0, n'_A) the staged
+ * sample is zero: the partner is added ONTO the primary's extent, and which columns are `fill` follows the primary alone.  A window without a
+ * partner is bit-identical to hftt_clip_logmel[_warp].  In the warp form both sources go through the one warped-sample function; its identity
+ * bypass keeps an unwarped source exact.  The LDS arrays are hftt_clip_logmel's (the partner is added into the same staged slot), so hop 324
+ * is still admitted.  Also refused: null mix_file / mix_start / mix_gain; in the warp form a null table of either warp.
+ *
+ * hftt_labels_render_mix: hftt_labels_render (`base`) with either source optionally under a warp map (shift / t_delay / t_scale all set or all
+ * NULL for the primary; mix_shift / mix_t_delay / mix_t_scale likewise for the partner).  Cell (frame t of the window, pitch j):
+ *     walks the primary's group at frame f = win_start[b] + t exactly as hftt_labels_render[_warp] does; its notes count where 0 <= f < nframe_A
+ *     then walks the partner's group mix_file * N + (j - mix_shift[b]) at partner frame fB = mix_start[b] + t, CARRYING the same o, off, mpe,
+ *     vel -- the reference writes velocity from the combined onset track and a carried vel == 0 test, so two separate renders combined
+ *     afterwards are not this rule; the partner's notes count where 0 <= fB < nframe_B AND 0 <= f < a_frames[b]
+ * nframe of a source = file_nframe[file] without a map, the warped count of hftt_labels_render_warp with one.  a_frames[b] (int64) is the
+ * primary's AUDIO frame count 1 + n'_A / hop, formed by the caller on the device from the wave table and the warp (0 for a window without a
+ * valid primary): the audio of a partner shows wherever the primary has audio frames, also behind the primary's last note.  flags bit 0 stays a
+ * property of a note inside its own file.  The frame shift between the sources is an integer on purpose: seconds added to the partner's note
+ * times would move frame_of and the fp64 triangle by an ulp.  With no partner the four tracks are bit-identical to hftt_labels_render[_warp].
+ * Also refused: null mix_file / mix_start / a_frames; a warp map of which only a part is given; file_end_sec null with a map; file_nframe null
+ * while a source has no map.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {
+  const int32_t* mix_file; const int32_t* mix_start;             /* [B] */
+  const float* mix_gain;                                         /* [B] */
+} hftt_clip_mix_args;
+typedef struct {
+  hftt_clip_logmel_desc base;
+  hftt_clip_mix_args mix;
+} hftt_clip_logmel_mix_desc;
+int hftt_clip_logmel_mix(const hftt_clip_logmel_mix_desc* d, void* stream);
+typedef struct {
+  hftt_clip_logmel_desc base;
+  hftt_warp_args warp;                                           /* the primaries' */
+  hftt_clip_mix_args mix;
+  hftt_warp_args mix_warp;                                       /* the partners' */
+} hftt_clip_logmel_mix_warp_desc;
+int hftt_clip_logmel_mix_warp(const hftt_clip_logmel_mix_warp_desc* d, void* stream);
+typedef struct {
+  hftt_labels_desc base;
+  const int32_t* shift; const double* t_delay; const double* t_scale;                    /* [B]: the primaries' map, or all NULL */
+  const int32_t* mix_file; const int32_t* mix_start;                                     /* [B] */
+  const int32_t* mix_shift; const double* mix_t_delay; const double* mix_t_scale;        /* [B]: the partners' map, or all NULL */
+  const double* file_end_sec;                                                            /* [n_files]; NULL allowed without a map */
+  const int64_t* a_frames;                                                               /* [B] */
+} hftt_labels_mix_desc;
+int hftt_labels_render_mix(const hftt_labels_mix_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Guarded optimizer step (csrc/guard.hip): global-norm gradient clipping, a non-finite guard and decoupled weight decay around the fused
  * Adam.  Like the note decoder and the label renderer these entry points were ADDED at ABI 8 and HFTT_ABI_VERSION stays 8: nothing that an
  * ABI-8 caller binds changed (hftt_adam_step above is untouched and remains the default step); a caller that needs them looks the symbols up.

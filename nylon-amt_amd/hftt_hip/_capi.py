@@ -242,6 +242,25 @@ class LabelsWarpDesc(C.Structure):
     _fields_ = [('base', LabelsDesc), ('shift', C.c_void_p), ('t_delay', C.c_void_p), ('t_scale', C.c_void_p), ('file_end_sec', C.c_void_p)]
 
 
+class ClipMixArgs(C.Structure):             # hftt_clip_mix_args: one window's partner (file, first frame, gain)
+    _fields_ = [('mix_file', C.c_void_p), ('mix_start', C.c_void_p), ('mix_gain', c_f32p)]
+
+
+class ClipLogmelMixDesc(C.Structure):
+    _fields_ = [('base', ClipLogmelDesc), ('mix', ClipMixArgs)]
+
+
+class ClipLogmelMixWarpDesc(C.Structure):
+    _fields_ = [('base', ClipLogmelDesc), ('warp', WarpArgs), ('mix', ClipMixArgs), ('mix_warp', WarpArgs)]
+
+
+class LabelsMixDesc(C.Structure):
+    _fields_ = [('base', LabelsDesc), ('shift', C.c_void_p), ('t_delay', C.c_void_p), ('t_scale', C.c_void_p),
+                ('mix_file', C.c_void_p), ('mix_start', C.c_void_p),
+                ('mix_shift', C.c_void_p), ('mix_t_delay', C.c_void_p), ('mix_t_scale', C.c_void_p),
+                ('file_end_sec', C.c_void_p), ('a_frames', C.c_void_p)]
+
+
 ADAM_MAX_GROUPS = 8                         # HFTT_ADAM_MAX_GROUPS
 
 
@@ -312,6 +331,9 @@ SIGNATURES = {
     'hftt_clip_logmel_warp': (C.c_int, [C.POINTER(ClipLogmelWarpDesc), C.c_void_p]),
     'hftt_wave_warp': (C.c_int, [C.POINTER(WaveWarpDesc), C.c_void_p]),
     'hftt_labels_render_warp': (C.c_int, [C.POINTER(LabelsWarpDesc), C.c_void_p]),
+    'hftt_clip_logmel_mix': (C.c_int, [C.POINTER(ClipLogmelMixDesc), C.c_void_p]),
+    'hftt_clip_logmel_mix_warp': (C.c_int, [C.POINTER(ClipLogmelMixWarpDesc), C.c_void_p]),
+    'hftt_labels_render_mix': (C.c_int, [C.POINTER(LabelsMixDesc), C.c_void_p]),
     'hftt_grad_norm_ws_bytes': (C.c_int64, [C.c_int64]),
     'hftt_grad_norm': (C.c_int, [c_f32p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hftt_adam_step_guarded': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32,

@@ -10,8 +10,8 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelWarpDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
-                    WARP_TABLE_L, WARP_TABLE_LEN, WARP_ZEROS,
+from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
+                    WARP_DELAY_MAX, WARP_STEP_MAX, WARP_STEP_MIN, WARP_TABLE_L, WARP_TABLE_LEN, WARP_ZEROS,
                     LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, STITCH_MAX_CLIPS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
                     ATTN_Q_F16PAIR, ATTN_KV_F16PAIR, check, lib)
@@ -965,16 +965,67 @@ def wave_warp(table, win_file, win_start, length, warp):
     return out
 
 
-def clip_logmel(table, logmel, win_file, win_start, width, fill, gain=None, noise_std=None, seed=0, warp=None):
+class Mix:
+    """The PARTNERS of B windows (clip mixing) as device tensors: file int32 [B] (an index outside 0 .. n_files: the window has no partner),
+    start int32 [B] (the partner frame that column 0 shows, counted in the partner's own -- warped -- file), gain fp32 [B], and warp: the
+    partners' own ops.Warp or None (played back as they are)."""
+
+    def __init__(self, file, start, gain, warp=None):
+        if warp is not None and not isinstance(warp, Warp):
+            raise HfttError('Mix: warp must be an ops.Warp')
+        self.file = torch.as_tensor(file).to(torch.int32).contiguous()
+        dev = self.file.device
+        self.start = torch.as_tensor(start, device=dev).to(torch.int32).contiguous()
+        self.gain = torch.as_tensor(gain, device=dev).to(torch.float32).contiguous()
+        self.warp = warp
+        if self.file.dim() != 1 or self.start.shape != self.file.shape or self.gain.shape != self.file.shape:
+            raise HfttError('Mix: file, start and gain must be [B]')
+        if warp is not None and (warp.step_q24.shape != self.file.shape or warp.step_q24.device != dev):
+            raise HfttError('Mix: the warp holds %d windows on %s, the partners %d on %s' % (warp.step_q24.numel(), warp.step_q24.device, self.file.numel(), dev))
+
+    def _check(self, what, B, dev):
+        if self.file.device != dev or self.file.numel() != B:
+            raise HfttError('%s: the mix holds %d windows on %s, the request %d on %s' % (what, self.file.numel(), self.file.device, B, dev))
+        _need_cuda(self.file, self.start, self.gain)
+
+
+def _identity_warp(B, dev):
+    return Warp(torch.full((B,), 1 << 24, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int64, device=dev))
+
+
+def audio_frames(table, hop, win_file, warp=None):
+    """int64 [B] on the device: the AUDIO frame count 1 + n' / hop of each window's file of `table` (a WaveTable) as clip_logmel sees it -- n' the
+    file's samples, under `warp` (an ops.Warp or None) the warped file's -- and 0 for a window without a valid file or warp.  What
+    labels_render takes as a_frames next to a mix."""
+    dev = table.device
+    f = torch.as_tensor(win_file, device=dev).long()
+    ok = (f >= 0) & (f < table.n_files)
+    fc = f.clamp(0, table.n_files - 1)
+    n = table.file_samp0[fc + 1] - table.file_samp0[fc]
+    if warp is not None:
+        if not isinstance(warp, Warp):
+            raise HfttError('audio_frames: warp must be an ops.Warp')
+        step, delay, cut = warp.step_q24.long(), warp.delay_q24, warp.cut()
+        ok = ok & (step >= WARP_STEP_MIN) & (step <= WARP_STEP_MAX) & (delay >= 0) & (delay <= WARP_DELAY_MAX) & (cut >= 0.25) & (cut <= 1.0)
+        step = step.clamp(WARP_STEP_MIN, WARP_STEP_MAX)
+        n = torch.where(n > 0, (((n - 1) << 24) + delay) // step + 1, torch.zeros_like(n))
+    return torch.where(ok, 1 + n // int(hop), torch.zeros_like(n)).contiguous()
+
+
+def clip_logmel(table, logmel, win_file, win_start, width, fill, gain=None, noise_std=None, seed=0, warp=None, mix=None):
     """B clip windows of a waveform corpus -> spec [B, n_mels, width] fp32 in ONE launch (hftt_clip_logmel): window b shows log-mel frames
     win_start[b] .. + width of file win_file[b] of `table` (a WaveTable), each frame computed from that file's samples alone with the device
     tables of `logmel` (an ops.LogMel); frames outside the file are `fill`.  gain / noise_std: fp32 [B] device tensors or None (per-window
     gain factor; standard deviation of additive noise keyed on (seed, file, sample)).  warp: an ops.Warp or None -- with one, the files are
     played back at each window's rate and delay (hftt_clip_logmel_warp), win_start counts frames of the warped file and the noise is keyed on
-    the warped sample.  Nothing is read back to the host."""
+    the warped sample.  mix: an ops.Mix or None -- with one (hftt_clip_logmel_mix / _mix_warp) each window's partner is added onto the primary's
+    extent: gain * primary + mix.gain * partner, then the noise; a warp on either side takes both through the warped sample (the other side
+    under the identity, which is exact).  Nothing is read back to the host."""
     dev = table.device
     if warp is not None and not isinstance(warp, Warp):
         raise HfttError('clip_logmel: warp must be an ops.Warp')
+    if mix is not None and not isinstance(mix, Mix):
+        raise HfttError('clip_logmel: mix must be an ops.Mix')
     win_file = torch.as_tensor(win_file, device=dev).to(torch.int32).contiguous()
     win_start = torch.as_tensor(win_start, device=dev).to(torch.int32).contiguous()
     _need_cuda(table.wave, table.file_samp0, logmel.window, win_file, win_start)
@@ -1002,6 +1053,22 @@ def clip_logmel(table, logmel, win_file, win_start, width, fill, gain=None, nois
     d.gain, d.noise_std = (t.data_ptr() if t is not None else None for t in aug)
     d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     d.out = out.data_ptr()
+    if mix is not None:
+        mix._check('clip_logmel', B, dev)
+        ma = ClipMixArgs()
+        ma.mix_file, ma.mix_start, ma.mix_gain = mix.file.data_ptr(), mix.start.data_ptr(), mix.gain.data_ptr()
+        if warp is None and mix.warp is None:
+            m = ClipLogmelMixDesc()
+            m.base, m.mix = d, ma
+            check(lib().hftt_clip_logmel_mix(C.byref(m), _stream(dev)), 'clip_logmel_mix')
+            return out
+        wa, wb = warp or _identity_warp(B, dev), mix.warp or _identity_warp(B, dev)
+        m = ClipLogmelMixWarpDesc()
+        m.base, m.mix = d, ma
+        m.warp, keep_a = wa._args('clip_logmel', B, dev)
+        m.mix_warp, keep_b = wb._args('clip_logmel', B, dev)
+        check(lib().hftt_clip_logmel_mix_warp(C.byref(m), _stream(dev)), 'clip_logmel_mix_warp')
+        return out
     if warp is not None:
         w = ClipLogmelWarpDesc()
         w.base = d
@@ -1113,13 +1180,16 @@ def labels_table(notes_per_file, config, device):
     return LabelsTable(labels_table_host(notes_per_file, config), device)
 
 
-def labels_render(table, win_file, win_start, length, form='train', duration_tolerance=False, warp=None):
+def labels_render(table, win_file, win_start, length, form='train', duration_tolerance=False, warp=None, mix=None, a_frames=None):
     """B windows of `length` frames -> (onset, offset, mpe, velocity) [B, length, N] device tensors in ONE launch (hftt_labels_render).
     win_file / win_start: int32 [B] device tensors (file index; first frame counted from the file's frame 0, may be negative or behind the file:
     frames outside the file are zero) -- nothing is read back to the host.  form 'train': fp32, fp32, fp32, int64 (what engine.loss takes);
     'store': fp32, fp32, bool, int8 (the dtypes of corpus.conv_note2label.note2label_arrays).  warp: an ops.Warp or None -- with one
     (hftt_labels_render_warp) window b shows the labels of the file played back under it: pitches moved by shift[b], note times
-    (t + t_delay) * t_scale, win_start in frames of the warped file."""
+    (t + t_delay) * t_scale, win_start in frames of the warped file.  mix: an ops.Mix or None -- with one (hftt_labels_render_mix) each cell
+    walks the partner's notes (under mix.warp's map, if any) behind the primary's with the same carried state: the labels of the summed
+    audio; a_frames: int64 [B] device tensor, the primaries' audio frame counts (ops.audio_frames), required with a mix -- the partner's
+    notes show only where the primary has audio.  mix.gain is not read."""
     if form not in LABELS_FORM:
         raise HfttError('labels_render: form %r (train / store)' % (form,))
     dev = table.device
@@ -1127,6 +1197,13 @@ def labels_render(table, win_file, win_start, length, form='train', duration_tol
         if not isinstance(warp, Warp):
             raise HfttError('labels_render: warp must be an ops.Warp')
         if table.file_end_sec is None or table.sr is None:
+            raise HfttError('labels_render: the note table carries no file_end_sec / sr (built before the warped render): rebuild it with labels_table_host')
+    if mix is not None:
+        if not isinstance(mix, Mix):
+            raise HfttError('labels_render: mix must be an ops.Mix')
+        if a_frames is None:
+            raise HfttError('labels_render: a mix needs a_frames (the primaries\' audio frame counts: ops.audio_frames)')
+        if mix.warp is not None and (table.file_end_sec is None or table.sr is None):
             raise HfttError('labels_render: the note table carries no file_end_sec / sr (built before the warped render): rebuild it with labels_table_host')
     win_file = torch.as_tensor(win_file, device=dev).to(torch.int32).contiguous()
     win_start = torch.as_tensor(win_start, device=dev).to(torch.int32).contiguous()
@@ -1148,7 +1225,29 @@ def labels_render(table, win_file, win_start, length, form='train', duration_tol
     d.duration_tolerance, d.form = int(bool(duration_tolerance)), LABELS_FORM[form]
     d.hop_ms, d.fps = table.hop_ms, table.fps
     d.onset, d.offset, d.mpe, d.velocity = onset.data_ptr(), offset.data_ptr(), mpe.data_ptr(), velocity.data_ptr()
-    if warp is not None:
+    if mix is not None:
+        mix._check('labels_render', B, dev)
+        a_frames = torch.as_tensor(a_frames, device=dev).to(torch.int64).contiguous()
+        _need_cuda(a_frames)
+        if a_frames.shape != win_file.shape:
+            raise HfttError('labels_render: a_frames must be [B]')
+        m = LabelsMixDesc()
+        m.base = d
+        keep = []
+        for w, names in ((warp, ('shift', 't_delay', 't_scale')), (mix.warp, ('mix_shift', 'mix_t_delay', 'mix_t_scale'))):
+            if w is None:
+                continue
+            if w.step_q24.device != dev or w.step_q24.numel() != B:
+                raise HfttError('labels_render: the warp holds %d windows on %s, the request %d on %s' % (w.step_q24.numel(), w.step_q24.device, B, dev))
+            ts = (w.shift, w.t_delay(table.sr).contiguous(), w.t_scale().contiguous())
+            _need_cuda(*ts, table.file_end_sec)
+            keep.append(ts)
+            for name, t in zip(names, ts):
+                setattr(m, name, t.data_ptr())
+            m.file_end_sec = table.file_end_sec.data_ptr()
+        m.mix_file, m.mix_start, m.a_frames = mix.file.data_ptr(), mix.start.data_ptr(), a_frames.data_ptr()
+        check(lib().hftt_labels_render_mix(C.byref(m), _stream(dev)), 'labels_render_mix')
+    elif warp is not None:
         if warp.step_q24.device != dev or warp.step_q24.numel() != B:
             raise HfttError('labels_render: the warp holds %d windows on %s, the request %d on %s' % (warp.step_q24.numel(), warp.step_q24.device, B, dev))
         t_delay, t_scale = warp.t_delay(table.sr).contiguous(), warp.t_scale().contiguous()

@@ -10,7 +10,14 @@ Corpus: `--files` synthetic minutes of corpus.synth_audio (pluck_notes / pluck_w
 `--batch` clips: the note store, the wave store without augmentation, the wave store with gain and noise drawn per clip, and the wave store
 under the warp (pitch shift -2 .. 2 semitones, 20 cents detune, time offset: hftt_clip_logmel_warp + hftt_labels_render_warp, every clip warped).  A
 call is timed with one device event on each side, after a warm-up, the stores alternating; the median of `--calls` calls is reported.
---step-ms: the benchmark's median step time on the same box (bench.py --gpus 1), to state the extra time of a batch as a share of a step."""
+--step-ms: the benchmark's median step time on the same box (bench.py --gpus 1), to state the extra time of a batch as a share of a step.
+
+  python tools/bench_wave_store.py --mix-out profiles/clip_mix.json
+
+The mixed leg (clip mixing: hftt_clip_logmel_mix[_warp] + hftt_labels_render_mix): WaveClipStore.batch with mix_p 0, 0.5 and 1, without and with
+the warp above, on the same batches.  `--mix-repeats` repeats, the six stores interleaved inside each (the order rotates); a repeat's figure
+is the median of `--mix-calls` calls, the reported figure the median of the repeats, next to every repeat's.  mix_p = 0 is the un-mixed
+leg the others are read against.  Measured, no threshold."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'nylon-amt_amd'))
@@ -31,6 +38,73 @@ def timed(fn):
     return a.elapsed_time(b), out
 
 
+def mixed_leg(wstore, config, dev, chunks, repeats=5, calls=60, warmup=10, mix_ps=(0.0, 0.5, 1.0)):
+    """{leg: {'ms': median over the repeats, 'repeats': [...]}} for mix_p x (plain, warped); the legs interleaved inside every repeat"""
+    legs = {}
+    for warp in (False, True):
+        for p in mix_ps:
+            kw = dict(seed=1)
+            if warp:
+                kw.update(pitch_semitones=(-2, 2), detune_cents=20.0, shift=True)
+            if p > 0.0:
+                kw.update(mix_p=p)
+            aug = WaveAugment(**kw) if (warp or p > 0.0) else None
+            legs['mix_p_%g%s' % (p, '_warped' if warp else '')] = WaveClipStore(wstore, config, dev, wave_dtype='int16', augment=aug)
+    names = list(legs)
+    assert len(chunks) >= warmup + calls, 'corpus too small for %d calls' % (warmup + calls)
+    per = {n: [] for n in names}
+    for r in range(repeats):
+        t = {n: [] for n in names}
+        for i, c in enumerate(chunks[:warmup + calls]):
+            for n in names[r % len(names):] + names[:r % len(names)]:
+                ms, _ = timed(lambda: legs[n].batch(c))
+                if i >= warmup:
+                    t[n].append(ms)
+        for n in names:
+            per[n].append(float(np.median(t[n])))
+    out = {n: {'ms': float(np.median(v)), 'repeats': v} for n, v in per.items()}
+    if len(mix_ps) > 1:
+        out['calls'] = mixed_calls(legs['mix_p_%g' % mix_ps[-1]], legs['mix_p_%g_warped' % mix_ps[-1]], chunks, repeats, calls, warmup)
+    for warp in ('', '_warped'):
+        base = out['mix_p_0' + warp]['ms']
+        for p in mix_ps[1:]:
+            out['mix_p_%g%s' % (p, warp)]['extra_ms_over_unmixed'] = out['mix_p_%g%s' % (p, warp)]['ms'] - base
+    return out
+
+
+def mixed_calls(store, warped, chunks, repeats, calls, warmup):
+    """the two launches alone (through their ops wrappers, which derive cut / t_scale / t_delay), with and without a partner for every window,
+    under draws made beforehand: {call: median over the repeats of the median ms}"""
+    c = chunks[0]
+    B = len(c)
+    file, frame = store.clip_file[c], store.clip_frame[c]
+    on, partner, gain = store.augment.draw_mix(B, len(store))
+    pfile, pframe = store.clip_file[partner], store.clip_frame[partner]
+    w, pw = warped._draw_warp(file), warped._draw_warp(pfile)
+    width, mb = store.mb + store.T + store.mf, store.mb
+    af, afw = ops.audio_frames(store.waves, store.logmel.hop, file), ops.audio_frames(store.waves, store.logmel.hop, file, w)
+    mix = lambda off, pwarp: ops.Mix(pfile, pframe - off, gain, pwarp)
+    fns = {'clip_logmel': lambda: ops.clip_logmel(store.waves, store.logmel, file, frame - mb, width, store.fill),
+           'clip_logmel_mix': lambda: ops.clip_logmel(store.waves, store.logmel, file, frame - mb, width, store.fill, mix=mix(mb, None)),
+           'clip_logmel_warp': lambda: ops.clip_logmel(store.waves, store.logmel, file, frame - mb, width, store.fill, warp=w),
+           'clip_logmel_mix_warp': lambda: ops.clip_logmel(store.waves, store.logmel, file, frame - mb, width, store.fill, warp=w, mix=mix(mb, pw)),
+           'labels_render': lambda: ops.labels_render(store.table, file, frame, store.T),
+           'labels_render_mix': lambda: ops.labels_render(store.table, file, frame, store.T, mix=mix(0, None), a_frames=af),
+           'labels_render_warp': lambda: ops.labels_render(store.table, file, frame, store.T, warp=w),
+           'labels_render_mix_warp': lambda: ops.labels_render(store.table, file, frame, store.T, warp=w, mix=mix(0, pw), a_frames=afw)}
+    per = {n: [] for n in fns}
+    for r in range(repeats):
+        t = {n: [] for n in fns}
+        for i in range(warmup + calls):
+            for n, fn in fns.items():
+                ms, _ = timed(fn)
+                if i >= warmup:
+                    t[n].append(ms)
+        for n in fns:
+            per[n].append(float(np.median(t[n])))
+    return {n: float(np.median(v)) for n, v in per.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--files', type=int, default=2, help='synthetic one-minute files')
@@ -39,11 +113,31 @@ def main():
     ap.add_argument('--warmup', type=int, default=30)
     ap.add_argument('--step-ms', type=float, default=0.0)
     ap.add_argument('--out', default='profiles/wave_store.json')
+    ap.add_argument('--mix-out', default='', help='run the mixed leg alone and write it here')
+    ap.add_argument('--mix-repeats', type=int, default=5)
+    ap.add_argument('--mix-calls', type=int, default=60)
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     config = finalize_config(prepare_config(SA.default_config()))
     notes = [SA.pluck_notes(2000 + i) for i in range(args.files)]
     waves = [SA.pluck_wave(a, device=dev) for a in notes]
+    if args.mix_out:
+        wstore = assemble_wave_store([w.cpu().numpy() for w in waves], notes, config)
+        n = len(wstore['clip_file'])
+        g = torch.Generator().manual_seed(1)
+        ids = torch.randperm(n, generator=g)
+        chunks = [ids[i:i + args.batch].to(dev) for i in range(0, n - args.batch + 1, args.batch)]
+        cin = config['input']
+        res = {'what': 'WaveClipStore.batch under clip mixing (mix_p 0 / 0.5 / 1, plain and warped): device events around each call; per repeat the median of the calls, reported the median of the repeats',
+               'device': torch.cuda.get_device_name(0), 'files': args.files, 'clips': n, 'batch': args.batch, 'window_frames': cin['margin_b'] + cin['num_frame'] + cin['margin_f'],
+               'mel_bins': config['feature']['mel_bins'], 'repeats': args.mix_repeats, 'calls': args.mix_calls, 'warmup': 10,
+               'legs': mixed_leg(wstore, config, dev, chunks, args.mix_repeats, args.mix_calls, 10)}
+        os.makedirs(os.path.dirname(os.path.abspath(args.mix_out)), exist_ok=True)
+        with open(args.mix_out, 'w') as fh:
+            json.dump(res, fh, indent=1)
+            fh.write('\n')
+        print(json.dumps(res))
+        return
     lm = ops.LogMel(dev)
     feats = [lm(w).cpu().numpy() for w in waves]
     waves = [w.cpu().numpy() for w in waves]

@@ -9,7 +9,8 @@ store (corpus.make_dataset.assemble_store) resident in HBM (training.dataset.Dev
 instead of the label tracks (assemble_note_store, NoteClipStore) and every batch's labels are rendered on the device; with --wave-store it keeps the
 WAVEFORMS (int16) and the notes (assemble_wave_store, WaveClipStore): no feature pass, every batch's log-mel windows are computed on the device,
 optionally under --aug-gain-db LO HI / --aug-noise-dbfs LO HI (per-clip gain and additive noise, new for every batch) and --aug-pitch LO HI /
---aug-detune-cents C / --aug-shift / --aug-warp-p P (per-clip pitch shift, detune and time offset: the clip is resampled and its labels move with it).  Training: the product's own step
+--aug-detune-cents C / --aug-shift / --aug-warp-p P (per-clip pitch shift, detune and time offset: the clip is resampled and its labels move with it)
+and --aug-mix-p P / --aug-mix-gain-db LO HI (clip mixing: a second clip summed in, the labels those of the sum).  Training: the product's own step
 (hftt_hip.trainer.TrainStep: forward + fused loss + backward + fused Adam) in the chosen precision mode, dropout 0.1, batch 8, until the
 time budget is spent.  The model is pickled the way m_training.py:372-373 does it (whole module, protocol 4).
 
@@ -199,6 +200,8 @@ def main():
     ap.add_argument('--aug-detune-cents', type=float, default=0.0, metavar='C', help='with --wave-store: per-clip detune, uniform in +-C cents (C <= 50)')
     ap.add_argument('--aug-shift', action='store_true', help='with --wave-store: per-clip time offset, uniform in [0, hop) samples')
     ap.add_argument('--aug-warp-p', type=float, default=1.0, metavar='P', help='probability that a clip is warped at all (pitch, detune, shift)')
+    ap.add_argument('--aug-mix-p', type=float, default=0.0, metavar='P', help='with --wave-store: probability that a clip is summed with another clip of the corpus (the labels are those of the sum)')
+    ap.add_argument('--aug-mix-gain-db', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --aug-mix-p: the partner clip\'s gain, uniform in dB (default -6 0)')
     ap.add_argument('--out', default='gpurun_out/config5_tiny.pkl')
     ap.add_argument('--score-only', default='', help='skip training: score this pickled model')
     ap.add_argument('--init', default='', help='start from this pickled model (weights only: the optimizer state starts afresh) -- chains runs that are each bounded by the GPU call limit')
@@ -212,6 +215,9 @@ def main():
     warp_aug = args.aug_pitch is not None or args.aug_detune_cents != 0.0 or args.aug_shift or args.aug_warp_p != 1.0
     if warp_aug and not args.wave_store:
         ap.error('--aug-pitch / --aug-detune-cents / --aug-shift / --aug-warp-p act on the waveform: they need --wave-store')
+    mix_aug = args.aug_mix_p != 0.0 or args.aug_mix_gain_db is not None
+    if mix_aug and not args.wave_store:
+        ap.error('--aug-mix-p / --aug-mix-gain-db act on the waveform: they need --wave-store')
     if args.freeze and not args.init:
         ap.error('--freeze keeps pretrained weights fixed: it needs --init')
     groups = None
@@ -236,13 +242,15 @@ def main():
         if (args.aug_gain_db or args.aug_noise_dbfs) and not args.wave_store:
             ap.error('--aug-gain-db / --aug-noise-dbfs act on the waveform: they need --wave-store')
         augment = None
-        if args.aug_gain_db or args.aug_noise_dbfs or warp_aug:
+        if args.aug_gain_db or args.aug_noise_dbfs or warp_aug or mix_aug:
             augment = WaveAugment(gain_db=args.aug_gain_db, noise_dbfs=args.aug_noise_dbfs, seed=args.seed, pitch_semitones=args.aug_pitch,
-                                  detune_cents=args.aug_detune_cents, shift=args.aug_shift, p_warp=args.aug_warp_p)
+                                  detune_cents=args.aug_detune_cents, shift=args.aug_shift, p_warp=args.aug_warp_p, mix_p=args.aug_mix_p,
+                                  mix_gain_db=args.aug_mix_gain_db or (-6.0, 0.0))
         clips, log['corpus'] = build_corpus(config, args.files, dev, note_store=args.note_store, wave_store=args.wave_store, augment=augment)
         if args.wave_store:
             log['augment'] = {'gain_db': args.aug_gain_db, 'noise_dbfs': args.aug_noise_dbfs, 'pitch_semitones': args.aug_pitch,
-                              'detune_cents': args.aug_detune_cents, 'shift': args.aug_shift, 'p_warp': args.aug_warp_p}
+                              'detune_cents': args.aug_detune_cents, 'shift': args.aug_shift, 'p_warp': args.aug_warp_p,
+                              'mix_p': args.aug_mix_p, 'mix_gain_db': args.aug_mix_gain_db}
         # ---- training ----
         model = model.to(dev)
         saver = None
