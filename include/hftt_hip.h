@@ -778,7 +778,7 @@ typedef struct {
 int hftt_labels_render_warp(const hftt_labels_warp_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Clip mixing (csrc/clip_logmel_kernel.h, csrc/clip_mix.hip, csrc/labels_walk.h, csrc/labels_mix.hip): two clips summed while the samples are
+ * Clip mixing (csrc/clip_logmel.hip, csrc/labels.hip): two clips summed while the samples are
  * staged, and the labels of the sum -- the one augmentation that changes the polyphony.  Three entry points ADDED at ABI 8; HFTT_ABI_VERSION
  * stays 8 and every descriptor above keeps its layout and its results.
  *

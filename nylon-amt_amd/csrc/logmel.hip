@@ -4,22 +4,17 @@
 // Replaces torchaudio MelSpectrogram + log of AMT.wav2feature (model/amt.py:59-61); see include/hftt_hip.h.
 #include "hftt_common.h"
 #include "hftt_launch.h"
+#include "logmel_frame.h"
 #include "../../include/hftt_hip.h"
 
 namespace {
 
-// Round 6: the frame is REAL, so its 2048-point transform is one 1024-point COMPLEX transform of z[n] = x[2n] + i x[2n+1] plus a pass that
-// separates the spectra of the even and odd samples (X[k] = E[k] + W^k O[k], E / O from Z[k] and conj(Z[N/2 - k])): half the butterflies.
-// The 1024-point transform is radix-4 Stockham (autosort: natural order in, natural order out, no bit-reversal pass): 5 stages of ONE
-// butterfly per thread and one barrier each (the round-1 kernel ran 11 radix-2 stages of four butterflies per thread on 2048 complex points
-// with a zero imaginary half).  Points live in LDS as interleaved (re, im) pairs: a stage READS x[j + q N/4] -- consecutive lanes,
-// consecutive 8-byte words: conflict-free -- and writes its four results Ns apart (stride-4 Ns writes: 4-way conflicts in the first three
-// stages, none in the last two; 15 of the kernel's ~60 LDS instructions per thread).  Twiddles come from the table the host already passes
-// (cos / sin of 2 pi k / 2048, k < 1024; the second half turn is a sign).
+// The frame is real: its 2048-point transform is one 1024-point complex radix-4 Stockham transform of the packed frame plus a split pass
+// (logmel_frame.h: frame_stage and frame_split, written once for this kernel and clip_logmel_kernel).  Here: the frame's start, the packing
+// -- global loads, each slot with its own bounds test --, the loop over the stages and the store of one mel row per thread and pass.
 template <int NFFT>
 __global__ __launch_bounds__(256) void logmel_kernel(const hftt_logmel_desc g) {
-  static_assert(NFFT == 2048, "the stage count below is for 1024 complex points");
-  constexpr int N = NFFT / 2, Q = N / 4;              // complex points, butterflies per stage (= threads)
+  constexpr int N = NFFT / 2;                         // complex points
   __shared__ float2 bufA[N];
   __shared__ float2 bufB[N];
   __shared__ float pw[N + 1];
@@ -28,12 +23,6 @@ __global__ __launch_bounds__(256) void logmel_kernel(const hftt_logmel_desc g) {
   const long start = frame * g.hop - NFFT / 2;
   const float* tc = g.twiddle;
   const float* ts = g.twiddle + NFFT / 2;
-  auto tw = [&](int m) {                              // e^(-2 pi i m / 2048), 0 <= m < 2048
-    const int mm = m & (NFFT / 2 - 1);
-    const float c = tc[mm], sn = ts[mm];
-    return (m & (NFFT / 2)) ? make_float2(-c, sn) : make_float2(c, -sn);
-  };
-  auto cmul = [](float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); };
 #pragma unroll
   for (int u = 0; u < N / 256; u++) {
     const int n = tid + 256 * u;
@@ -47,36 +36,12 @@ __global__ __launch_bounds__(256) void logmel_kernel(const hftt_logmel_desc g) {
   float2* dst = bufB;
 #pragma unroll
   for (int Ns = 1; Ns < N; Ns *= 4) {
-    const int j = tid, k = j & (Ns - 1);
-    const int step = NFFT / (4 * Ns);                 // twiddle index of exp(-2 pi i k / (4 Ns)) per unit k
-    float2 v0 = src[j], v1 = src[j + Q], v2 = src[j + 2 * Q], v3 = src[j + 3 * Q];
-    if (Ns > 1) { v1 = cmul(v1, tw(k * step)); v2 = cmul(v2, tw(2 * k * step)); v3 = cmul(v3, tw(3 * k * step)); }
-    const float2 a02 = make_float2(v0.x + v2.x, v0.y + v2.y), s02 = make_float2(v0.x - v2.x, v0.y - v2.y);
-    const float2 a13 = make_float2(v1.x + v3.x, v1.y + v3.y), s13 = make_float2(v1.x - v3.x, v1.y - v3.y);
-    const int j0 = ((j - k) << 2) + k;                // (j / Ns) * 4 Ns + k
-    dst[j0] = make_float2(a02.x + a13.x, a02.y + a13.y);
-    dst[j0 + Ns] = make_float2(s02.x + s13.y, s02.y - s13.x);          // v0 - i v1 - v2 + i v3
-    dst[j0 + 2 * Ns] = make_float2(a02.x - a13.x, a02.y - a13.y);
-    dst[j0 + 3 * Ns] = make_float2(s02.x - s13.y, s02.y + s13.x);      // v0 + i v1 - v2 - i v3
-    __syncthreads();
-    float2* t = src; src = dst; dst = t;
+    frame_stage<NFFT>(src, dst, Ns, tc, ts, tid);
+    float2* sw = src; src = dst; dst = sw;
   }
-  // real spectrum: E = (Z[k] + conj Z[N-k]) / 2, O = (Z[k] - conj Z[N-k]) / (2i), X[k] = E + W^k O, k = 0 .. N (Z[N] = Z[0]); |X|^2
-  for (int k = tid; k <= N; k += 256) {
-    const float2 zk = src[k & (N - 1)], zn = src[(N - k) & (N - 1)];
-    const float2 e = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
-    const float2 o = make_float2(0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x));
-    const float2 wo = cmul(o, tw(k));
-    const float xr = e.x + wo.x, xi = e.y + wo.y;
-    pw[k] = xr * xr + xi * xi;
-  }
-  __syncthreads();
-  for (int m = tid; m < g.n_mels; m += 256) {
-    const int st = g.fb_start[m], len = g.fb_len[m], off = g.fb_off[m];
-    float acc = 0.f;
-    for (int j = 0; j < len; j++) acc += g.fb_w[off + j] * pw[st + j];
-    g.feat[frame * g.n_mels + m] = logf(acc + g.log_offset);
-  }
+  frame_split<NFFT>(src, pw, tc, ts, tid);
+  for (int m = tid; m < g.n_mels; m += 256)
+    g.feat[frame * g.n_mels + m] = frame_mel(g.fb_w, pw, g.fb_start[m], g.fb_len[m], g.fb_off[m], g.log_offset);
 }
 
 // Polyphase band-limited resampling (the convolution of torchaudio.transforms.Resample, model/amt.py:57-58): output sample f * new + p is the

@@ -1,5 +1,5 @@
 // The warped sample (gfx950): one window's warp and the Hann-windowed sinc that reads a resident waveform at pos = j * step - delay (Q24).
-// ONE device function, called by the staging loop of clip_logmel_kernel (clip_logmel_kernel.h: for the primary and, under clip mixing, the
+// ONE device function, called by the staging loop of clip_logmel_kernel (clip_logmel.hip: for the primary and, under clip mixing, the
 // partner) and by wave_warp_kernel (wave_warp.hip): what the log-mel sees is what hftt_wave_warp writes.  See include/hftt_hip.h for the
 // contract; every operation and its order is stated there.
 #pragma once

@@ -930,16 +930,26 @@ class Warp:
     def t_delay(self, sr):
         return self.delay_q24.double() / float(1 << 24) / float(sr)
 
-    def _args(self, what, B, dev):
-        """(WarpArgs, the tensors it points to) for a launch on `dev` with B windows"""
+    def _holds(self, what, B, dev):
         if self.step_q24.device != dev or self.step_q24.numel() != B:
             raise HfttError('%s: the warp holds %d windows on %s, the request %d on %s' % (what, self.step_q24.numel(), self.step_q24.device, B, dev))
+
+    def _args(self, what, B, dev):
+        """(WarpArgs, the tensors it points to) for a launch on `dev` with B windows"""
+        self._holds(what, B, dev)
         _need_cuda(self.step_q24, self.delay_q24)
         cut, proto = self.cut().contiguous(), warp_table(dev).proto
         a = WarpArgs()
         a.step_q24, a.delay_q24 = self.step_q24.data_ptr(), self.delay_q24.data_ptr()
         a.cut, a.proto = cut.data_ptr(), proto.data_ptr()
         return a, (cut, proto)
+
+    def _label_map(self, what, B, dev, table):
+        """(shift, t_delay, t_scale), to keep alive: the label map of `table` (a LabelsTable) for a launch on `dev` with B windows"""
+        self._holds(what, B, dev)
+        ts = (self.shift, self.t_delay(table.sr).contiguous(), self.t_scale().contiguous())
+        _need_cuda(*ts, table.file_end_sec)
+        return ts
 
 
 def wave_warp(table, win_file, win_start, length, warp):
@@ -1193,18 +1203,21 @@ def labels_render(table, win_file, win_start, length, form='train', duration_tol
     if form not in LABELS_FORM:
         raise HfttError('labels_render: form %r (train / store)' % (form,))
     dev = table.device
+
+    def need_warp_columns():
+        if table.file_end_sec is None or table.sr is None:
+            raise HfttError('labels_render: the note table carries no file_end_sec / sr (built before the warped render): rebuild it with labels_table_host')
     if warp is not None:
         if not isinstance(warp, Warp):
             raise HfttError('labels_render: warp must be an ops.Warp')
-        if table.file_end_sec is None or table.sr is None:
-            raise HfttError('labels_render: the note table carries no file_end_sec / sr (built before the warped render): rebuild it with labels_table_host')
+        need_warp_columns()
     if mix is not None:
         if not isinstance(mix, Mix):
             raise HfttError('labels_render: mix must be an ops.Mix')
         if a_frames is None:
             raise HfttError('labels_render: a mix needs a_frames (the primaries\' audio frame counts: ops.audio_frames)')
-        if mix.warp is not None and (table.file_end_sec is None or table.sr is None):
-            raise HfttError('labels_render: the note table carries no file_end_sec / sr (built before the warped render): rebuild it with labels_table_host')
+        if mix.warp is not None:
+            need_warp_columns()
     win_file = torch.as_tensor(win_file, device=dev).to(torch.int32).contiguous()
     win_start = torch.as_tensor(win_start, device=dev).to(torch.int32).contiguous()
     _need_cuda(table.notes, table.row_ptr, table.file_nframe, win_file, win_start)
@@ -1237,10 +1250,7 @@ def labels_render(table, win_file, win_start, length, form='train', duration_tol
         for w, names in ((warp, ('shift', 't_delay', 't_scale')), (mix.warp, ('mix_shift', 'mix_t_delay', 'mix_t_scale'))):
             if w is None:
                 continue
-            if w.step_q24.device != dev or w.step_q24.numel() != B:
-                raise HfttError('labels_render: the warp holds %d windows on %s, the request %d on %s' % (w.step_q24.numel(), w.step_q24.device, B, dev))
-            ts = (w.shift, w.t_delay(table.sr).contiguous(), w.t_scale().contiguous())
-            _need_cuda(*ts, table.file_end_sec)
+            ts = w._label_map('labels_render', B, dev, table)
             keep.append(ts)
             for name, t in zip(names, ts):
                 setattr(m, name, t.data_ptr())
@@ -1248,13 +1258,10 @@ def labels_render(table, win_file, win_start, length, form='train', duration_tol
         m.mix_file, m.mix_start, m.a_frames = mix.file.data_ptr(), mix.start.data_ptr(), a_frames.data_ptr()
         check(lib().hftt_labels_render_mix(C.byref(m), _stream(dev)), 'labels_render_mix')
     elif warp is not None:
-        if warp.step_q24.device != dev or warp.step_q24.numel() != B:
-            raise HfttError('labels_render: the warp holds %d windows on %s, the request %d on %s' % (warp.step_q24.numel(), warp.step_q24.device, B, dev))
-        t_delay, t_scale = warp.t_delay(table.sr).contiguous(), warp.t_scale().contiguous()
-        _need_cuda(warp.shift, t_delay, t_scale, table.file_end_sec)
+        ts = warp._label_map('labels_render', B, dev, table)
         w = LabelsWarpDesc()
         w.base = d
-        w.shift, w.t_delay, w.t_scale, w.file_end_sec = warp.shift.data_ptr(), t_delay.data_ptr(), t_scale.data_ptr(), table.file_end_sec.data_ptr()
+        w.shift, w.t_delay, w.t_scale, w.file_end_sec = [t.data_ptr() for t in ts] + [table.file_end_sec.data_ptr()]
         check(lib().hftt_labels_render_warp(C.byref(w), _stream(dev)), 'labels_render_warp')
     else:
         check(lib().hftt_labels_render(C.byref(d), _stream(dev)), 'labels_render')

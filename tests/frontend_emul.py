@@ -1,4 +1,5 @@
-"""fp32 restatements, fp64 references and rounding-model criteria of the audio front end, csrc/logmel.hip: hftt_logmel and hftt_resample.
+"""fp32 restatements, fp64 references and rounding-model criteria of the audio front end, csrc/logmel.hip (hftt_logmel and hftt_resample) and
+the frame transform it shares with the clip log-mel, csrc/logmel_frame.h.
 
 As in tests/elementwise_emul.py, three things per kernel, all in torch and device-agnostic:
 
@@ -8,8 +9,8 @@ As in tests/elementwise_emul.py, three things per kernel, all in torch and devic
            sum, logf; four interleaved fma accumulators for the resampler); defect=<name> selects one deliberately wrong variant;
   *_check  |got - ref| <= bound element by element, no element excluded; returns the list of violations (empty = pass).
 
-The bounds are first-order rounding models: U32 = 2^-24 per fp32 rounding times a count read off logmel.hip (the line is cited beside each
-count) times the magnitude the rounding acts on.  The device contracts a * b + c into one fma where it can; that removes roundings, so the
+The bounds are first-order rounding models: U32 = 2^-24 per fp32 rounding times a count read off the source (the function or kernel is cited
+by name beside each count) times the magnitude the rounding acts on.  The device contracts a * b + c into one fma where it can; that removes roundings, so the
 counts (no contraction) hold for either code.  tests/test_frontend_emul_bound.py shows on the CPU what the criteria resolve;
 tests/test_frontend_fp64_gpu.py holds the kernels to them.
 """
@@ -55,7 +56,7 @@ def n_frames_of(n, hop=HOP):
 
 
 def _frames(wave, t, n_frames, start_shift=0):
-    """[n_frames, n_fft] samples of the centred, zero-padded frames (logmel.hip:28, 40-42: start = frame * hop - n_fft / 2) and their validity"""
+    """[n_frames, n_fft] samples of the centred, zero-padded frames (logmel_kernel, frame start and packing: start = frame * hop - n_fft / 2) and their validity"""
     n = wave.numel()
     idx = (torch.arange(n_frames, device=wave.device)[:, None] * t['hop'] - t['n_fft'] // 2 + start_shift
            + torch.arange(t['n_fft'], device=wave.device)[None, :])
@@ -81,7 +82,7 @@ def logmel_ref(wave, t):
 
 
 # ================================================================================================ log-mel: the kernel in fp32
-def _cmul(ax, ay, wx, wy):                     # logmel.hip:36, without contraction: two products and one sum per component
+def _cmul(ax, ay, wx, wy):                     # logmel_frame.h: frame_cmul, without contraction: two products and one sum per component
     return ax * wx - ay * wy, ax * wy + ay * wx
 
 
@@ -95,7 +96,7 @@ def logmel_emul(wave, t, defect=None):
     F = 1 + ((n - 1) // hop if defect == 'frames_floor_of_n_minus_1' else n // hop)
     fr, ok, idx = _frames(wave, t, F, start_shift=1 if defect == 'frame_start_off_by_one' else 0)
     win = t['window']
-    # packing (logmel.hip:38-44): z[n] = x[2n] w[2n] + i x[2n + 1] w[2n + 1], each slot with its own bounds test
+    # packing (logmel_kernel): z[n] = x[2n] w[2n] + i x[2n + 1] w[2n + 1], each slot with its own bounds test
     xe = fr[:, 0::2] * win[None, 0::2]
     w_odd = win[None, 0::2] if defect == 'odd_sample_uses_even_window' else win[None, 1::2]
     odd = fr[:, 1::2]
@@ -106,7 +107,7 @@ def logmel_emul(wave, t, defect=None):
     re, im = torch.where(ok[:, 0::2], xe, zero), torch.where(ok[:, 1::2], xo, zero)      # (an out-of-range slot is 0, not wave * window)
     tc, ts = t['twiddle'][:N], t['twiddle'][N:]
 
-    def tw(m, split=False):                    # logmel.hip:31-35: e^(-2 pi i m / 2048); the second half turn is a sign
+    def tw(m, split=False):                    # logmel_frame.h: frame_tw: e^(-2 pi i m / 2048); the second half turn is a sign
         mm = m & (N - 1)
         c, sn = tc[mm], ts[mm]
         second = (m & N) != 0
@@ -119,7 +120,7 @@ def logmel_emul(wave, t, defect=None):
 
     j = torch.arange(Q, device=dev)
     Ns = 1
-    while Ns < N:                              # logmel.hip:49-63
+    while Ns < N:                              # logmel_frame.h: frame_stage, once per Ns (the stage loop of both kernels)
         k = j & (Ns - 1)
         step = NFFT // (4 * Ns)
         v = [(re[:, j + q * Q], im[:, j + q * Q]) for q in range(4)]
@@ -136,7 +137,7 @@ def logmel_emul(wave, t, defect=None):
         nre[:, j0 + 3 * Ns] = s02[0] - s13[1]; nim[:, j0 + 3 * Ns] = s02[1] + s13[0]
         re, im = nre, nim
         Ns *= 4
-    # the split pass (logmel.hip:65-72), k = 0 .. N with Z[N] = Z[0]
+    # logmel_frame.h: frame_split, split pass and power, k = 0 .. N with Z[N] = Z[0]
     kk = torch.arange(N + 1, device=dev)
     zkx, zky = re[:, kk & (N - 1)], im[:, kk & (N - 1)]
     znx, zny = re[:, (N - kk) & (N - 1)], im[:, (N - kk) & (N - 1)]
@@ -145,7 +146,7 @@ def logmel_emul(wave, t, defect=None):
     wox, woy = _cmul(ox, oy, *tw(kk, split=True))
     xr, xi = ex + wox, ey + woy
     pw = xr * xr + xi * xi
-    # the CSR sum, in sequence (logmel.hip:74-79)
+    # logmel_frame.h: frame_mel, the CSR sum in sequence
     st, ln, off = t['fb_start'].long(), t['fb_len'].long(), t['fb_off'].long()
     if defect == 'mel_last_weight_dropped':
         ln = ln - 1
@@ -162,25 +163,25 @@ def logmel_emul(wave, t, defect=None):
 
 # ================================================================================================ log-mel: the criterion
 # Delta X_k, in U32 of the frame's magnitude S (below), along the longest path from a sample to X_k:
-#   window product (logmel.hip:41-42)                                                                                          1
-#   stage Ns = 1 (:54-60, no twiddle): two additions                                                                           2
-#   stages Ns = 4 .. 256 (:53-60): cmul = product + sum 2, its twiddle's two table entries (:33) 2, two additions 2  = 6, x 4   24
-#   split pass (:67-70): e or o 1 (the halving is exact), cmul 2, its twiddle's two table entries 2, e + wo 1                   6
+#   window product (logmel_kernel, packing; clip_logmel_kernel packs with the same product)                                    1
+#   frame_stage, Ns = 1 (no twiddle): a02 / s02 / a13 / s13, then the sum of two of them: two additions                         2
+#   frame_stage, Ns = 4 .. 256: frame_cmul = product + sum 2, frame_tw's two table entries 2, two additions 2        = 6, x 4   24
+#   frame_split: e or o 1 (the halving is exact), frame_cmul 2, frame_tw's two table entries 2, e + wo 1                        6
 C_FFT = 1 + 2 + 4 * 6 + 6
 # The magnitude S.  'l1': sum |x w| of the frame -- every rounding of every path with the same sign: a bound in the strict sense, and the
 # criterion.  'l2': ||x w||_2 -- the count still linear along a path, the 2048 paths into one bin added as independent terms -- is the
 # tighter, statistical form; tests/test_frontend_emul_bound.py records what share of the cells each leaves open.
 LOGMEL_NORM = 'l1'
-# p_k = xr * xr + xi * xi (:71): two products and a sum, 3 U32 of p_k at most
+# p_k = xr * xr + xi * xi (frame_split, power): two products and a sum, 3 U32 of p_k at most
 C_POW = 3
 
 
 def logmel_bound(ref, norm=LOGMEL_NORM, c_fft=C_FFT, c_pow=C_POW, c_sum=None, c_log=C_LOG):
     """(upward, downward) bounds of got - ref, each [n_frames, n_mels]:
       Delta X_k  <= c_fft U32 S;   Delta p_k <= 2 |X_k| Delta X_k + Delta X_k^2 + c_pow U32 p_k  (+ F32_TINY: a product below the normal range)
-      Delta mel  <= sum_j w_j Delta p_j + c_sum U32 sum_j w_j p_j, c_sum = len + 1      (:77: the product w * p 1, len additions in sequence)
+      Delta mel  <= sum_j w_j Delta p_j + c_sum U32 sum_j w_j p_j, c_sum = len + 1      (frame_mel: the product w * p 1, len additions in sequence)
       log domain: up = log1p(r), r = Delta mel / (mel + offset); down = -log1p(-r), and never below log(offset): pw and the weights are
-      >= 0, so acc >= 0 and got >= logf(offset) -- that guards r >= 1;  + c_log U32 |log| for logf and 1 U32 for acc + offset (:78)."""
+      >= 0, so acc >= 0 and got >= logf(offset) -- that guards r >= 1;  + c_log U32 |log| for logf and 1 U32 for acc + offset (frame_mel)."""
     S = (ref['l2'] if norm == 'l2' else ref['l1'])[:, None]
     dX = c_fft * U32 * S
     dp = 2 * ref['absX'] * dX + dX * dX + c_pow * U32 * ref['p'] + F32_TINY
@@ -322,7 +323,7 @@ def _fma(a, b, c):
 
 
 def resample_emul(wave, kern, up, down, width, defect=None):
-    """resample_kernel in fp32 (logmel.hip:89-119): four interleaved fma accumulators over the taps, a0 takes the tail, (a0 + a1) + (a2 + a3)"""
+    """resample_kernel (logmel.hip) in fp32: four interleaved fma accumulators over the taps, a0 takes the tail, (a0 + a1) + (a2 + a3)"""
     assert defect is None or defect in RESAMPLE_DEFECTS
     wave = wave.detach().reshape(-1).float()
     dev = wave.device
@@ -355,9 +356,9 @@ def resample_emul(wave, kern, up, down, width, defect=None):
 
 
 def resample_bound(ref):
-    """an accumulator takes taps / 4 fma of one rounding each (logmel.hip:111-116), then two additions (:118): (taps / 4 + 2) U32 of
+    """an accumulator takes taps / 4 fma of one rounding each (resample_kernel, the tap loop), then two additions (its last line): (taps / 4 + 2) U32 of
     sum |x_t k_t|, + F32_TINY for a result below the normal range.  (The count charges every term the whole chain; only a chain's first
-    term passes all of it, so the <= 3 tail taps of a0, :117, whose table entries are the smallest of the row, fit inside.)"""
+    term passes all of it, so the <= 3 tail taps of a0 (the loop behind the unrolled one), whose table entries are the smallest of the row, fit inside.)"""
     return (ref['taps'] / 4 + 2) * U32 * ref['scale'] + F32_TINY
 
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import util
+from hipcc_remarks import get, resources
 
 HDR = os.path.join(util.ROOT, 'include', 'hftt_hip.h')
 
@@ -100,20 +101,12 @@ def test_kernel_needs_no_scratch_and_stays_inside_64_kb_of_lds():
     '''the compiler's own resource remarks (hipcc cross-compiles without a GPU) for every kernel of clip_logmel.hip: no scratch, and the static
     LDS plus the staged samples of the largest hop the host admits (and of the paper's hop 256) within 65,536 bytes'''
     from hftt_hip import _capi
-    hipcc = '/opt/rocm/bin/hipcc'
-    if not os.path.exists(hipcc):
-        pytest.skip('hipcc not found')
-    out = subprocess.run([hipcc, '--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wno-unused-result', '-x', 'hip', '-c',
-                          os.path.join(util.ROOT, 'nylon-amt_amd', 'csrc', 'clip_logmel.hip'), '-o', '/dev/null', '-Rpass-analysis=kernel-resource-usage'],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels = re.findall(r'Function Name: (\S+)', out.stderr)
+    res = resources('clip_logmel.hip')
+    kernels = list(res)
     assert len(kernels) >= 1 and all('clip_logmel_kernel' in k for k in kernels), kernels
-    scratch = [int(x) for x in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', out.stderr)]
-    lds = [int(x) for x in re.findall(r'LDS Size \[bytes/block\]: (\d+)', out.stderr)]
-    assert len(scratch) == len(lds) == len(kernels)
-    assert scratch == [0] * len(kernels)
-    assert [int(x) for x in re.findall(r'VGPRs Spill: (\d+)', out.stderr)] == [0] * len(kernels)
+    assert [get(v, 'ScratchSize') for v in res.values()] == [0] * len(kernels)
+    assert [get(v, 'VGPRs Spill') for v in res.values()] == [0] * len(kernels)
+    lds = [get(v, 'LDS Size') for v in res.values()]
     staged = lambda hop: ((_capi.CLIP_LOGMEL_RUN - 1) * hop + 2048) * 4
     for static in lds:
         assert static + staged(256) <= 65536 and static + staged(324) <= 65536 < static + staged(325), (static, staged(324))

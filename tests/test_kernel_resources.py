@@ -3,40 +3,11 @@
 Round 5 found the <= 128-key attention backward forms at HALF their intended occupancy for three rounds: nothing bounded their registers, hipcc
 spread them over 280-300 (accumulation registers as spill space), and one workgroup per CU ran where the LDS budget was laid out for two.  The
 kernels were correct, so no parity test could see it; this one reads the compiler's own resource remarks."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'nylon-amt_amd', 'csrc')
-HIPCC = '/opt/rocm/bin/hipcc' if os.path.exists('/opt/rocm/bin/hipcc') else shutil.which('hipcc')
-
-
-def _resources(src):
-    out = subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wno-unused-result', '-x', 'hip', '-c', os.path.join(CSRC, src),
-                          '-o', '/dev/null', '-Rpass-analysis=kernel-resource-usage'], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rows, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'Function Name: (\S+)', line)
-        if m:
-            cur = m.group(1); rows[cur] = {}
-            continue
-        m = re.search(r'remark:\s+([A-Za-z ]+(?:\[[^\]]*\])?): (\d+)', line)
-        if m and cur:
-            rows[cur][m.group(1).strip()] = int(m.group(2))
-    names = subprocess.run(['c++filt'], input='\n'.join(rows), capture_output=True, text=True).stdout.splitlines()
-    return {re.sub(r'\(anonymous namespace\)::|void |\(.*$', '', n): v for n, v in zip(names, rows.values())}
-
-
-def _get(v, key):
-    for k, x in v.items():
-        if k.startswith(key):
-            return x
-    raise KeyError(key)
+from hipcc_remarks import HIPCC, get as _get, resources as _resources
 
 
 @pytest.mark.skipif(HIPCC is None, reason='hipcc not found')

@@ -1,6 +1,6 @@
 """C ABI and host half of clip mixing (hftt_clip_logmel_mix, hftt_clip_logmel_mix_warp, hftt_labels_render_mix; hftt_hip.ops.Mix /
 audio_frames): the symbols, the descriptor layouts against the C compiler, every host-side refusal by message (they run before the device
-guard and the launch, so a box without a GPU tests them), the compile remarks of the two new translation units, and the Python entry
+guard and the launch, so a box without a GPU tests them), the compile remarks of the kernels with a partner, and the Python entry
 points' argument checks.  No compute calls."""
 import ctypes as C
 import os
@@ -13,9 +13,9 @@ import pytest
 import torch
 
 import util
+from hipcc_remarks import CSRC, get, resources
 
 HDR = os.path.join(util.ROOT, 'include', 'hftt_hip.h')
-CSRC = os.path.join(util.ROOT, 'nylon-amt_amd', 'csrc')
 ENTRIES = {'hftt_clip_logmel_mix': ('ClipLogmelMixDesc', 'hftt_clip_logmel_mix_desc'), 'hftt_clip_logmel_mix_warp': ('ClipLogmelMixWarpDesc', 'hftt_clip_logmel_mix_warp_desc'),
            'hftt_labels_render_mix': ('LabelsMixDesc', 'hftt_labels_mix_desc')}
 
@@ -184,47 +184,45 @@ def test_null_descriptors(lib):
         assert getattr(lib, name)(None, None) not in (0, 2, 3) and b'null descriptor' in lib.hftt_last_error()
 
 
-def _remarks(src):
-    hipcc = '/opt/rocm/bin/hipcc'
-    if not os.path.exists(hipcc):
-        pytest.skip('hipcc not found')
-    out = subprocess.run([hipcc, '--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wno-unused-result', '-x', 'hip', '-c', os.path.join(CSRC, src),
-                          '-o', '/dev/null', '-Rpass-analysis=kernel-resource-usage'], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    get = lambda pat: [int(x) for x in re.findall(pat + r': (\d+)', out.stderr)]
-    return {'kernels': re.findall(r'Function Name: (\S+)', out.stderr), 'scratch': get(r'ScratchSize \[bytes/lane\]'), 'vgpr_spill': get('VGPRs Spill'),
-            'sgpr_spill': get('SGPRs Spill'), 'lds': get(r'LDS Size \[bytes/block\]'), 'vgprs': get(' VGPRs'), 'occupancy': get(r'Occupancy \[waves/SIMD\]')}
+CLIP_KERNELS = ['clip_logmel_kernel<2048, false>', 'clip_logmel_kernel<2048, true>', 'clip_logmel_kernel<2048, false, clip_mix>', 'clip_logmel_kernel<2048, true, clip_mix>']
+LABEL_KERNELS = ['labels_render_kernel<true>', 'labels_render_kernel<false>', 'labels_render_kernel<true, label_mix>', 'labels_render_kernel<false, label_mix>']
 
 
 def test_the_mixed_clip_kernels_need_no_scratch_and_keep_the_static_lds():
-    """clip_mix.hip: two kernels (unwarped and warped), both instantiations of clip_logmel_kernel with a partner, no scratch, no register
-    spilled to memory, and the static LDS of clip_logmel.hip's kernels: hop 324 is still admitted"""
+    """clip_logmel.hip: exactly four kernels, clip_logmel_kernel unwarped and warped, without and with a partner; the two with a partner have
+    no scratch, no register spilled to memory, and the static LDS of the two without: hop 324 is still admitted"""
     from hftt_hip import _capi
-    mix, base = _remarks('clip_mix.hip'), _remarks('clip_logmel.hip')
-    assert len(mix['kernels']) == 2 and len(set(mix['kernels'])) == 2 and all('clip_logmel_kernel' in k and 'clip_mix' in k for k in mix['kernels']), mix['kernels']
-    assert mix['scratch'] == [0, 0] and mix['vgpr_spill'] == [0, 0]
+    res = resources('clip_logmel.hip')
+    assert sorted(res) == sorted(CLIP_KERNELS)
+    base, mix = [res[k] for k in CLIP_KERNELS[:2]], [res[k] for k in CLIP_KERNELS[2:]]
+    assert [get(v, 'ScratchSize') for v in mix] == [0, 0] and [get(v, 'VGPRs Spill') for v in mix] == [0, 0]
     staged = lambda hop: ((_capi.CLIP_LOGMEL_RUN - 1) * hop + 2048) * 4
-    assert len(set(base['lds'])) == 1 and mix['lds'] == base['lds']
-    assert mix['lds'][0] + staged(324) <= 65536 < mix['lds'][0] + staged(325)
-    print('clip_mix.hip: VGPRs %s, occupancy %s, SGPRs spilled to VGPR lanes %s, static LDS %s' % (mix['vgprs'], mix['occupancy'], mix['sgpr_spill'], mix['lds']))
+    lds = [get(v, 'LDS Size') for v in mix]
+    assert len(set(get(v, 'LDS Size') for v in base)) == 1 and lds == [get(v, 'LDS Size') for v in base]
+    assert lds[0] + staged(324) <= 65536 < lds[0] + staged(325)
+    print('clip_logmel.hip with a partner: VGPRs %s, occupancy %s, SGPRs spilled to VGPR lanes %s, static LDS %s'
+          % tuple([get(v, k) for v in mix] for k in ('VGPRs', 'Occupancy', 'SGPRs Spill', 'LDS Size')))
 
 
 def test_the_mixed_label_kernels_need_no_scratch():
-    """labels_mix.hip: both output forms, no scratch; registers and occupancy are printed"""
-    mix = _remarks('labels_mix.hip')
-    assert len(mix['kernels']) == 2 and all('labels_render_kernel' in k and 'label_mix' in k for k in mix['kernels']), mix['kernels']
-    assert mix['scratch'] == [0, 0] and mix['vgpr_spill'] == [0, 0]
-    print('labels_mix.hip: VGPRs %s, occupancy %s, SGPRs spilled to VGPR lanes %s' % (mix['vgprs'], mix['occupancy'], mix['sgpr_spill']))
+    """labels.hip: exactly four kernels, both output forms without and with a partner; the two with a partner have no scratch; registers and
+    occupancy are printed"""
+    res = resources('labels.hip')
+    assert sorted(res) == sorted(LABEL_KERNELS)
+    mix = [res[k] for k in LABEL_KERNELS[2:]]
+    assert [get(v, 'ScratchSize') for v in mix] == [0, 0] and [get(v, 'VGPRs Spill') for v in mix] == [0, 0]
+    print('labels.hip with a partner: VGPRs %s, occupancy %s, SGPRs spilled to VGPR lanes %s' % tuple([get(v, k) for v in mix] for k in ('VGPRs', 'Occupancy', 'SGPRs Spill')))
 
 
 def test_the_shared_bodies_are_written_once():
-    """the kernel templates and the refusals live in the two headers; no translation unit carries a second copy"""
+    """the kernel templates, the refusals and the frame transform are written in one file each; no other file carries a second copy"""
     src = {f: open(os.path.join(CSRC, f)).read() for f in os.listdir(CSRC) if f.endswith(('.hip', '.h'))}
-    for pat, home in ((r'__global__ .*\bvoid clip_logmel_kernel\(', 'clip_logmel_kernel.h'), (r'__global__ .*\bvoid labels_render_kernel\(', 'labels_walk.h'),
-                      (r'\bvoid label_walk\(', 'labels_walk.h'), (r'clip_logmel: n_fft=%d unsupported', 'clip_logmel_kernel.h'), (r'labels_render: tol=%d', 'labels_walk.h')):
+    for pat, home in ((r'__global__ .*\bvoid clip_logmel_kernel\(', 'clip_logmel.hip'), (r'__global__ .*\bvoid labels_render_kernel\(', 'labels.hip'),
+                      (r'\bvoid label_walk\(', 'labels.hip'), (r'clip_logmel: n_fft=%d unsupported', 'clip_logmel.hip'), (r'labels_render: tol=%d', 'labels.hip'),
+                      (r'dst\[j0 \+ 3 \* Ns\]', 'logmel_frame.h'), (r'xr \* xr \+ xi \* xi', 'logmel_frame.h'), (r'acc \+= fb_w\[off \+ j\] \* pw\[st \+ j\]', 'logmel_frame.h')):
         assert [f for f, s in src.items() for _ in re.findall(pat, s)] == [home], pat
-    for f, header in (('clip_logmel.hip', 'clip_logmel_kernel.h'), ('clip_mix.hip', 'clip_logmel_kernel.h'), ('labels.hip', 'labels_walk.h'), ('labels_mix.hip', 'labels_walk.h')):
-        assert '#include "%s"' % header in src[f] and '__global__' not in src[f], f
+    for f in ('clip_logmel.hip', 'logmel.hip'):
+        assert '#include "logmel_frame.h"' in src[f] and '__global__' not in src['logmel_frame.h'], f
 
 
 def _note(pitch, onset, offset, velocity=64):

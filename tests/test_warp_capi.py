@@ -1,6 +1,6 @@
 """C ABI and host half of the warp (hftt_wave_warp, hftt_clip_logmel_warp, hftt_labels_render_warp; hftt_hip.ops.Warp / WarpTable; the warp draws
 of training.dataset.WaveAugment): the symbols, the descriptor layouts against the C compiler, every host-side refusal by message (they run
-before the device guard and the launch, so a box without a GPU tests them), the compile remarks of clip_logmel.hip with the new instantiation,
+before the device guard and the launch, so a box without a GPU tests them), the compile remarks of the warped clip_logmel_kernel,
 and the host tables.  No compute calls."""
 import ctypes as C
 import os
@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import util
+from hipcc_remarks import get, resources
 
 HDR = os.path.join(util.ROOT, 'include', 'hftt_hip.h')
 ENTRIES = {'hftt_wave_warp': 'WaveWarpDesc', 'hftt_clip_logmel_warp': 'ClipLogmelWarpDesc', 'hftt_labels_render_warp': 'LabelsWarpDesc'}
@@ -180,24 +181,17 @@ def test_null_descriptors_and_the_unwarped_file_nframe(lib):
 
 
 def test_both_instantiations_need_no_scratch_and_stay_inside_64_kb_of_lds():
-    """the compiler's resource remarks for clip_logmel.hip: two kernels now (the unwarped and the warped staging loop), both instantiations of
-    clip_logmel_kernel, neither with scratch or spills, both with the static LDS that admits hop 324 and not 325"""
+    """the compiler's resource remarks for the unwarped and the warped staging loop (clip_logmel.hip: clip_logmel_kernel<2048, false> and
+    <2048, true>): neither with scratch or spills, both with the static LDS that admits hop 324 and not 325"""
     from hftt_hip import _capi
-    hipcc = '/opt/rocm/bin/hipcc'
-    if not os.path.exists(hipcc):
-        pytest.skip('hipcc not found')
-    out = subprocess.run([hipcc, '--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wno-unused-result', '-x', 'hip', '-c',
-                          os.path.join(util.ROOT, 'nylon-amt_amd', 'csrc', 'clip_logmel.hip'), '-o', '/dev/null', '-Rpass-analysis=kernel-resource-usage'],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels = re.findall(r'Function Name: (\S+)', out.stderr)
-    assert len(kernels) == 2 and len(set(kernels)) == 2 and all('clip_logmel_kernel' in k for k in kernels), kernels
-    assert [int(x) for x in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', out.stderr)] == [0, 0]
-    assert [int(x) for x in re.findall(r'VGPRs Spill: (\d+)', out.stderr)] == [0, 0]
-    lds = [int(x) for x in re.findall(r'LDS Size \[bytes/block\]: (\d+)', out.stderr)]
+    res = resources('clip_logmel.hip')
+    both = [res['clip_logmel_kernel<2048, false>'], res['clip_logmel_kernel<2048, true>']]
+    assert [get(v, 'ScratchSize') for v in both] == [0, 0]
+    assert [get(v, 'VGPRs Spill') for v in both] == [0, 0]
+    lds = [get(v, 'LDS Size') for v in both]
     staged = lambda hop: ((_capi.CLIP_LOGMEL_RUN - 1) * hop + 2048) * 4
-    assert len(lds) == 2 and lds[0] == lds[1] and lds[0] + staged(324) <= 65536 < lds[0] + staged(325), lds
-    print('clip_logmel.hip: %s, VGPRs %s' % (kernels, re.findall(r' VGPRs: (\d+)', out.stderr)))
+    assert lds[0] == lds[1] and lds[0] + staged(324) <= 65536 < lds[0] + staged(325), lds
+    print('clip_logmel.hip: unwarped / warped VGPRs %s' % [get(v, 'VGPRs') for v in both])
 
 
 def _note(pitch, onset, offset, velocity=64):
