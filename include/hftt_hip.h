@@ -591,6 +591,62 @@ int64_t hftt_notes_seg_ws_bytes(int64_t F, int32_t N, int32_t n_seg);
 int hftt_notes_decode_seg(const hftt_notes_seg_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Streaming notes (csrc/notes_stream.hip; model/amt.py:179-341 mpe2note, mode_offset 'shorter' ONLY): the decode above with its state
+ * carried forward.  S streams each keep their four rolls as a RING of H rows, [S, H, N]; row r of stream s lives at ring row r % H.
+ * row_end[s] (DEVICE int64) is the number of rows delivered so far, closed[s] (DEVICE int32) != 0 says that the stream has ended and
+ * row_end[s] is its F.  One call returns every note that NO LATER ROW CAN CHANGE and that no earlier call returned: over all calls of a
+ * stream, the closing one included, the notes are exactly those of hftt_notes_decode on the whole rolls, none missing, none twice, for any
+ * split of the rows into calls (calls without new rows and calls of one row included).  ADDED at ABI 8; HFTT_ABI_VERSION stays 8.
+ *
+ * When a note is final.  A frame of a track is DECIDED when its peak status cannot change: its value is below the threshold, or not above the
+ * run in front of it, or its run has ended.  Only the trailing run can be undecided.  For the kept onset peak f of a pitch:
+ *   A  a next onset peak ln is decided: the mpe end comes from rows < ln; the offset peak p <= ln when one is decided, else "clipped to ln" as
+ *      soon as every offset frame <= ln is decided (under 'shorter' clipped and absent give the same value); the trim uses ln when it is kept,
+ *      else frame ln + 1 of the same plateau when that is kept -- from ln + 2 on every onset time lies a whole hop above the value.
+ *   B  none is decided: the deciding event ev is the first decided offset peak with no frame below thred_mpe in front of it, or the first such
+ *      frame with every offset frame up to it decided; the note is final once the onset frames <= ev + 1 are decided and hold no peak.
+ *   At the close the horizon is F and what is pending follows the offline rules, with F in the peak time's edge rule and the last "next onset".
+ * With 'longer' / 'offset' a note may depend on whether an offset peak occurs anywhere later: the number of pending notes is unbounded, so
+ * these modes are refused by name.
+ *
+ * State: hftt_notes_stream_state_bytes(S, N) bytes, ALL ZERO for fresh streams; 64 bytes per (stream, pitch) -- the commit frame c (every
+ * onset peak in front of it is returned or is the one pending head), the last row_end, the head's frame, time and velocity, on / off[c - 1]
+ * and the value of the run in front of theirs -- plus one int32 each that is zero between calls.  Its size does not depend on the stream's age,
+ * and a call reads rows c .. row_end only: its cost depends on the new rows and the undecided stretch, never on the age.
+ * Outputs: records within cap in stream-major, pitch-major, ascending-onset-frame order (prefix sums, no atomics), stream s = records
+ * stream_notes[s] .. stream_notes[s + 1]; *n_notes = stream_notes[S] = the number that this call found.  When it exceeds cap NOTHING is
+ * written to the records and the state STAYS AS IT WAS: the caller repeats the call with more room.  overflow[s] != 0: the rows that stream s
+ * still needs (an undecided plateau at or above a threshold, or more new rows than H) no longer lie in the ring; the stream returns nothing
+ * from then on -- a status, not a fault.  A closed stream that has been decoded returns nothing more.
+ * Kernels: one lane per (stream, pitch), one workgroup of 128 per stream, walks its rows sequentially (N is the contiguous axis: a wave reads
+ * whole rows); a count pass, a prefix sum, and an emit pass that alone commits the state.  Frame indices are int64.
+ * Refused in front of the launch: null pointers; S < 1 (or S * N >= 2^24); N outside 1..128; H < 4; max_new outside 0..H (the largest number
+ * of rows any stream received since its last call, as the host knows it); mode_offset != 0; mode_velocity outside 0..1; cap < 0; state_bytes
+ * below the helper's value (0 for arguments outside the domain).
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t S, N, H, note_min;                                     /* streams, notes (1..128), ring rows (>= 4), pitch of note 0 */
+  const void* onset; const void* offset; const void* mpe;        /* fp32 [S, H, N] */
+  const void* velocity;                                          /* int8 [S, H, N] */
+  const void* row_end;                                           /* DEVICE int64 [S] */
+  const void* closed;                                            /* DEVICE int32 [S] */
+  float thred_onset, thred_offset, thred_mpe;
+  int32_t mode_velocity;       /* 0 = ignore_zero, 1 = org */
+  int32_t mode_offset;         /* 0 = shorter; nothing else */
+  int32_t cap;                 /* capacity of the four output arrays, >= 0 */
+  int32_t max_new; int32_t pad;
+  double hop_sec;
+  void* state; int64_t state_bytes;
+  void* out_pitch; void* out_velocity;                           /* int32 [cap] */
+  void* out_onset; void* out_offset;                             /* double [cap] */
+  void* stream_notes;                                            /* int32 [S + 1] */
+  void* n_notes;                                                 /* int32 [1] */
+  void* overflow;                                                /* int32 [S] */
+} hftt_notes_stream_desc;
+int64_t hftt_notes_stream_state_bytes(int32_t S, int32_t N);
+int hftt_notes_stream_step(const hftt_notes_stream_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Label rendering on the device (csrc/labels.hip): note lists -> the frame labels that training consumes, the opposite direction of the
  * decoder above (corpus/conv_note2label.py:8-111 note2label).  Like the note decoder this entry point was ADDED at ABI 8 and HFTT_ABI_VERSION
  * stays 8: a caller that needs it looks the symbol up.

@@ -185,6 +185,19 @@ class NotesSegDesc(C.Structure):
                 ('seg_row0_host', C.POINTER(C.c_int32)), ('seg_row0', C.c_void_p), ('seg_notes', C.c_void_p)]
 
 
+class NotesStreamDesc(C.Structure):         # hftt_notes_stream_desc: S streams, their rolls as rings of H rows, the carried state
+    _fields_ = [('S', C.c_int32), ('N', C.c_int32), ('H', C.c_int32), ('note_min', C.c_int32),
+                ('onset', C.c_void_p), ('offset', C.c_void_p), ('mpe', C.c_void_p), ('velocity', C.c_void_p),
+                ('row_end', C.c_void_p), ('closed', C.c_void_p),
+                ('thred_onset', C.c_float), ('thred_offset', C.c_float), ('thred_mpe', C.c_float),
+                ('mode_velocity', C.c_int32), ('mode_offset', C.c_int32), ('cap', C.c_int32),
+                ('max_new', C.c_int32), ('pad', C.c_int32),
+                ('hop_sec', C.c_double),
+                ('state', C.c_void_p), ('state_bytes', C.c_int64),
+                ('out_pitch', C.c_void_p), ('out_velocity', C.c_void_p), ('out_onset', C.c_void_p), ('out_offset', C.c_void_p),
+                ('stream_notes', C.c_void_p), ('n_notes', C.c_void_p), ('overflow', C.c_void_p)]
+
+
 LABELS_CHUNK = 256                          # HFTT_LABELS_CHUNK
 LABELS_TRAIN, LABELS_STORE = 0, 1           # HFTT_LABELS_TRAIN / HFTT_LABELS_STORE
 
@@ -326,6 +339,8 @@ SIGNATURES = {
     'hftt_clip_windows': (C.c_int, [C.POINTER(ClipWindowsDesc), C.c_void_p]),
     'hftt_notes_seg_ws_bytes': (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     'hftt_notes_decode_seg': (C.c_int, [C.POINTER(NotesSegDesc), C.c_void_p]),
+    'hftt_notes_stream_state_bytes': (C.c_int64, [C.c_int32, C.c_int32]),
+    'hftt_notes_stream_step': (C.c_int, [C.POINTER(NotesStreamDesc), C.c_void_p]),
     'hftt_labels_render': (C.c_int, [C.POINTER(LabelsDesc), C.c_void_p]),
     'hftt_clip_logmel': (C.c_int, [C.POINTER(ClipLogmelDesc), C.c_void_p]),
     'hftt_clip_logmel_warp': (C.c_int, [C.POINTER(ClipLogmelWarpDesc), C.c_void_p]),

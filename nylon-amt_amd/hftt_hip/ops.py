@@ -10,7 +10,7 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
+from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
                     WARP_DELAY_MAX, WARP_STEP_MAX, WARP_STEP_MIN, WARP_TABLE_L, WARP_TABLE_LEN, WARP_ZEROS,
                     LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, STITCH_MAX_CLIPS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
@@ -812,6 +812,110 @@ def notes_decode_seg(onset, offset, mpe, velocity, seg_rows, hop_sec, note_min=2
             raise HfttError('notes_decode_seg: %d notes exist, capacity=%d' % (total, cap))
         total, t_on, t_off, pitch, vel, seg_notes = run(total)
     return pitch, vel, t_on, t_off, seg_notes
+
+
+class NotesStreamState:
+    """What hftt_notes_stream_step works on, for S streams on one device: the four rolls as rings of H rows ([S, H, N], fp32 x3 and int8; row
+    r of a stream lives at ring row r % H), the device tables row_end int64 [S] / closed int32 [S], the zero-initialised state buffer, and
+    the host's copy of the tables.  The producer writes rows into the rings (stitch on ``rings_flat``: stream s row r = flat row s * H +
+    r % H) and then calls ``deliver``."""
+
+    def __init__(self, S, N, H, device):
+        S, N, H = int(S), int(N), int(H)
+        nbytes = lib().hftt_notes_stream_state_bytes(S, N)
+        if nbytes <= 0 or H < 4:
+            raise HfttError('notes_stream_state: S=%d streams of N=%d notes (1..128) with H=%d ring rows (>= 4)' % (S, N, H))
+        self.S, self.N, self.H, self.device = S, N, H, torch.device(device)
+        if self.device.type != 'cuda':
+            raise HfttError('notes_stream_state: a ROCm device is required (got %s); there is no CPU fallback' % self.device)
+        self.rings = tuple(torch.zeros(S, H, N, dtype=torch.int8 if k == 3 else torch.float32, device=self.device) for k in range(4))
+        self.rings_flat = tuple(t.view(S * H, N) for t in self.rings)
+        self.state = torch.zeros(nbytes, dtype=torch.int8, device=self.device)
+        self.tables = torch.zeros(3 * S, dtype=torch.int32, device=self.device)        # row_end as int64 [S], then closed int32 [S]
+        self.row_end, self.closed = [0] * S, [False] * S
+        self.max_new = 0
+
+    def deliver(self, new_rows, close=None):
+        """new_rows[s] rows were written behind row_end[s]; close[s]: stream s has ended.  One small upload."""
+        close = [False] * self.S if close is None else list(close)
+        for s, n in enumerate(new_rows):
+            n = int(n)
+            if n < 0 or (n > 0 and self.closed[s]):
+                raise HfttError('notes_stream: stream %d: %d new rows for a %s stream' % (s, n, 'closed' if self.closed[s] else 'live'))
+            self.row_end[s] += n
+            self.max_new = max(self.max_new, n)
+            self.closed[s] = self.closed[s] or bool(close[s])
+        host = np.concatenate([np.asarray(self.row_end, np.int64).view(np.int32), np.asarray(self.closed, np.int32)])
+        self.tables.copy_(torch.from_numpy(host))
+
+
+def notes_stream_state(S, N, H, device):
+    """the rings, the tables and the zeroed state of S fresh streams (NotesStreamState)"""
+    return NotesStreamState(S, N, H, device)
+
+
+def _notes_stream_packed(st, args, cap):
+    """hftt_notes_stream_step into ONE device buffer: [n_notes int32 | stream_notes int32 [S + 1] | overflow int32 [S] | pad to 8 | onset
+    double cap | offset double cap | pitch int32 cap | velocity int32 cap]"""
+    thred_onset, thred_offset, thred_mpe, hop_sec, note_min, mode_velocity, mode_offset = args
+    if mode_velocity not in MODE_VELOCITY or mode_offset not in MODE_OFFSET:
+        raise HfttError('notes_stream_step: mode_velocity %r / mode_offset %r unknown' % (mode_velocity, mode_offset))
+    S = st.S
+    head = _align(4 * (2 * S + 2), 8)
+    buf = torch.empty(head + 24 * cap, dtype=torch.int8, device=st.device)
+    d = NotesStreamDesc()
+    d.S, d.N, d.H, d.note_min = S, st.N, st.H, int(note_min)
+    d.onset, d.offset, d.mpe, d.velocity = (t.data_ptr() for t in st.rings)
+    d.row_end, d.closed = st.tables.data_ptr(), st.tables.data_ptr() + 8 * S
+    d.thred_onset, d.thred_offset, d.thred_mpe = float(np.float32(thred_onset)), float(np.float32(thred_offset)), float(np.float32(thred_mpe))
+    d.mode_velocity, d.mode_offset, d.cap, d.max_new = MODE_VELOCITY[mode_velocity], MODE_OFFSET[mode_offset], cap, st.max_new
+    d.hop_sec = float(hop_sec)
+    d.state, d.state_bytes = st.state.data_ptr(), st.state.numel()
+    base = buf.data_ptr()
+    d.n_notes, d.stream_notes, d.overflow = base, base + 4, base + 4 * (S + 2)
+    d.out_onset, d.out_offset, d.out_pitch, d.out_velocity = base + head, base + head + 8 * cap, base + head + 16 * cap, base + head + 20 * cap
+    check(lib().hftt_notes_stream_step(C.byref(d), _stream(st.device)), 'notes_stream_step')
+    return buf, head
+
+
+def notes_stream_default_capacity(S, N):
+    """room for the notes of one step: a step returns what became final, a handful per stream; a long plateau that ends returns more and the
+    wrapper then repeats the step"""
+    return max(1024, 4 * S * N)
+
+
+def notes_stream_step(st, hop_sec, note_min=21, thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5, mode_velocity='ignore_zero',
+                      mode_offset='shorter', capacity=None, host=True):
+    """One step of S streams (hftt_notes_stream_step) on what ``st.deliver`` announced: -> (pitch int32, velocity int32, onset float64, offset
+    float64, stream_notes int32 [S + 1], overflow int32 [S]).  The notes are those that no later row can change, stream-major, pitch-major,
+    by ascending onset frame; stream s owns records stream_notes[s] .. stream_notes[s + 1].  Over all steps of a stream, the closing one
+    included, they are exactly the notes of notes_decode on the whole rolls.  mode_offset must be 'shorter'.  When more notes are final than
+    fit, the state is untouched and the wrapper repeats the step with the exact count -- unless the caller fixed capacity=, then it raises
+    HfttError (and the step can be repeated).  All arrays lie in one packed buffer: host=True is ONE device->host copy per step."""
+    if not isinstance(st, NotesStreamState):
+        raise HfttError('notes_stream_step: the first argument is the NotesStreamState of notes_stream_state()')
+    cap = notes_stream_default_capacity(st.S, st.N) if capacity is None else int(capacity)
+    args = (thred_onset, thred_offset, thred_mpe, hop_sec, note_min, mode_velocity, mode_offset)
+
+    def run(cap):
+        buf, head = _notes_stream_packed(st, args, cap)
+        if host:
+            buf = buf.cpu()
+        ints = buf[:4 * (2 * st.S + 2)].view(torch.int32)
+        total = int(ints[0])
+        n = total if total <= cap else 0
+        t_on = buf[head:head + 8 * cap].view(torch.float64)[:n]
+        t_off = buf[head + 8 * cap:head + 16 * cap].view(torch.float64)[:n]
+        pitch = buf[head + 16 * cap:head + 20 * cap].view(torch.int32)[:n]
+        vel = buf[head + 20 * cap:head + 24 * cap].view(torch.int32)[:n]
+        return total, (pitch, vel, t_on, t_off, ints[1:st.S + 2], ints[st.S + 2:2 * st.S + 2])
+    total, out = run(cap)
+    if total > cap:
+        if capacity is not None:
+            raise HfttError('notes_stream_step: %d notes are final, capacity=%d (the state is untouched: repeat the step with more room)' % (total, cap))
+        total, out = run(total)
+    st.max_new = 0
+    return out
 
 
 def clip_windows(feature, file_row0, win_file, win_start, width, fill):

@@ -4,6 +4,7 @@ Same surface as hftt_code/model/amt.py: ``AMT(config, model_path, batch_size=1, 
 ``wav2feature`` (:34), ``transcript`` (:66), ``transcript_stride`` (:121), ``mpe2note`` (:179), ``note2midi`` (:347).
 Two additions: ``transcript_notes`` = ``mpe2note(*transcript(...))`` with the rolls and the decoding kept on the device (csrc/notes.hip).
 and ``transcript_notes_files``, the same for a list of files in one pass (the file loop of evaluation/m_inference.py:77-165).
+``open_stream`` returns a ``NoteStream``: the same notes for audio that arrives in pieces, each as soon as it is final (csrc/notes_stream.hip).
 Differences in mechanism, not in results:
   * wav2feature runs the log-mel kernel of libhftt_hip.so (STFT + sparse mel + log on the GPU) instead of torchaudio;
   * transcript/transcript_stride gather ALL clip windows of a file and run them through the model in batches of
@@ -359,6 +360,13 @@ class AMT():
             return [(notes_of(f), notes_of(n_files + f)) for f in range(n_files)]
         return [notes_of(f) for f in range(n_files)]
 
+    # ------------------------------------------------------------------ audio as it arrives -> notes as they become final
+    def open_stream(self, n_streams=1, n_offset=None, output='B', thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5,
+                    mode_velocity='ignore_zero', history=None, mode_offset='shorter'):
+        """A NoteStream: ``transcript_notes`` for audio that arrives in pieces, n_streams recordings side by side on this GPU.  See NoteStream
+        for the contract.  One process, one GPU (world > 1 raises HfttError); mode_offset 'shorter' only; there is no CPU fallback."""
+        return NoteStream(self, n_streams, n_offset, output, thred_onset, thred_offset, thred_mpe, mode_velocity, history, mode_offset)
+
     # ------------------------------------------------------------------ posteriorgram -> notes (amt.py:179-344)
     def mpe2note(self, a_onset=None, a_offset=None, a_mpe=None, a_velocity=None, thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5,
                  mode_velocity='ignore_zero', mode_offset='shorter'):
@@ -430,6 +438,259 @@ class AMT():
             f.write(b'MThd' + struct.pack('>IHHH', 6, 0, 1, 220))
             f.write(b'MTrk' + struct.pack('>I', len(trk)) + bytes(trk))
         return
+
+
+class NoteStream():
+    """``AMT.open_stream``: push log-mel frames (``push``) or samples (``push_wave``) of n_streams recordings as they arrive and get back, per
+    stream, the notes that no later audio can change; ``close`` ends streams and returns the rest.  The contract:
+
+        sorted(all notes returned by push... + close, key=(onset, pitch)) == amt.transcript_notes(whole_feature, same arguments)
+
+    bit for bit, for any chunking (with push_wave: whole_feature = ``wave2feature(wave, sr, on_device=True)``).  Mechanism: the frames join a
+    per-stream tail; every clip whose look-ahead has arrived is cut from the tail (hftt_clip_windows, the tail as the "file", so the min_value
+    padding shows only where transcript pads), the ready clips of ALL streams are packed into model calls of up to batch_size clips and
+    stitched (hftt_stitch) into per-stream rings of `history` rows, and one hftt_notes_stream_step per round returns what became final with
+    one device->host copy.  The decoder's state has a fixed size; nothing grows with the length of the recording.
+    Latency: a roll row exists once the clip that holds it has run, i.e. once num_frame + margin_f frames behind the clip's start have
+    arrived -- with n_offset = num_frame / 2, num_frame + margin_f - n_offset frames (96 frames, 1.5 s, at the default config); a note is
+    final a few frames behind its offset peak, its mpe end or the next onset (include/hftt_hip.h: streaming notes).
+    history: ring rows per stream, a multiple of the stitch length, default 4 * num_frame; a round delivers at most half of it, the other
+    half holds what is undecided (an onset or offset plateau at or above its threshold that has not ended).  A stretch that outgrows it
+    raises HfttError naming the stream and history=.
+    Refused with HfttError: world > 1, a device that is not ROCm, mode_offset other than 'shorter' (under 'longer' / 'offset' a note may
+    wait for an offset peak anywhere later in the file), a chunk for a closed stream, samples at another rate.  No CPU fallback."""
+
+    def __init__(self, amt, n_streams, n_offset, output, thred_onset, thred_offset, thred_mpe, mode_velocity, history, mode_offset):
+        from hftt_hip import ops
+        if amt.world > 1:
+            raise HfttError('open_stream runs on one GPU (world = %d): sharded inference uses transcript / transcript_stride + mpe2note' % amt.world)
+        if output not in ('A', 'B'):
+            raise HfttError("output must be 'A' (heads 0-3) or 'B' (heads 5-8)")
+        if mode_offset != 'shorter':
+            raise HfttError("open_stream decodes mode_offset 'shorter' only (got %r): under 'longer' / 'offset' a note may wait for an offset peak "
+                            "anywhere later in the file" % (mode_offset,))
+        if mode_velocity not in ops.MODE_VELOCITY:
+            raise HfttError('open_stream: mode_velocity %r unknown' % (mode_velocity,))
+        if not str(amt.device).startswith('cuda'):
+            raise HfttError('open_stream decodes on the device: a ROCm device is required (there is no CPU fallback)')
+        self.amt, self.S = amt, int(n_streams)
+        if self.S < 1:
+            raise HfttError('open_stream: n_streams=%d must be positive' % self.S)
+        cin, cm = amt.config['input'], amt.config['midi']
+        T = cin['num_frame']
+        if n_offset is None:                                                    # transcript (amt.py:66-118)
+            self.step, self.src0, self.front = T, 0, cin['margin_b']
+        else:                                                                   # transcript_stride (amt.py:121-176)
+            self.step, self.src0, self.front = int(T / 2), int(n_offset), cin['margin_b'] + int(n_offset)
+            if not 0 <= self.src0 <= T - self.step:
+                raise HfttError('open_stream: n_offset=%d outside 0..%d' % (self.src0, T - self.step))
+        self.n_offset, self.h0 = n_offset, 0 if output == 'A' else 5
+        self.width = cin['margin_b'] + T + cin['margin_f']
+        H = 4 * T if history is None else int(history)
+        if H < 2 * self.step or H % self.step:
+            raise HfttError('open_stream: history=%d must be a multiple of the stitch length %d, at least twice it' % (H, self.step))
+        self.per_round = max(1, H // 2 // self.step)                            # clips per stream and round: half the ring
+        self.kw = dict(note_min=cm['note_min'], thred_onset=thred_onset, thred_offset=thred_offset, thred_mpe=thred_mpe, mode_velocity=mode_velocity)
+        self.st = ops.notes_stream_state(self.S, cm['num_note'], H, amt.device)
+        n_bins = amt.config['feature']['n_bins']
+        self.tail = [torch.zeros(0, n_bins, dtype=torch.float32, device=amt.device) for _ in range(self.S)]
+        self.tail0 = [0] * self.S                                               # the file frame of tail row 0
+        self.n = [0] * self.S                                                   # frames received
+        self.next = [0] * self.S                                                # start of the next clip
+        self.closed = [False] * self.S
+        self.wave = [None] * self.S                                             # push_wave: the retained samples (device fp32), from sample wave0
+        self.wave0, self.n_samp, self.wave_frames = [0] * self.S, [0] * self.S, [0] * self.S
+
+    # ------------------------------------------------------------------ the public calls
+    def push(self, chunks):
+        """chunks[s]: [n, n_bins] log-mel frames of stream s (numpy array or device tensor; None or n = 0: nothing) -> per stream the notes
+        that became final, as the dicts of transcript_notes, sorted by (onset, pitch).  With n_streams == 1 a bare array goes in and a bare
+        list comes out."""
+        chunks, bare = self._per_stream(chunks)
+        for s, a in enumerate(chunks):
+            self._append(s, a)
+        out = self._run([False] * self.S)
+        return out[0] if bare else out
+
+    def push_wave(self, chunks, sr=None):
+        """chunks[s]: samples of stream s at the feature rate (1-d, floating point in [-1, 1) or int16; any length; None: nothing).  A frame is
+        computed (hftt_clip_logmel over the retained samples) once the samples through t * hop + n_fft / 2 - 1 have arrived; then as push."""
+        fe = self.amt.config['feature']
+        if sr is not None and int(sr) != int(fe['sr']):
+            raise HfttError('push_wave takes samples at the feature rate %d (got %d): resample in front of the stream' % (fe['sr'], sr))
+        chunks, bare = self._per_stream(chunks)
+        for s, w in enumerate(chunks):
+            if w is None:
+                continue
+            self._append_wave(s, w)
+            self._append(s, self._wave_frames(s, False))
+        out = self._run([False] * self.S)
+        return out[0] if bare else out
+
+    def close(self, which=None):
+        """End the streams `which` (default: all that are open): pad as transcript / transcript_stride do, run the remaining clips, deliver
+        the file's last rows and return the rest of the notes, per stream (a bare list with n_streams == 1)."""
+        which = [s for s in range(self.S) if not self.closed[s]] if which is None else [int(s) for s in ([which] if np.isscalar(which) else which)]
+        closing = [False] * self.S
+        for s in which:
+            if self.closed[s]:
+                raise HfttError('close: stream %d is closed already' % s)
+            if self.wave[s] is not None:
+                self._append(s, self._wave_frames(s, True))
+            closing[s] = True
+        out = self._run(closing)
+        return out[0] if self.S == 1 else out
+
+    # ------------------------------------------------------------------ the parts
+    def _per_stream(self, chunks):
+        bare = self.S == 1 and not isinstance(chunks, (list, tuple))
+        chunks = [chunks] if bare else list(chunks)
+        if len(chunks) != self.S:
+            raise HfttError('NoteStream: %d chunks for %d streams' % (len(chunks), self.S))
+        return chunks, bare
+
+    def _append(self, s, a):
+        from hftt_hip import ops
+        if a is None:
+            return
+        n_bins = self.tail[s].shape[1]
+        if torch.is_tensor(a):
+            ops._need_cuda(a)
+            x = a.to(device=self.amt.device, dtype=torch.float32).reshape(-1, n_bins)
+        else:
+            x = torch.from_numpy(np.array(a, dtype=np.float32).reshape(-1, n_bins)).to(self.amt.device)
+        if x.shape[0] == 0:
+            return
+        if self.closed[s]:
+            raise HfttError('NoteStream: stream %d is closed' % s)
+        self.tail[s] = torch.cat([self.tail[s], x], dim=0)
+        self.n[s] += x.shape[0]
+
+    def _append_wave(self, s, w):
+        w = torch.as_tensor(w)
+        if w.dim() != 1:
+            raise HfttError('push_wave: stream %d: samples are 1-d (mono), got shape %s' % (s, tuple(w.shape)))
+        if w.dtype == torch.int16:
+            w = w.to(self.amt.device).float() * (1.0 / 32768.0)
+        elif w.dtype.is_floating_point:
+            w = w.to(device=self.amt.device, dtype=torch.float32)
+        else:
+            raise HfttError('push_wave: stream %d: samples are int16 or floating point, got %s' % (s, w.dtype))
+        if w.numel() and self.closed[s]:
+            raise HfttError('NoteStream: stream %d is closed' % s)
+        self.wave[s] = w if self.wave[s] is None else torch.cat([self.wave[s], w])
+        self.n_samp[s] += w.numel()
+
+    def _wave_frames(self, s, last):
+        """the frames of stream s that its samples complete (last: all 1 + n / hop of the file, zeros to the right of the samples)"""
+        from hftt_hip import ops
+        amt, fe = self.amt, self.amt.config['feature']
+        hop, n_fft = fe['hop_sample'], fe['fft_bins']
+        if amt._logmel is None:
+            if fe['fft_bins'] != fe['window_length']:
+                raise HfttError('window_length must equal fft_bins')
+            amt._logmel = ops.LogMel(amt.device, sr=fe['sr'], n_fft=n_fft, hop=hop, n_mels=fe['mel_bins'], log_offset=fe['log_offset'])
+        t0 = self.wave_frames[s]
+        t1 = 1 + self.n_samp[s] // hop if last else max(t0, (self.n_samp[s] - n_fft // 2) // hop + 1 if self.n_samp[s] >= n_fft // 2 else 0)
+        if t1 <= t0:
+            return None
+        table = ops.WaveTable([self.wave[s]], amt.device, dtype='float32')
+        spec = ops.clip_logmel(table, amt._logmel, [0], [t0 - self.wave0[s] // hop], t1 - t0, 0.0)       # [1, n_mels, t1 - t0]
+        self.wave_frames[s] = t1
+        keep = max(self.wave0[s], (t1 * hop - n_fft // 2) // hop * hop)           # a multiple of hop, n_fft / 2 samples behind the next frame
+        keep = max(keep, 0)
+        self.wave[s] = self.wave[s][keep - self.wave0[s]:]
+        self.wave0[s] = keep
+        return spec[0].T.contiguous()
+
+    def _roll_rows(self, s):
+        """F of transcript / transcript_stride for the n frames of stream s"""
+        cin = self.amt.config['input']
+        n, T = self.n[s], cin['num_frame']
+        if self.n_offset is None:
+            return int(np.ceil(n / T) * T)
+        tmp_len = n + cin['margin_b'] + cin['margin_f'] + self.step
+        return n + int(np.ceil(tmp_len / self.step) * self.step) - tmp_len
+
+    def _run(self, closing):
+        """rounds of: the ready clips of all streams (at most half a ring per stream) -> model -> stitch -> one decoder step"""
+        from hftt_hip import ops
+        amt, st, S, step = self.amt, self.st, self.S, self.step
+        cin, cf = amt.config['input'], amt.config['feature']
+        hop_sec = float(cf['hop_sample'] / cf['sr'])
+        H = st.H
+        notes = [[] for _ in range(S)]
+        while True:
+            clips, new_rows, close_now = [], [0] * S, [False] * S
+            for s in range(S):
+                if self.closed[s]:
+                    continue
+                F = self._roll_rows(s) if closing[s] else None
+                k = 0
+                while k < self.per_round:
+                    i = self.next[s]
+                    ready = i < self.n[s] if closing[s] else i - self.front + self.width <= self.n[s]
+                    if not ready:
+                        break
+                    length = step if F is None else max(0, min(step, F - i))
+                    clips.append((s, i, length))
+                    new_rows[s] += length
+                    self.next[s] = i + step
+                    k += 1
+                if closing[s] and self.next[s] >= self.n[s]:                     # its last clips are in this round: the rows up to F follow
+                    close_now[s] = True
+            if not clips and not any(close_now):
+                break
+            if clips:
+                rows = [0]
+                for s in range(S):
+                    rows.append(rows[-1] + self.tail[s].shape[0])
+                feature = torch.cat(self.tail, dim=0) if S > 1 else self.tail[0]
+                if feature.shape[0] == 0:
+                    feature = torch.zeros(1, feature.shape[1], dtype=torch.float32, device=amt.device)
+                table = torch.tensor(rows + [s for s, _, _ in clips] + [i - self.front - self.tail0[s] for s, i, _ in clips], dtype=torch.int32).to(amt.device)
+                nc = len(clips)
+                frow, wf, ws = table[:S + 1], table[S + 1:S + 1 + nc], table[S + 1 + nc:]
+                amt.model.eval()
+                for b0 in range(0, nc, amt.batch_size):
+                    b1 = min(b0 + amt.batch_size, nc)
+                    spec = ops.clip_windows(feature.contiguous(), frow, wf[b0:b1], ws[b0:b1], self.width, cin['min_value'])
+                    with torch.no_grad():
+                        o = amt.model(spec)
+                    for length in sorted({c[2] for c in clips[b0:b1]}):
+                        sel = [q for q in range(b0, b1) if clips[q][2] == length]
+                        if length == 0:
+                            continue
+                        idx = torch.tensor([q - b0 for q in sel], device=amt.device)
+                        heads = [o[self.h0 + k] if len(sel) == b1 - b0 else o[self.h0 + k].index_select(0, idx) for k in range(4)]
+                        ops.stitch(*heads, st.rings_flat, [clips[q][0] * H + clips[q][1] % H for q in sel], src0=self.src0, length=length)
+            for s in range(S):
+                if close_now[s]:                                                # rows that no clip covers are zero rows, as in transcript_notes
+                    F, have = self._roll_rows(s), st.row_end[s] + new_rows[s]
+                    for r in range(have, F):
+                        for ring in st.rings_flat:
+                            ring[s * H + r % H].zero_()
+                    new_rows[s] += max(0, F - have)
+                    self.closed[s] = True
+                keep = max(self.tail0[s], min(self.next[s] - self.front, self.n[s]))
+                if keep > self.tail0[s]:
+                    self.tail[s] = self.tail[s][keep - self.tail0[s]:]
+                    self.tail0[s] = keep
+            st.deliver(new_rows, close_now)
+            pitch, vel, t_on, t_off, heads, overflow = (x.numpy() for x in ops.notes_stream_step(st, hop_sec, host=True, **self.kw))
+            for s in range(S):
+                if overflow[s]:
+                    raise HfttError('NoteStream: stream %d: an undecided stretch (a plateau at or above a threshold) outgrew the ring of %d rows: '
+                                    'open the stream with a larger history=' % (s, H))
+                a, b = int(heads[s]), int(heads[s + 1])
+                notes[s] += [(float(t_on[q]), int(pitch[q]), float(t_off[q]), int(vel[q])) for q in range(a, b)]
+        out = []
+        for s in range(S):
+            p = np.array([x[1] for x in notes[s]], np.int64)
+            t = np.array([x[0] for x in notes[s]], np.float64)
+            order = np.lexsort((p, t))                                          # by onset, then pitch (amt.py:343)
+            out.append([{'pitch': notes[s][q][1], 'onset': notes[s][q][0], 'offset': notes[s][q][2], 'velocity': notes[s][q][3]} for q in order])
+        return out
 
 
 # ---------------------------------------------------------------------- helpers
