@@ -42,7 +42,12 @@ struct AbCfg {
   static constexpr int Q_ELEMS = 32 * RSQ;
   static constexpr int S_ELEMS = 32 * RSS;
   static constexpr int ELEMS = K_ELEMS + 2 * Q_ELEMS + S_ELEMS;
-  static constexpr int LDS_BYTES = ELEMS * (F32 ? 4 : 2) + 96 * 4;
+  static constexpr int LDS_LOOP = ELEMS * (F32 ? 4 : 2) + 96 * 4;
+  // bf16 dK / dV leave through per-wave LDS patches of 2 x 32 rows of DH + 8 halves (the epilogue): at dh = 32 and eight key tiles they are
+  // larger than the loop's images (40,960 against 38,784 bytes; what the last wave kept of dV past the allocation read back as zeros)
+  static constexpr int RSE = DH + 8;
+  static constexpr int LDS_EPI = F32 ? 0 : KT * 2 * 32 * RSE * 2;
+  static constexpr int LDS_BYTES = LDS_LOOP > LDS_EPI ? LDS_LOOP : LDS_EPI;
   static constexpr int NTHR = KT * 64;
 };
 
@@ -464,7 +469,7 @@ __global__ __launch_bounds__(KT * 64, HFTT_AB_WAVES(NPASS, KT, HB)) void attn_bw
     // is 8 bytes per lane into 32 different rows per instruction.  Written row-major into the wave's own LDS patch and read back as 16 bytes
     // per lane, eight lanes cover the 128-byte row segment of this head: whole sectors per instruction (the scattered form wrote up to 2.7x
     // the bytes to HBM on the [S, 2d] cross-attention layout, whose 1 KB row pitch defeats the L2's write combining).
-    constexpr int RSE = DH + 8;
+    constexpr int RSE = Cfg::RSE;
     __syncthreads();                                           // every wave is done with the K / Q / dO / dS images
     unsigned short* ek = reinterpret_cast<unsigned short*>(smem) + wave * (2 * 32 * RSE);
     unsigned short* ev = ek + 32 * RSE;

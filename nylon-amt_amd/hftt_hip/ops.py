@@ -374,15 +374,21 @@ def _attn_desc(q, k, v, n_heads, npass, drop_p, drop_site, drop_seed, planes=Fal
     return d
 
 
-def attn_fwd(q, k, v, n_heads, npass=3, want_probs=False, drop_p=0.0, drop_site=0, drop_seed=0, out_dtype=torch.float32, planes=False):
+def attn_fwd(q, k, v, n_heads, npass=3, want_probs=False, drop_p=0.0, drop_site=0, drop_seed=0, out_dtype=torch.float32, planes=False, outs=None):
     """q [n_seq, Lq, d], k/v [n_seq, Lk, d] (any row/seq strides) -> out [n_seq, Lq, d], row stats [n_seq, H, Lq, 2](, probs).
-    planes (npass 2): q, k, v hold f16-pair planes (to_planes / a projection with SL_C_F16PAIR) instead of fp32 values."""
+    planes (npass 2): q, k, v hold f16-pair planes (to_planes / a projection with SL_C_F16PAIR) instead of fp32 values.
+    outs = (out, lse, probs): preallocated tensors to write into (out possibly strided; lse and probs contiguous; probs None without want_probs)."""
     _need_cuda(q, k, v)
     n_seq, Lq, dm = q.shape
     Lk = k.shape[1]
-    out = torch.empty(n_seq, Lq, dm, device=q.device, dtype=out_dtype)
-    lse = torch.empty(n_seq, n_heads, Lq, 2, device=q.device)     # (row max, 1/row sum)
-    probs = torch.empty(n_seq, n_heads, Lq, Lk, device=q.device) if want_probs else None
+    if outs is not None:
+        out, lse, probs = outs
+        out_dtype = out.dtype
+        assert lse.is_contiguous() and lse.dtype == torch.float32 and (not want_probs or (probs.is_contiguous() and probs.dtype == torch.float32))
+    else:
+        out = torch.empty(n_seq, Lq, dm, device=q.device, dtype=out_dtype)
+        lse = torch.empty(n_seq, n_heads, Lq, 2, device=q.device)     # (row max, 1/row sum)
+        probs = torch.empty(n_seq, n_heads, Lq, Lk, device=q.device) if want_probs else None
     d = _attn_desc(q, k, v, n_heads, npass, drop_p, drop_site, drop_seed, planes)
     d.out, d.o_seq_stride, d.ldo = out.data_ptr(), out.stride(0), out.stride(1)
     d.lse = lse.data_ptr()
