@@ -100,6 +100,9 @@ int hftt_prep_weights_x3(const float* params, uint16_t* whi, uint16_t* wlo, floa
  * W is the prepared matrix [N_pad, K] (K % 32 == 0, N_pad % 64 == 0, rows >= N zero): bf16 when npass == 1,
  * fp32 when npass == 3 (passed through the same pointer); npass 2 / 4: the hi plane in W and the lo plane in W_lo
  * (hftt_prep_weights_x3), A / C / residual / gate fp32.
+ * npass 2 / 4 without LayerNorm, K <= 256 and N == 256 (or K == 256 and N <= 256) take an A-stationary streaming form of the kernel with
+ * the same results to the bit.  Environment variable HFTT_NT_STREAM=0 (read at every such call, so one process can run both) keeps
+ * them on the tiled kernel.
  * --------------------------------------------------------------------------------------------- */
 #define HFTT_NT_A_BF16 1u
 #define HFTT_NT_C_BF16 2u      /* not with LayerNorm */
@@ -400,6 +403,13 @@ int hftt_dropout_bwd(float* g, int64_t n, float drop_p, uint32_t site, uint64_t 
 /* colsum: out[j] = beta*out[j] + sum_r x[r*ld + j], j < n (x fp32, or bf16 when x_bf16 != 0; out fp32) */
 int hftt_colsum(const float* x, int64_t rows, int64_t n, int64_t ld, float* out, float beta, float* ws, uint32_t x_bf16, void* stream);
 int64_t hftt_colsum_ws_bytes(int64_t rows, int64_t n);
+/* hftt_dropout_bwd and hftt_colsum in one pass over g (rows x n, row stride ld): every quad of g is read once, masked in place and summed.
+ * The element index of the keep decision is the element's offset r*ld + j in g (hftt_dropout_bwd over the rows*ld elements of the buffer
+ * counts the same); the columns [n, ld) of a row are neither read nor written.  g (masked) and out are bit-identical to the two calls;
+ * drop_p == 0: g is only read.  n % 4 == 0, ld % 4 == 0, g and ws 16-byte aligned, ws of hftt_colsum_ws_bytes(rows, n) bytes.  ADDED at ABI 8;
+ * HFTT_ABI_VERSION stays 8. */
+int hftt_dropout_bwd_colsum(float* g, int64_t rows, int64_t n, int64_t ld, float drop_p, uint32_t site, uint64_t seed, float* out, float beta,
+                            float* ws, uint32_t bf16, void* stream);
 /* heads: logits [S, ldl] with cols [0,V) velocity, V onset, V+1 offset, V+2 mpe ->
  *   velocity [.,V] raw, onset/offset/mpe sigmoid; time_major!=0: rows are (b,n,t) and outputs are (b,t,n). */
 int hftt_heads_split(const float* logits, int64_t ldl, float* onset, float* offset, float* mpe, float* velocity,

@@ -591,6 +591,53 @@ __global__ void colsum_stage1_kernel(const float* __restrict__ x, long rows, lon
   else { for (long r = r0; r < r1; r++) acc += x[r * ld + j]; }
   ws[(long)sp * n + j] = acc;
 }
+// Stage 1 with the dropout backward in it: the same 16 row splits and the same row order per column as colsum_stage1_kernel, one quad of
+// columns per thread.  A quad is read once, masked by its site's keep decisions (one hash per quad: the element index is its offset r * ld + j
+// in the buffer, as dropout_bwd_kernel counts it), written back in place and added -- as the value that was stored, so a bf16 buffer adds its
+// rounding and the product never fuses into the sum.  DCS_RB rows are in flight per thread: the loads may not pass the stores of the same
+// buffer on their own.  drop_p == 0: nothing is masked or written.
+constexpr int DCS_RB = 8;
+__global__ __launch_bounds__(256) void dropout_bwd_colsum_stage1_kernel(float* gbuf, long rows, long n, long ld, float drop_p, uint32_t site, uint64_t seed,
+                                                                        float* __restrict__ ws, uint32_t bf) {
+  const long j = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (j >= n) return;                               // n % 4 == 0 (host check): a quad is inside the row or outside it
+  const uint32_t thr = hftt_keep_thr(drop_p);
+  const float inv_keep = hftt_keep_scale(drop_p);
+  const bool mask = drop_p > 0.f;
+  const int sp = blockIdx.y;
+  const long per = (rows + CS_SPLITS - 1) / CS_SPLITS;
+  const long r0 = sp * per;
+  long r1 = r0 + per; if (r1 > rows) r1 = rows;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (long r = r0; r < r1; r += DCS_RB) {
+    float4 a[DCS_RB];
+#pragma unroll
+    for (int u = 0; u < DCS_RB; u++) {              // unconditional, from a clamped row
+      const long rc = r + u < r1 ? r + u : r1 - 1;
+      a[u] = hftt_load4(gbuf, bf, rc * ld + j);
+    }
+#pragma unroll
+    for (int u = 0; u < DCS_RB; u++) {
+      if (r + u < r1) {
+        const long off = (r + u) * ld + j;
+        float v[4] = {a[u].x, a[u].y, a[u].z, a[u].w};
+        if (mask) {
+          const uint32_t k4 = hftt_keep_quad(seed, site, (uint64_t)off >> 2, thr);
+#pragma unroll
+          for (int e = 0; e < 4; e++) v[e] = ((k4 >> e) & 1u) ? __fmul_rn(v[e], inv_keep) : 0.f;
+          hftt_store4(gbuf, bf, off, v[0], v[1], v[2], v[3]);
+          if (bf) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) v[e] = bf2f(f2bf(v[e]));
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; e++) acc[e] += v[e];
+      }
+    }
+  }
+  *reinterpret_cast<float4*>(ws + (long)sp * n + j) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+}
 __global__ void colsum_stage2_kernel(const float* __restrict__ ws, long n, float* __restrict__ out, float beta) {
   const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
@@ -919,8 +966,23 @@ extern "C" int hftt_dropout_bwd(float* g, int64_t n, float drop_p, uint32_t site
 extern "C" int64_t hftt_colsum_ws_bytes(int64_t rows, int64_t n) { (void)rows; return (int64_t)CS_SPLITS * n * 4; }
 extern "C" int hftt_colsum(const float* x, int64_t rows, int64_t n, int64_t ld, float* out, float beta, float* ws, uint32_t x_bf16, void* stream) {
   HFTT_REQUIRE(x && out && ws && rows > 0 && n > 0 && ld >= n, "colsum: bad arguments");
+  // whole quads, 16-byte aligned: the quad-per-thread stage 1 with nothing to mask (drop_p = 0: x is only read) -- the same splits, the same
+  // row order per column, the same sums, in 16-byte loads with eight rows in flight
+  if (n % 4 == 0 && ld % 4 == 0 && (((uintptr_t)x | (uintptr_t)ws) & 15) == 0) {
+    if (int rc = hftt_launch<dropout_bwd_colsum_stage1_kernel>("colsum(1)", dim3((unsigned)((n / 4 + 255) / 256), CS_SPLITS), dim3(256), 0, (hipStream_t)stream,
+                                                               const_cast<float*>(x), (long)rows, (long)n, (long)ld, 0.f, 0u, (uint64_t)0, ws, x_bf16)) return rc;
+    return hftt_launch<colsum_stage2_kernel>("colsum(2)", dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, (long)n, out, beta);
+  }
   if (int rc = hftt_launch<colsum_stage1_kernel>("colsum(1)", dim3((unsigned)((n + 255) / 256), CS_SPLITS), dim3(256), 0, (hipStream_t)stream, x, (long)rows, (long)n, (long)ld, ws, x_bf16)) return rc;
   return hftt_launch<colsum_stage2_kernel>("colsum(2)", dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, (long)n, out, beta);
+}
+extern "C" int hftt_dropout_bwd_colsum(float* g, int64_t rows, int64_t n, int64_t ld, float drop_p, uint32_t site, uint64_t seed, float* out, float beta,
+                                       float* ws, uint32_t bf16, void* stream) {
+  HFTT_REQUIRE(g && out && ws && rows > 0 && n > 0 && ld >= n && drop_p >= 0.f && drop_p < 1.f, "dropout_bwd_colsum: bad arguments");
+  HFTT_REQUIRE(n % 4 == 0 && ld % 4 == 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)ws & 15) == 0, "dropout_bwd_colsum: n %% 4 == 0, ld %% 4 == 0, g and ws 16-byte aligned");
+  if (int rc = hftt_launch<dropout_bwd_colsum_stage1_kernel>("dropout_bwd_colsum(1)", dim3((unsigned)((n / 4 + 255) / 256), CS_SPLITS), dim3(256), 0, (hipStream_t)stream,
+                                                             g, (long)rows, (long)n, (long)ld, drop_p, site, seed, ws, bf16)) return rc;
+  return hftt_launch<colsum_stage2_kernel>("dropout_bwd_colsum(2)", dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, (long)n, out, beta);
 }
 extern "C" int hftt_heads_split(const float* logits, int64_t ldl, float* onset, float* offset, float* mpe, float* velocity,
                                 int32_t B, int32_t T, int32_t Nn, int32_t V, int32_t time_major, void* stream) {

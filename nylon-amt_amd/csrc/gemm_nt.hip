@@ -6,8 +6,9 @@
 //                         plane; v_mfma_f32_32x32x16_bf16; LDS rows padded to 80 B (conflict-free ds_read_b128).
 //   npass == 3 ("parity"): operands stay fp32 in LDS (rows of 33 floats: conflict-free ds_read_b32), weights come as a
 //                         prepared fp32 matrix; v_mfma_f32_32x32x2_f32 = exact fp32 FMA chains (<= 1e-3 parity mode).
-// bf16 mode with N a multiple of 256 and K <= 768 takes the A-stationary kernel further down (gemm_nt_as1_kernel); it and the split
-// modes' full tiles finish their rows in one shared row pass (row_pass).
+// bf16 mode with N a multiple of 256 and K <= 768 takes the A-stationary kernel further down (gemm_nt_as1_kernel), the split modes with
+// N <= 256 and K <= 256 theirs (gemm_nt_as3_kernel); both and the split modes' full tiles finish their rows in one shared row pass (row_pass).
+#include <cstdlib>
 #include <type_traits>
 #include "hftt_common.h"
 #include "x3_common.h"
@@ -454,44 +455,61 @@ __global__ __launch_bounds__(512) void gemm_nt_kernel(const hftt_gemm_nt_desc g)
 // Thread t owns chunks t, t + 512, ... of the block; (row, chunk) advance incrementally -- one integer division per thread instead of one
 // per load (the index math was ~20 % of the kernel's VALU time).  Rows past M or past the block read a clamped address and become zeros:
 // the loads stay unconditional (no branch, no early vmcnt wait).
-template <int BM_, typename CH>
-__device__ __forceinline__ void load_a_block(const hftt_gemm_nt_desc g, const long m0, unsigned short* As, const int RSA) {
+// The walk itself: (row, chunk) of this thread's next chunk of a block with cpr chunks per row.
+struct AWalk {
+  int cpr, drow, dch, row, ch;
+  __device__ __forceinline__ AWalk(int cpr_) : cpr(cpr_), drow(512 / cpr_), dch(512 - (512 / cpr_) * cpr_) {
+    row = threadIdx.x / cpr; ch = threadIdx.x - row * cpr;
+  }
+  __device__ __forceinline__ void next() {
+    row += drow; ch += dch;
+    if (ch >= cpr) { ch -= cpr; row++; }
+  }
+};
+// The loads of the next NCH chunks of the walk, all issued, none waited for (the split form keeps them in flight under its MFMA loop).  A chunk
+// past M or past the block reads a clamped row and is NOT zeroed here: a select on the loaded value makes hipcc branch around the load and wait
+// for each one in turn.  a_chunk_live() says at the LDS write whether the chunk counts.
+template <int BM_, typename CH, int NCH>
+__device__ __forceinline__ void a_block_issue(const hftt_gemm_nt_desc& g, const long m0, AWalk& w, CH (&v)[NCH]) {
   constexpr bool ABF = std::is_same<CH, uint4>::value;
   using T = typename std::conditional<ABF, unsigned short, float>::type;
   constexpr int E = 16 / sizeof(T);                // elements per chunk
   const T* A = reinterpret_cast<const T*>(g.A);
-  const int cpr = g.K / E;                         // chunks per row
-  const int total = BM_ * cpr;
-  const int drow = 512 / cpr, dch = 512 - drow * cpr;
-  int row = threadIdx.x / cpr, ch = threadIdx.x - row * cpr;
+#pragma unroll
+  for (int u = 0; u < NCH; u++) {
+    const long grow = m0 + w.row;
+    const long gr = (w.row < BM_ && grow < g.M) ? grow : (m0 < g.M ? m0 : 0);
+    v[u] = *reinterpret_cast<const CH*>(A + gr * g.lda + w.ch * E);
+    w.next();
+  }
+}
+template <int BM_>
+__device__ __forceinline__ bool a_chunk_live(const hftt_gemm_nt_desc& g, const long m0, const AWalk& w) { return w.row < BM_ && m0 + w.row < g.M; }
+template <int BM_, typename CH>
+__device__ __forceinline__ void load_a_block(const hftt_gemm_nt_desc g, const long m0, unsigned short* As, const int RSA) {
+  constexpr bool ABF = std::is_same<CH, uint4>::value;
+  AWalk w(g.K / (ABF ? 8 : 4));
+  const int total = BM_ * w.cpr;
   for (int base = 0; base < total; base += 512 * 8) {
     CH v[8];
-    int rr[8], cc[8];
+    AWalk at = w;
+    a_block_issue<BM_, CH, 8>(g, m0, w, v);
 #pragma unroll
     for (int u = 0; u < 8; u++) {
-      rr[u] = row; cc[u] = ch;
-      const bool in = row < BM_;
-      const long grow = m0 + row;
-      const long gr = (in && grow < g.M) ? grow : (m0 < g.M ? m0 : 0);
-      const CH t = *reinterpret_cast<const CH*>(A + gr * g.lda + ch * E);
-      if constexpr (ABF) v[u] = (in && grow < g.M) ? t : make_uint4(0u, 0u, 0u, 0u);
-      else v[u] = (in && grow < g.M) ? t : make_float4(0.f, 0.f, 0.f, 0.f);
-      row += drow; ch += dch;
-      if (ch >= cpr) { ch -= cpr; row++; }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u++)
-      if (rr[u] < BM_) {
-        // (fp32: the address as chunk pair + half -- with rr * RSA + cc * 4 hipcc keeps fewer loads in flight)
-        unsigned short* dst = ABF ? As + rr[u] * RSA + (cc[u] << 3) : As + rr[u] * RSA + ((cc[u] >> 1) << 3) + (cc[u] & 1) * 4;
+      if (at.row < BM_) {
+        // (fp32: the address as chunk pair + half -- with row * RSA + ch * 4 hipcc keeps fewer loads in flight)
+        unsigned short* dst = ABF ? As + at.row * RSA + (at.ch << 3) : As + at.row * RSA + ((at.ch >> 1) << 3) + (at.ch & 1) * 4;
+        const bool live = a_chunk_live<BM_>(g, m0, at);
         if constexpr (ABF) {
-          *reinterpret_cast<uint4*>(dst) = v[u];
+          *reinterpret_cast<uint4*>(dst) = live ? v[u] : make_uint4(0u, 0u, 0u, 0u);
         } else {
           typedef __bf16 bf4_t __attribute__((ext_vector_type(4)));
-          const f32x4 fv = {v[u].x, v[u].y, v[u].z, v[u].w};
+          const f32x4 fv = {live ? v[u].x : 0.f, live ? v[u].y : 0.f, live ? v[u].z : 0.f, live ? v[u].w : 0.f};
           *reinterpret_cast<uint2*>(dst) = __builtin_bit_cast(uint2, __builtin_convertvector(fv, bf4_t));
         }
       }
+      at.next();
+    }
   }
 }
 
@@ -709,6 +727,233 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, MODE == 
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Split modes (npass 2 / 4), A-stationary form: N <= 256 (one N tile), K <= 256.  The same tall, short-K products as above -- the
+// embedding (K = 96), the heads and their dX (K = 256 / 192) -- in three MFMA passes on split operands.  A persistent grid of one
+// workgroup per CU walks the 64-row blocks (blk += gridDim.x; the workgroups never talk to each other).  Per block: the A rows are read
+// from HBM once, split once (x3_split4) into a hi and a lo plane in LDS, and the prepared weight planes W / W_lo stream from L2 through
+// a double-buffered ring that keeps running across the blocks (one N tile: k tile 0 follows k tile KT - 1).  The next block's A loads
+// are issued in the last k step, behind the last weight load, and stay in flight in registers under that step's MFMAs and the row pass.
+// Per accumulator the MFMAs come in gemm_nt_kernel's order (k ascending in k16 chunks; lo.hi, hi.lo, hi.hi within a chunk) and the epilogue
+// is its text -- acc + bias, ReLU, out_scale, stage, row_pass -- so the results are its results bit for bit.
+//   XE   X3_F16 / X3_BF16 (the descriptor's npass)
+//   NCH  16-byte A chunks per thread: 4 (K <= 128) or 8 (K <= 256)
+//   PF2  K / 32 is even: weight tiles are loaded two k steps ahead (see WRegs)
+// LDS: the A planes, 64 x (K + 8) x 2 x 2 B <= 66 KB, and in the same bytes, once the k loop is done, the staged 64 x 260 fp32 tile
+// (65 KB) + the ring, 2 x 2 planes x 256 x 40 x 2 B = 80 KB: 145 - 146 KB, ONE workgroup per CU.  Registers: 8 waves = two per SIMD, up
+// to 256 VGPRs each (32 accumulators, 16 or 32 of weight staging, 4 * NCH of prefetched A, the row pass with 8 (NCH 4) or 4 rows in
+// flight: 216 - 249 as built); no scratch (tests/test_nt_streaming_resources.py).
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int AS3_BM = 64;
+constexpr int AS3_RSW = 40;
+constexpr int AS3_W_ELEMS = 2 * 256 * AS3_RSW;           // one ring buffer: hi plane, then lo plane
+constexpr int AS3_STAGE_LD = 256 + 4;
+constexpr int as3_a_bytes(int nch) {                     // A planes at the largest K of the form, or the stage
+  const int a = AS3_BM * (nch * 32 + 8) * 2 * 2, s = AS3_BM * AS3_STAGE_LD * 4;
+  return a > s ? a : s;
+}
+constexpr int as3_lds_bytes(int nch) { return as3_a_bytes(nch) + 2 * AS3_W_ELEMS * 2; }
+
+template <int XE, int NCH, bool PF2>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_nt_as3_kernel(const hftt_gemm_nt_desc g, const int nblk) {
+  constexpr int BM_ = AS3_BM, BN = 256, WN = 4, TN = 2, RSW = AS3_RSW, STAGE_LD = AS3_STAGE_LD;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int K = g.K;
+  const int RSA = K + 8;
+  unsigned short* As = reinterpret_cast<unsigned short*>(smem);                          // hi plane, lo plane at + BM_ * RSA
+  unsigned short* Ws = reinterpret_cast<unsigned short*>(smem + as3_a_bytes(NCH));
+  float* stage = reinterpret_cast<float*>(smem);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const int lr = lane & 31, lh = lane >> 5;
+  const int KT = K / 32;
+  const unsigned short* Wb = reinterpret_cast<const unsigned short*>(g.W);
+  const unsigned short* Wlo = reinterpret_cast<const unsigned short*>(g.W_lo);
+
+  // weight tile kt: two 16-byte chunks of the hi plane and two of the lo plane per thread (zeroed at the start: left undefined, hipcc kept the
+  // sets in scratch).  Rows past N read row N - 1 (their columns are never stored).  PF2 (K / 32 even): two sets -- tile kt waits in set kt & 1,
+  // loaded two k steps before it is read from the ring, so an L2 round trip has a whole step of MFMAs to hide behind; an odd K / 32 (the
+  // embedding's 3) would swap the sets' roles from block to block and loads one step ahead into one set.  The scheduling barrier keeps
+  // the loads where they are written: left alone, hipcc sinks them to the ring write at the end of the step.
+  struct WRegs { uint4 h0, h1, l0, l1; };
+  const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
+  WRegs w0 = {z4, z4, z4, z4}, w1 = {z4, z4, z4, z4};
+  const int wrow = tid >> 2, wch = tid & 3;
+  const long wg0 = (long)(wrow < g.N ? wrow : g.N - 1) * K + wch * 8, wg1 = (long)(wrow + 128 < g.N ? wrow + 128 : g.N - 1) * K + wch * 8;
+  const int ws0 = wrow * RSW + wch * 8, ws1 = ws0 + 128 * RSW;
+  auto wload = [&](WRegs& w, int kt) __attribute__((always_inline)) {
+    w.h0 = *reinterpret_cast<const uint4*>(Wb + wg0 + kt * 32); w.h1 = *reinterpret_cast<const uint4*>(Wb + wg1 + kt * 32);
+    w.l0 = *reinterpret_cast<const uint4*>(Wlo + wg0 + kt * 32); w.l1 = *reinterpret_cast<const uint4*>(Wlo + wg1 + kt * 32);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto wstore = [&](const WRegs& w, int buf) __attribute__((always_inline)) {
+    unsigned short* d = Ws + buf * AS3_W_ELEMS;
+    *reinterpret_cast<uint4*>(d + ws0) = w.h0; *reinterpret_cast<uint4*>(d + ws1) = w.h1;
+    *reinterpret_cast<uint4*>(d + BN * RSW + ws0) = w.l0; *reinterpret_cast<uint4*>(d + BN * RSW + ws1) = w.l1;
+  };
+  float4 av[NCH];
+  auto a_issue = [&](long m0) __attribute__((always_inline)) {
+    AWalk w(K / 4);
+    a_block_issue<BM_, float4, NCH>(g, m0, w, av);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto a_commit = [&](long m0) __attribute__((always_inline)) {
+    AWalk w(K / 4);
+#pragma unroll
+    for (int u = 0; u < NCH; u++) {
+      if (w.row < BM_) {
+        uint2 hi, lo;
+        x3_split4<XE>(a_chunk_live<BM_>(g, m0, w) ? av[u] : make_float4(0.f, 0.f, 0.f, 0.f), hi, lo);
+        unsigned short* dst = As + w.row * RSA + w.ch * 4;
+        *reinterpret_cast<uint2*>(dst) = hi;
+        *reinterpret_cast<uint2*>(dst + BM_ * RSA) = lo;
+      }
+      w.next();
+    }
+  };
+
+  f32x16 acc[TN];
+  auto k_step = [&](int kt, int buf) __attribute__((always_inline)) {
+    const unsigned short* Wt = Ws + buf * AS3_W_ELEMS;
+#pragma unroll
+    for (int ks = 0; ks < 2; ks++) {
+      const unsigned short* pa = As + (wm * 32 + lr) * RSA + kt * 32 + ks * 16 + lh * 8;
+      const bf16x8 ah = lds_read_b128(pa), al = lds_read_b128(pa + BM_ * RSA);
+#pragma unroll
+      for (int j = 0; j < TN; j++) {
+        const unsigned short* pb = Wt + (wn * TN * 32 + j * 32 + lr) * RSW + ks * 16 + lh * 8;
+        const bf16x8 bh = lds_read_b128(pb), bl = lds_read_b128(pb + BN * RSW);
+        acc[j] = x3_mma<XE>(ah, al, bh, bl, acc[j]);
+      }
+    }
+  };
+
+  const uint32_t thr = hftt_keep_thr(g.drop_p);
+  const float inv_keep = hftt_keep_scale(g.drop_p);
+  // whole-row 16-byte stores with the table add / gate / dropout / residual per quad (gemm_nt_kernel's condition); the dispatch sends
+  // here only what either meets it or has none of the four (the heads: N = 131, bias only)
+  const bool rowpass = (g.N % 4 == 0) && (g.gate == nullptr || g.ldg % 4 == 0) && (g.residual == nullptr || g.ldr % 4 == 0) &&
+                       ((((uintptr_t)g.gate | (uintptr_t)g.residual | (uintptr_t)g.add_table) & 15) == 0);
+
+  float bv[TN];                                  // (loaded once: a load inside the block loop would wait for the prefetched A as well)
+#pragma unroll
+  for (int j = 0; j < TN; j++) {
+    const int col_l = wn * TN * 32 + j * 32 + lr;
+    bv[j] = (g.bias != nullptr && col_l < g.N) ? g.bias[col_l] : 0.f;
+  }
+  long blk = blockIdx.x;
+  wload(w0, 0);
+  if constexpr (PF2) wload(w1, 1);
+  a_issue(blk * BM_);
+  wstore(w0, 0);
+  int s = 0;                                     // !PF2: k steps so far -- tile s of the endless sequence sits in ring buffer s & 1
+  for (; blk < nblk; blk += gridDim.x) {
+    const long m0 = blk * BM_;
+    a_commit(m0);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < TN; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[j][r] = 0.f;
+    // In the last k step the first tile(s) of the next block go on their way, and behind them the next block's A (past the last block: a
+    // clamped row, unused) into registers.  The barrier behind the last step also says that every wave is done with the A planes: the
+    // stage may overwrite them.
+    if constexpr (PF2) {                           // tile kt in ring buffer kt & 1; at the top of a block tile 0 is in the ring, tile 1 in w1
+      for (int kt = 0; kt + 2 < KT; kt += 2) {
+        wload(w0, kt + 2); k_step(kt, 0); wstore(w1, 1);
+        __syncthreads();
+        wload(w1, kt + 3); k_step(kt + 1, 1); wstore(w0, 0);
+        __syncthreads();
+      }
+      wload(w0, 0); k_step(KT - 2, 0); wstore(w1, 1);
+      __syncthreads();
+      wload(w1, 1);
+      a_issue((blk + gridDim.x) * BM_);
+      k_step(KT - 1, 1); wstore(w0, 0);
+      __syncthreads();
+    } else {
+      for (int kt = 0; kt + 1 < KT; kt++) {
+        wload(w0, kt + 1); k_step(kt, s & 1); wstore(w0, (s & 1) ^ 1);
+        __syncthreads();
+        s++;
+      }
+      wload(w0, 0);
+      a_issue((blk + gridDim.x) * BM_);
+      k_step(KT - 1, s & 1); wstore(w0, (s & 1) ^ 1);
+      __syncthreads();
+      s++;
+    }
+
+#pragma unroll
+    for (int j = 0; j < TN; j++) {
+      const int col_l = wn * TN * 32 + j * 32 + lr;
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int row_l = wm * 32 + acc_row32(r, lh);
+        float v = acc[j][r] + bv[j];
+        if (g.act == 1) v = fmaxf(v, 0.f);
+        v *= g.out_scale;
+        stage[row_l * STAGE_LD + col_l] = v;
+      }
+    }
+    __syncthreads();
+    if (rowpass) {
+      // (a wave's rows in flight: all eight where the registers allow it -- one wait for the table / residual loads per block instead of two)
+      row_pass<BM_ / 8, NCH == 4 ? 8 : 4, false, false>(g, m0, 0, stage, STAGE_LD, lane * 4 < g.N, thr, inv_keep);
+    } else {
+      const int c4 = lane * 4;
+#pragma unroll 1
+      for (int rr = 0; rr < BM_ / 8; rr++) {
+        const int row_l = wave * (BM_ / 8) + rr;
+        const long row = m0 + row_l;
+        if (row >= g.M) break;                   // (wave-uniform)
+        const float4 sv = *reinterpret_cast<const float4*>(stage + row_l * STAGE_LD + c4);
+        float* cp = g.C + row * g.ldc + c4;
+        if (c4 + 4 <= g.N) {
+          *reinterpret_cast<float4*>(cp) = sv;
+        } else {                                 // the quad that N cuts: the columns [N, ldc) keep what they hold
+          if (c4 < g.N) cp[0] = sv.x;
+          if (c4 + 1 < g.N) cp[1] = sv.y;
+          if (c4 + 2 < g.N) cp[2] = sv.z;
+        }
+      }
+    }
+    __syncthreads();                             // the stage is read: the next block's A planes may take its place
+  }
+}
+
+// 0 = off: every split-mode product takes gemm_nt_kernel, as before the A-stationary form existed.  Read at every qualifying call, so one
+// process can run both (hftt_hip/plan.py nt_meta reads the same variable for the kernel's name).
+bool nt_as3_enabled() {
+  const char* e = getenv("HFTT_NT_STREAM");
+  return !(e != nullptr && e[0] == '0');
+}
+// does the A-stationary split form take this product?  (npass 2 / 4 without HFTT_NT_A_HI is the caller's test)
+bool nt_as3_takes(const hftt_gemm_nt_desc& d) {
+  if (d.ln_gamma != nullptr || d.K > 256 || !(d.N == 256 || (d.K == 256 && d.N <= 256))) return false;
+  if (d.ldc % 4 != 0 || ((uintptr_t)d.C & 15) != 0) return false;
+  const bool rich = d.add_table || d.gate || d.drop_p > 0.f || d.residual;
+  const bool quads = (d.N % 4 == 0) && (!d.gate || d.ldg % 4 == 0) && (!d.residual || d.ldr % 4 == 0) &&
+                     ((((uintptr_t)d.gate | (uintptr_t)d.residual | (uintptr_t)d.add_table) & 15) == 0);
+  return (quads || !rich) && nt_as3_enabled();
+}
+template <int XE, int NCH, bool PF2>
+int launch_nt_as3(const hftt_gemm_nt_desc& d, hipStream_t st) {
+  constexpr int lds = as3_lds_bytes(NCH);
+  const int nblk = (d.M + AS3_BM - 1) / AS3_BM;
+  int wgs = 0;
+  if (int rc = hftt_resident_wgs<gemm_nt_as3_kernel<XE, NCH, PF2>>("gemm_nt", 512, lds, &wgs)) return rc;
+  dim3 grid((unsigned)(nblk < wgs ? nblk : wgs), 1, 1);
+  return hftt_launch<gemm_nt_as3_kernel<XE, NCH, PF2>>("gemm_nt", grid, dim3(512), lds, st, d, nblk);
+}
+template <int XE>
+int dispatch_nt_as3(const hftt_gemm_nt_desc& d, hipStream_t st) {
+  const bool pf2 = (d.K / 32) % 2 == 0;
+  if (d.K <= 128) return pf2 ? launch_nt_as3<XE, 4, true>(d, st) : launch_nt_as3<XE, 4, false>(d, st);
+  return pf2 ? launch_nt_as3<XE, 8, true>(d, st) : launch_nt_as3<XE, 8, false>(d, st);
+}
+
 template <int BM_, int MODE, bool EW = false, int PF = 1>
 int launch_nt_as1(const hftt_gemm_nt_desc& d, hipStream_t st) {
   int lds = (BM_ * (d.K + 8) + 2 * 256 * 40) * 2;
@@ -807,12 +1052,12 @@ extern "C" int hftt_gemm_nt(const hftt_gemm_nt_desc* d, void* stream) {
   HFTT_REQUIRE(d->ln_gamma == nullptr || (d->ln_beta != nullptr && d->ldc == d->N), "gemm_nt: LN needs beta and ldc == N");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->npass == 3) return dispatch_nt<3>(*d, st);
-  if (d->npass == 2) return dispatch_nt<2>(*d, st);
+  if (d->npass == 2) return nt_as3_takes(*d) ? dispatch_nt_as3<X3_F16>(*d, st) : dispatch_nt<2>(*d, st);
 #ifdef HFTT_GRAD_HI_BUILD
   if (d->npass == 4 && (d->io_flags & HFTT_NT_A_HI)) return dispatch_nt<5>(*d, st);
 #else
   HFTT_REQUIRE(!(d->io_flags & HFTT_NT_A_HI), "gemm_nt: this library was built without the gradient-rounding option (HFTT_BUILD_GRAD_HI=1 python nylon-amt_amd/build.py)");
 #endif
-  if (d->npass == 4) return dispatch_nt<4>(*d, st);
+  if (d->npass == 4) return nt_as3_takes(*d) ? dispatch_nt_as3<X3_BF16>(*d, st) : dispatch_nt<4>(*d, st);
   return dispatch_nt_bf16(*d, st);
 }

@@ -304,6 +304,9 @@ class HfttEngine:
             elif fn == 'dropout_bwd':
                 g, n, site, gbf = args
                 rc = L.hftt_dropout_bwd(g, n, p, site, seed, gbf, stream) if p > 0.0 else 0
+            elif fn == 'dropout_bwd_colsum':
+                g, rows, n, ld, site, out, beta, wsp, gbf = args
+                rc = L.hftt_dropout_bwd_colsum(g, rows, n, ld, p, site, seed, out, beta, wsp, gbf, stream)
             else:
                 raise _capi.HfttError('unknown plan op %s' % fn)
             if prof is not None:

@@ -62,6 +62,10 @@ def nt_meta(npass, a_hi, M, N, K, a_bf, c_bf, gate_bf, res_bf, add_table, gate, 
             kname = 'gemm_nt_as1_kernel<%d, 1, false, 2>' % (32 if ln else 64)
         else:
             kname = 'gemm_nt_as1_kernel<32, 2, false, 1>'
+    elif (npass in (2, 4) and not a_hi and not ln and K <= 256 and (N == 256 or (K == 256 and N <= 256)) and (N % 4 == 0 or not rich)
+          and _env_on('HFTT_NT_STREAM')):
+        # (nt_as3_takes: the A-stationary split form; the C side reads HFTT_NT_STREAM at every call, this name is fixed when the plan is built)
+        kname = 'gemm_nt_as3_kernel<%d, %d, %s>' % (npass, 4 if K <= 128 else 8, _tf((K // 32) % 2 == 0))
     else:
         kname = 'gemm_nt_kernel<%d, %d, %s>' % (bn, 5 if a_hi else npass, _tf(ln))
     return {'kernel': kname, 'flops': 2.0 * M * N * K, 'bytes': float(nbytes), 'shape': (M, N, K)}
@@ -790,8 +794,9 @@ class PlanBuilder:
         for i in reversed(range(e.Le)):
             self.enc_layer_bwd(f'enc{i}', f'{enc_}layers_freq.{i}.', Se, BT, F, e.He, ws['enc_in'][i], Ge, dx_fp32=(i == 0))     # the embedding stage below reads fp32
         # ---- embedding ----
-        plan.append(('dropout_bwd', (eGA, Se * d, ws['sites']['embed'], 1 if bs else 0), 'dropout_bwd', None))
-        plan.append(('colsum', (eGA, BT, F * d, F * d, e.G(enc_ + 'pos_embedding_freq.weight'), 0.0, cs_ws, 1 if bs else 0), 'colsum', None))
+        # (the dropout mask and the position-embedding gradient's column sum in one pass over the gradient: ld == n, so the element index is row * n + col)
+        plan.append(('dropout_bwd_colsum', (eGA, BT, F * d, F * d, ws['sites']['embed'], e.G(enc_ + 'pos_embedding_freq.weight'), 0.0, cs_ws, 1 if bs else 0),
+                     'dropout_bwd_colsum', None))
         self.tn(Se, d, e.Kp, eGA, d, b['win'].data_ptr(), e.Kp, [(0, d, e.dweff.data_ptr(), e.dbeff.data_ptr())], out_scale=math.sqrt(d))
         plan.append((self.lib.hftt_embed_fold_bwd, (C.byref(e.fold),), 'embed_fold_bwd', None))
         marks.append((len(plan), 0, o_dec))
