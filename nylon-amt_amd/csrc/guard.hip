@@ -2,7 +2,7 @@
 // factor, apply / skip, counters) in a 32-byte device record, and the Adam kernel that reads the record: it skips a step whose norm is not
 // finite, scales the gradient by the clip factor on the fly and applies decoupled weight decay.  No float atomics, no cross-workgroup
 // tickets: every sum has one fixed order, so the record is bitwise reproducible.  Entry points and the torch definitions they restate:
-// include/hftt_hip.h.  The unguarded step (hftt_adam_step / adam_kernel, csrc/elementwise.hip) is untouched and stays the default path.
+// include/hftt_hip.h.  The unguarded step (hftt_adam_step / adam_kernel) stays the default path; all three Adam kernels share one update.
 // The grouped forms (hftt_grad_norm_groups, hftt_adam_step_groups) read a per-quad group map: per-group learning rate and decay, and frozen
 // groups whose quads are neither loaded nor stored (fine-tuning).
 #include "hftt_common.h"
@@ -69,18 +69,16 @@ __global__ __launch_bounds__(GN_THREADS) void grad_norm_finalize_kernel(const do
   }
 }
 
-// ------------------------------------------------------------------ guarded Adam
-// adam_kernel's update on gr = g * (grad_scale * coef), behind p *= d (decoupled decay, d = 1 - lr * weight_decay); nothing is written
-// when the record says skip.  With coef == 1 and d == 1 every operation reproduces adam_kernel's bits.
-//
-// adam_kernel writes  m = beta1 * m + omb1 * gr;  v = beta2 * v + omb2 * gr * gr;  p -= lr_c * m / (sqrtf(v) * inv_sqrt_bc2 + eps)  and leaves
-// the choice of which product joins which sum in one fma to the compiler -- which chooses differently in its quad loop and in its tail
-// (and differently again for the same text behind `g * s` with s read from memory).  Bit-identity cannot rest on that, so the two forms
-// adam_kernel compiles to are written out here with contraction switched off around them: QUAD m = fma(beta1, m, omb1 gr),
-// v = fma(gr, omb2 gr, beta2 v); tail m = fma(omb1, gr, beta1 m), v = gr (omb2 gr) + beta2 v unfused; both den = fma(sqrt v, inv_sqrt_bc2, eps)
-// and an unfused p - q.  tests/test_guard_gpu.py::test_inactive_guard_is_bit_identical_to_adam_step holds the two kernels together.
+// ------------------------------------------------------------------ Adam: one update, three kernels
+// m = beta1 * m + omb1 * gr;  v = beta2 * v + omb2 * gr * gr;  p = p * d - lr_c * m / (sqrtf(v) * inv_sqrt_bc2 + eps)  on gr = g * s, with
+// d = 1 - lr * weight_decay (decoupled decay; the unguarded step passes d = 1, and p * 1.0f is exact) and s = grad_scale (* the clip factor
+// in the guarded forms).  The rule: the update is written out, with contraction switched off around it, so that which product joins which
+// sum in one fma is this text's choice and never a compiler's -- the default optimizer's bits do not move with a compiler update, and the
+// three kernels agree by construction (tests/test_guard_gpu.py::test_inactive_guard_is_bit_identical_to_adam_step).  The quad loops and the
+// tails use two operand orders; they are historical bits that are kept: QUAD m = fma(beta1, m, omb1 gr), v = fma(gr, omb2 gr, beta2 v);
+// tail m = fma(omb1, gr, beta1 m), v = gr (omb2 gr) + beta2 v unfused; both den = fma(sqrt v, inv_sqrt_bc2, eps) and an unfused p - q.
 template <bool QUAD>
-__device__ __forceinline__ void adam_guarded_update(float& p, float g, float& m, float& v, float s, float d, float lr_c, float beta1, float beta2,
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float s, float d, float lr_c, float beta1, float beta2,
                                                     float omb1, float omb2, float eps, float inv_sqrt_bc2) {
 #pragma clang fp contract(off)
   const float gr = g * s;
@@ -96,6 +94,31 @@ __device__ __forceinline__ void adam_guarded_update(float& p, float g, float& m,
   p = pd - lr_c * m / den;
 }
 
+// the unguarded step: nothing to read but the operands
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
+                            float lr_c, float beta1, float beta2, float omb1, float omb2, float eps, float inv_sqrt_bc2, float grad_scale) {
+  const long n4 = n / 4;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    float4 mm = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    float* pe = &pp.x; const float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
+#pragma unroll
+    for (int e = 0; e < 4; e++) adam_update<true>(pe[e], ge[e], me[e], ve[e], grad_scale, 1.0f, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(m)[i] = mm;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+  const long tail = n4 * 4;
+  for (long i = tail + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_update<false>(pi, g[i], mi, vi, grad_scale, 1.0f, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+  }
+}
+
+// the guarded step: gr = g * (grad_scale * coef) behind p *= d; nothing is written when the record says skip
 __global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
                                     float lr_c, float beta1, float beta2, float omb1, float omb2, float eps, float inv_sqrt_bc2, float grad_scale,
                                     float d, const hftt_guard_ctl* __restrict__ ctl) {
@@ -109,7 +132,7 @@ __global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restri
     float4 vv = reinterpret_cast<float4*>(v)[i];
     float* pe = &pp.x; const float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
 #pragma unroll
-    for (int e = 0; e < 4; e++) adam_guarded_update<true>(pe[e], ge[e], me[e], ve[e], s, d, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
+    for (int e = 0; e < 4; e++) adam_update<true>(pe[e], ge[e], me[e], ve[e], s, d, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
     reinterpret_cast<float4*>(p)[i] = pp;
     reinterpret_cast<float4*>(m)[i] = mm;
     reinterpret_cast<float4*>(v)[i] = vv;
@@ -117,7 +140,7 @@ __global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restri
   const long tail = n4 * 4;
   for (long i = tail + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     float pi = p[i], mi = m[i], vi = v[i];
-    adam_guarded_update<false>(pi, g[i], mi, vi, s, d, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
+    adam_update<false>(pi, g[i], mi, vi, s, d, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
     p[i] = pi; m[i] = mi; v[i] = vi;
   }
 }
@@ -168,14 +191,14 @@ __global__ __launch_bounds__(GN_THREADS) void adam_groups_kernel(float* __restri
     float4 vv = reinterpret_cast<float4*>(v)[i];
     float* pe = &pp.x; const float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
 #pragma unroll
-    for (int e = 0; e < 4; e++) adam_guarded_update<true>(pe[e], ge[e], me[e], ve[e], s, d, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
+    for (int e = 0; e < 4; e++) adam_update<true>(pe[e], ge[e], me[e], ve[e], s, d, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
     reinterpret_cast<float4*>(p)[i] = pp;
     reinterpret_cast<float4*>(m)[i] = mm;
     reinterpret_cast<float4*>(v)[i] = vv;
   }
 }
 
-// workgroups over n elements read four at a time: adam_kernel's grid (ceil((n / 4 + 1) / 256), at most GN_MAX_WGS)
+// workgroups over n elements read four at a time: the grid of all three Adam kernels (ceil((n / 4 + 1) / 256), at most GN_MAX_WGS)
 inline int guard_grid(long n) {
   long b = (n / 4 + 1 + GN_THREADS - 1) / GN_THREADS;
   if (b < 1) b = 1;
@@ -196,6 +219,20 @@ extern "C" int hftt_grad_norm(const float* g, int64_t n, double grad_scale, doub
   const int wgs = guard_grid((long)n);
   if (int rc = hftt_launch<grad_sqsum_kernel>("grad_norm(1)", dim3(wgs), dim3(GN_THREADS), 0, (hipStream_t)stream, g, (long)n, (double*)ws)) return rc;
   return hftt_launch<grad_norm_finalize_kernel>("grad_norm(2)", dim3(1), dim3(GN_THREADS), 0, (hipStream_t)stream, (const double*)ws, wgs, fabs(grad_scale), max_norm, ctl);
+}
+
+extern "C" int hftt_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int32_t step,
+                              double lr, double beta1, double beta2, double eps, double grad_scale, void* stream) {
+  HFTT_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adam_step: bad arguments");
+  HFTT_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step: buffers must be 16-byte aligned");
+  // hyper-parameters arrive as doubles (python floats) and 1-beta is formed BEFORE rounding to fp32, as torch.optim.Adam does: 1.f - 0.999f is
+  // off by 1.3e-5 relative and would show in exp_avg_sq of every step
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  const float lr_c = (float)(lr / bc1);
+  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  return hftt_launch<adam_kernel>("adam_step", dim3(guard_grid((long)n)), dim3(GN_THREADS), 0, (hipStream_t)stream, p, g, m, v, (long)n,
+                                               lr_c, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, inv_sqrt_bc2, (float)grad_scale);
 }
 
 extern "C" int hftt_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, int32_t step,

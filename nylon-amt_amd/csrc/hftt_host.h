@@ -15,3 +15,11 @@ void hftt_set_error(const char* fmt, ...);
   } while (0)
 
 static inline int hftt_ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// workgroups of `block` threads over `work_items` for a grid-stride kernel: at least one, at most `cap`
+static inline int grid_for(long work_items, int block, int cap = 4096) {
+  long b = (work_items + block - 1) / block;
+  if (b < 1) b = 1;
+  if (b > cap) b = cap;
+  return (int)b;
+}

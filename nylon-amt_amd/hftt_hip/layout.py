@@ -2,7 +2,7 @@
 
 From the model dimensions, the precision mode, the option switches and the parameters' offsets / shapes in the flat buffer, `WeightLayout`
 computes where every prepared operand lives: the matrix planes (bf16, fp32 or the x3 hi / lo pair -- the same element offsets), the fp32
-vector plane, the strip-pack stream, and the table entries that tell the prepare kernels what to copy where (csrc/elementwise.hip:
+vector plane, the strip-pack stream, and the table entries that tell the prepare kernels what to copy where (csrc/prep.hip:
 prep entries; csrc/strip_gemm.hip, csrc/x3_strip.hip: strip-pack entries).  The engine allocates the tensors and uploads the tables.
 """
 from collections import OrderedDict, namedtuple

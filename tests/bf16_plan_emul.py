@@ -9,9 +9,9 @@ decoder_layer, decoder_forward) -- never by the plan's descriptors, so a launch 
 a defect shows at the launch that made it.
 
 Rounding points, and where the kernels make them:
-  * matrix weights: rne to bf16 once -- csrc/elementwise.hip prep_weights_kernel behind hftt_prep_weights (f2bf, hftt_common.h: a __bf16 cast, rne), the
+  * matrix weights: rne to bf16 once -- csrc/prep.hip prep_weights_kernel behind hftt_prep_weights (f2bf, hftt_common.h: a __bf16 cast, rne), the
     strip packs (strip_gemm.hip hftt_strip_pack, x3_strip.hip hftt_x3_strip_pack with bf16 halves, of which bs_strip.hip reads the hi fragment),
-    the folded embedding Linear(n_proc -> d) (elementwise.hip fold_fwd_kernel: up to C * k products summed in fp32, then f2bf; its bias fp32),
+    the folded embedding Linear(n_proc -> d) (prep.hip fold_fwd_kernel: up to C * k products summed in fp32, then f2bf; its bias fp32),
     the stacked heads, and the bf16 copy of the decoder position table (layout.py 'dec_pos_bf', a plain prep entry);
   * biases, LayerNorm parameters and both position tables as add_table / time_embed operands: fp32;
   * an fp32 A operand of the block GEMM is rounded while it is staged: gemm_nt.hip gemm_nt_kernel (`ph.x = f2bf(areg[j].x) ...`) and the
@@ -24,7 +24,7 @@ Rounding points, and where the kernels make them:
     fused FFN (strip_mlp2_kernel, bs_mlp_kernel): the hidden rounded once as the operand of fc_2;
   * attention: bf16_emul.attention (attn_fwd.hip / attn_fwd8.hip); the attention map is the fp32 p * (1/sum) (attn_fwd.hip: `p4[e] = sacc * inv`);
     lse = (raw max, 1/sum) per (sequence, head, query);
-  * elementwise.hip time_embed_fwd_kernel: y0[(b, n, t)] = store(x[(b, t, n)] * sqrt(d) + pos_t[t]); heads_split_kernel: a copy of the
+  * glue.hip time_embed_fwd_kernel: y0[(b, n, t)] = store(x[(b, t, n)] * sqrt(d) + pos_t[t]); heads_split_kernel: a copy of the
     velocity columns and 1 / (1 + expf(-x)) of the three others, time-major rows re-ordered.
 
 Families (layout.precision_modes): strip256 / small64 -- bf16 stream, fused FFN, nothing saved; block -- fp32 stream, GEMM-only tensors bf16, the

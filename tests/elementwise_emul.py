@@ -1,4 +1,4 @@
-"""fp32 restatements, fp64 references and rounding-model criteria of the non-MFMA kernels of csrc/elementwise.hip: LayerNorm backward, the
+"""fp32 restatements, fp64 references and rounding-model criteria of the non-MFMA kernels of csrc/ln_bwd.hip, guard.hip, loss.hip and glue.hip: LayerNorm backward, the
 fused Adam step, the fused loss, the two-stage column sum and the time-embedding backward -- in the forms hftt_hip/engine.py launches.
 
 Three things per kernel, all in torch and device-agnostic (the GPU tests evaluate the fp64 reference where the tensors live):
@@ -70,7 +70,7 @@ def violations(name, got, ref, bound):
 
 
 # ================================================================================================ LayerNorm backward
-# branch table of hftt_ln_bwd (csrc/elementwise.hip): name -> N, storage of dy / r / dr, the dropped copy (None, 'f32', 'bf16'), operands
+# branch table of hftt_ln_bwd (csrc/ln_bwd.hip): name -> N, storage of dy / r / dr, the dropped copy (None, 'f32', 'bf16'), operands
 # offset by one element (the unaligned fallbacks), R = rows a wave takes per step (the ragged-M handling), and the M values: 1, R +- 1 and
 # multiples +- 1, and one M just past the kernel's first grid pass (hftt_ln_bwd_wgs caps at 1024 workgroups of 4 waves: 4096 * R rows).
 _M2 = (1, 2, 3, 7, 9, 8193)

@@ -1,4 +1,4 @@
-"""The non-MFMA kernels of csrc/elementwise.hip against fp64, in the forms hftt_hip/engine.py launches them, under the rounding-model
+"""The non-MFMA kernels of csrc/ln_bwd.hip, guard.hip, loss.hip and glue.hip against fp64, in the forms hftt_hip/engine.py launches them, under the rounding-model
 criteria of tests/elementwise_emul.py (derivations there; tests/test_elementwise_emul_bound.py shows on the CPU what they resolve).
 
 LayerNorm backward over every branch of the hftt_ln_bwd dispatcher (the unaligned fallbacks through views offset by one element) x three

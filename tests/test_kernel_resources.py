@@ -66,3 +66,19 @@ def test_x3_strip_registers_and_occupancy():
             fused += 1
             assert scratch == 0 and _get(v, 'VGPRs') + _get(v, 'AGPRs') <= 512, (name, v)
     assert (n_kernels, half_set, fused) == (18, 8, 6)
+
+
+@pytest.mark.skipif(HIPCC is None, reason='hipcc not found')
+def test_layernorm_backward_registers_and_occupancy():
+    """The four LayerNorm backward forms are loaders around shared row helpers (ln_bwd.hip), and registers decide the bandwidth of the wide ones
+    (the header comment of ln_bwd256_rows_kernel: R = 4 lost its occupancy to them).  A helper that keeps an array alive across the prefetch
+    shows here and nowhere else: no scratch, and registers and occupancy no worse than each symbol had before the helpers."""
+    # (VGPRs, Occupancy) of commit 7301703, where each kernel spelled its own arithmetic out (csrc/elementwise.hip)
+    parent = {'ln_bwd_kernel<1>': (27, 8), 'ln_bwd_kernel<2>': (50, 8), 'ln_bwd_kernel<4>': (64, 8), 'ln_bwd64_kernel': (52, 8),
+              'ln_bwd256_bf16_kernel': (166, 3), 'ln_bwd256_rows_kernel<2, true>': (104, 4)}
+    res = {k: v for k, v in _resources('ln_bwd.hip').items() if k.startswith('ln_bwd') and k != 'ln_bwd_reduce_kernel'}
+    assert sorted(res) == sorted(parent)
+    for name, v in res.items():
+        vgprs, occ = parent[name]
+        assert _get(v, 'ScratchSize') == 0, (name, v)
+        assert _get(v, 'VGPRs') <= vgprs and _get(v, 'Occupancy') >= occ, (name, v, parent[name])

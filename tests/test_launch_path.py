@@ -64,15 +64,50 @@ def test_strip_helpers_and_the_small_width_family_are_written_once():
     assert tail.count(marker) == 0 and all('#include "small_strip.h"' in s for s in small[1:])
 
 
+def _code(text):
+    return re.sub(r'//[^\n]*', '', text)
+
+
+def _body(text, start):
+    """the definition that `start` opens, up to the closing brace in column 0"""
+    text = text[text.index(start):]
+    return text[:text.index('\n}\n')]
+
+
 def test_the_guard_test_op_is_a_single_launch_that_writes_its_sentinel():
     '''test_second_device_is_refused_before_anything_is_enqueued tells guard-before-launch from guard-after-launch only if the FIRST launch of
-    the refused call writes the tensor that carries the sentinel: hftt_adam_step is one launch, and adam_kernel updates p, m, v in place.'''
-    s = _sources()['elementwise.hip']
-    body = s[s.index('extern "C" int hftt_adam_step('):]
-    body = body[:body.index('\n}\n')]
+    the refused call writes the tensor that carries the sentinel: hftt_adam_step is one launch, and adam_kernel updates p, m, v in place -- in
+    its quad loop and in its tail, through the one update (adam_update) that assigns all three.'''
+    s = _sources()['guard.hip']
+    body = _body(s, 'extern "C" int hftt_adam_step(')
     assert body.count('hftt_launch<') == 1 and 'hftt_launch<adam_kernel>' in body
-    kern = s[s.index('adam_kernel('):s.index('inline int grid_for(')]
-    assert re.search(r'\bp\[i\] -=', kern) and re.search(r'\bm\[i\] =', kern) and re.search(r'\bv\[i\] =', kern)
+    quad, tail = _body(s, 'void adam_kernel(').split('const long tail', 1)
+    update = _body(s, 'void adam_update(')
+    for x in 'pmv':
+        assert re.search(r'float& %s\b' % x, update) and re.search(r'^\s*%s = ' % x, update, re.M), x        # the update writes its p, m, v ...
+        # ... and both loops hand it theirs and store them back
+        assert re.search(r'adam_update<true>\(pe\[e\], ge\[e\], me\[e\], ve\[e\],', quad) and re.search(r'reinterpret_cast<float4\*>\(%s\)\[i\] = %s;' % (x, x * 2), quad), x
+        assert re.search(r'adam_update<false>\(pi, g\[i\], mi, vi,', tail) and re.search(r'\b%s\[i\] = %si;' % (x, x), tail), x
+
+
+def test_layernorm_backward_and_adam_are_written_once():
+    '''The LayerNorm backward output expression and the Adam denominator have one definition each across csrc/ (the four LayerNorm forms are
+    loaders around ln_row_terms / ln_row_out, the three Adam kernels call adam_update), and no kernel of ln_bwd.hip spells the row arithmetic
+    out again.'''
+    src = {f: _code(t) for f, t in _sources().items()}
+    assert 'elementwise.hip' not in src
+    defs = {'LayerNorm output': r'=\s*(?:rstd|rs) \* (?:\(|__builtin_fmaf\()', 'Adam denominator': r'sqrtf\(\w+(?:\[\w+\])?\)[^;\n]*\beps\b'}
+    for (name, pat), home in zip(defs.items(), ('ln_bwd.hip', 'guard.hip')):
+        where = [f for f, t in src.items() for _ in re.findall(pat, t)]
+        assert where == [home], (name, where)
+    ln = src['ln_bwd.hip']
+    kernels = ln.split('__global__')[1:]
+    assert len(kernels) == 5          # four forms and the reduce
+    for k in kernels:
+        k = k[:k.index('\n}\n')]
+        assert not re.search(r'\b(rstd|rs) \* |fmaf', k), k[:80]
+        if 'ln_bwd_reduce_kernel' not in k:
+            assert all(h in k for h in ('ln_row_terms<', 'ln_row_out<', 'ln_flush<')), k[:80]
 
 
 _CHILD = r'''

@@ -77,7 +77,7 @@ def test_prep_entries_stay_inside_their_region(cname, precision):
     for (so, do, rows, cols, sld, dld, kind), key in zip(lay.prep, lay.prep_keys):
         flat = lay.fl if kind == 2 else lay.wl
         lo, hi = flat.items[key], flat.items[key] + flat.sizes[key]
-        # csrc/elementwise.hip: kind 0 writes dst[r * dld + c], kind 1 (transposed) dst[c * dld + r], kind 2 a vector of `cols` elements
+        # csrc/prep.hip: kind 0 writes dst[r * dld + c], kind 1 (transposed) dst[c * dld + r], kind 2 a vector of `cols` elements
         last = {0: (rows - 1) * dld + cols, 1: (cols - 1) * dld + rows, 2: cols}[kind]
         assert lo <= do and do + last <= hi, (key, kind)
         assert sld >= cols and dld >= (rows if kind == 1 else cols)

@@ -17,7 +17,7 @@ Roundings modelled (csrc/x3_common.h, gemm_tn.hip, x3_strip.hip, x3_attn_bwd.h):
       - its gradient dh after the gate: the dY factor of dW1 and the source of db1 (the dX product of fc_1 reads dh at full width from
         registers, x3_mlp_kernel<1>);
       - every pre-LayerNorm sum: the LayerNorm backward recomputes x_hat = (bf16(r) - mean) * rstd with the fp32 statistics of the forward
-        (elementwise.hip, ln_bwd);
+        (ln_bwd.hip);
     a bf16-stored factor enters its product as its bf16 value alone (no lo half).
   * the conv + token embedding as ONE Linear(n_proc -> d) on the folded weights (the device's hftt_fold + one x3 product).
 Not modelled (2^-22 and below): the f16-pair storage of q / k / v, the fp16 pair of the FFN block's residual.

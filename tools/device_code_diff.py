@@ -3,8 +3,9 @@
 
     python tools/device_code_diff.py [--base REV] [--grad-hi] [--jobs N]
 
-Exports REV (default HEAD) next to the working tree, compiles every HIP source of build.py's SOURCES in both with build.py's FLAGS, device
-side only (`--cuda-device-only --no-gpu-bundle-output`: one gfx950 code object per file), and compares per kernel symbol
+Exports REV (default HEAD) next to the working tree, compiles every HIP source of each side's own build.py SOURCES with this tree's FLAGS, device
+side only (`--cuda-device-only --no-gpu-bundle-output`: one gfx950 code object per file), and compares per kernel symbol -- whichever file holds
+it on either side (a symbol that one tree holds in several sources is matched file by file); a symbol that moved is reported with where from --
   * the instruction bytes (llvm-objdump -d), symbol by symbol, so that a changed order of instantiation does not matter, and
   * the amdhsa.kernels metadata (llvm-readelf --notes): register counts, spills, scratch, static LDS, kernarg size, workgroup size.
 --grad-hi adds -DHFTT_GRAD_HI_BUILD (the HFTT_BUILD_GRAD_HI=1 library).  Exit status 0 = no difference, 1 = differences (listed).
@@ -29,8 +30,8 @@ META_KEYS = ('.vgpr_count', '.agpr_count', '.sgpr_count', '.vgpr_spill_count', '
              '.group_segment_fixed_size', '.kernarg_segment_size', '.max_flat_workgroup_size', '.uses_dynamic_stack')
 
 
-def _build_py():
-    spec = importlib.util.spec_from_file_location('hftt_build', os.path.join(ROOT, 'nylon-amt_amd', 'build.py'))
+def _build_py(root):
+    spec = importlib.util.spec_from_file_location('hftt_build', os.path.join(root, 'nylon-amt_amd', 'build.py'))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
@@ -85,52 +86,66 @@ def kernels_of(tree, src, flags, hipcc, out_dir):
     return out
 
 
+def _keyed(got, side, sources):
+    """{key: (source file, kernels_of value)}: key = the symbol, or (file, symbol) for a symbol that `dup` names"""
+    return {((src, name) if name in got['dup'] else name): (src, v) for src in sources for name, v in got[(side, src)].items()}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--base', default='HEAD')
     ap.add_argument('--grad-hi', action='store_true')
     ap.add_argument('--jobs', type=int, default=8)
     a = ap.parse_args()
-    b = _build_py()
+    b = _build_py(ROOT)
     flags = [f for f in b.FLAGS if f != '-DHFTT_GRAD_HI_BUILD'] + (['-DHFTT_GRAD_HI_BUILD'] if a.grad_hi else [])
-    sources = [s for s in b.SOURCES if s.endswith('.hip')]
     with tempfile.TemporaryDirectory() as tmp:
         base = os.path.join(tmp, 'base')
         os.makedirs(base)
         tar = os.path.join(tmp, 'base.tar')
-        _run(['git', '-C', ROOT, 'archive', '-o', tar, a.base, CSRC, 'include'])
+        _run(['git', '-C', ROOT, 'archive', '-o', tar, a.base, CSRC, 'include', os.path.join('nylon-amt_amd', 'build.py')])
         with tarfile.open(tar) as t:
             t.extractall(base)
+        # each side compiles the sources its own build.py names: a kernel may have moved to another file, or its file may be gone
+        sources = {side: [s for s in _build_py(tree).SOURCES if s.endswith('.hip')] for side, tree in (('base', base), ('tree', ROOT))}
         jobs = []
         for side, tree in (('base', base), ('tree', ROOT)):
             os.makedirs(os.path.join(tmp, 'co_' + side))
-            # a source added since the base has nothing to be compared with
-            jobs += [(side, tree, s) for s in sources if os.path.exists(os.path.join(tree, CSRC, s))]
+            jobs += [(side, tree, s) for s in sources[side]]
         with ThreadPoolExecutor(max_workers=a.jobs) as ex:
             res = list(ex.map(lambda j: kernels_of(j[1], j[2], flags, b._hipcc(), os.path.join(tmp, 'co_' + j[0])), jobs))
     got = {(j[0], j[2]): r for j, r in zip(jobs, res)}
-    n_diff = n_kern = n_bytes = 0
-    for s in sources:
-        old, new = got.get(('base', s)), got.get(('tree', s))
-        if old is None or new is None:
-            print('%-18s only in the %s' % (s, 'working tree' if old is None else 'base'))
-            n_diff += 1
-            continue
-        bad = []
-        for name in sorted(set(old) | set(new)):
-            if name not in old or name not in new:
-                bad.append('  %s: only in the %s' % (name, 'working tree' if name not in old else 'base'))
-            elif old[name][:2] != new[name][:2]:
-                bad.append('  %s: instruction bytes differ (%d -> %d bytes)' % (name, old[name][1], new[name][1]))
-            elif old[name][2] != new[name][2]:
-                bad.append('  %s: metadata differs: %s -> %s' % (name, old[name][2], new[name][2]))
-        n_kern += len(new)
-        n_bytes += sum(v[1] for v in new.values())
+    # matched by symbol across files; by (file, symbol) only where one tree holds the symbol in more than one source
+    got['dup'] = {name for side in sources for name in set().union(*(got[(side, s)] for s in sources[side]))
+                  if sum(name in got[(side, s)] for s in sources[side]) > 1}
+    old, new = _keyed(got, 'base', sources['base']), _keyed(got, 'tree', sources['tree'])
+    n_diff = n_moved = 0
+    for s in sources['tree']:
+        mine = {k: v for k, (src, v) in new.items() if src == s}
+        bad, moved = [], {}
+        for k in sorted(mine, key=str):
+            name = k if isinstance(k, str) else k[1]
+            if k not in old:
+                bad.append('  %s: only in the working tree' % name)
+                continue
+            was, o = old[k]
+            if was != s:
+                moved.setdefault(was, []).append(name)
+            if o[:2] != mine[k][:2]:
+                bad.append('  %s: instruction bytes differ (%d -> %d bytes)' % (name, o[1], mine[k][1]))
+            elif o[2] != mine[k][2]:
+                bad.append('  %s: metadata differs: %s -> %s' % (name, o[2], mine[k][2]))
         n_diff += len(bad)
-        print('%-18s %4d symbols %9d code bytes  %s' % (s, len(new), sum(v[1] for v in new.values()), 'identical' if not bad else '%d DIFFER' % len(bad)))
+        n_moved += sum(len(v) for v in moved.values())
+        print('%-18s %4d symbols %9d code bytes  %s%s' % (s, len(mine), sum(v[1] for v in mine.values()), 'identical' if not bad else '%d DIFFER' % len(bad),
+                                                       ''.join('  (%d moved here from %s)' % (len(v), f) for f, v in sorted(moved.items()))))
         for line in bad:
             print(line)
-    print('%s against %s%s: %d symbols, %d code bytes, %d differences' % ('working tree', a.base, ' (-DHFTT_GRAD_HI_BUILD)' if a.grad_hi else '', n_kern, n_bytes, n_diff))
+    for k in sorted(set(old) - set(new), key=str):
+        print('%-18s %s: only in the base' % (old[k][0], k if isinstance(k, str) else k[1]))
+        n_diff += 1
+    print('%s against %s%s: %d symbols, %d code bytes, %d moved to another file, %d differences' % (
+        'working tree', a.base, ' (-DHFTT_GRAD_HI_BUILD)' if a.grad_hi else '', len(new), sum(v[1] for _, v in new.values()), n_moved, n_diff))
     return 1 if n_diff else 0
 
 
