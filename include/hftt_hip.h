@@ -906,6 +906,76 @@ typedef struct {
 int hftt_labels_render_mix(const hftt_labels_mix_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Clip room (csrc/clip_room.hip, csrc/clip_dry.h): reverb and equalisation -- each window's dry signal convolved with one impulse response of
+ * a device-resident bank while the batch is gathered.  It augments the clip log-mel above (hftt_clip_logmel and its warp / mix forms) and
+ * touches none of their kernels: it writes a scratch corpus of WET samples that a plain, unchanged hftt_clip_logmel reads in a second launch.
+ * One entry point ADDED at ABI 8; HFTT_ABI_VERSION stays 8 and every descriptor above keeps its layout and its results.
+ *
+ * Inputs: the corpus and window tables of hftt_clip_logmel_desc -- wave, wave_i16, file_samp0, n_files, total_samples, win_file, win_start, B,
+ * width, hop, n_fft -- and gain [B] or NULL; `warp` (the primaries'), `mix` (the partners) and `mix_warp` (the partners' warps) exactly as the
+ * four entry points above take them, a table with all pointers NULL being absent; mix_warp is given exactly when warp and mix both are.
+ *     ir        fp32 [n_ir, L] in device memory, 1 <= L <= HFTT_ROOM_MAX_TAPS (0.5 s at 16 kHz); tap 0 is the direct path
+ *     ir_taps   int32 [n_ir]: response r has taps k < ir_taps[r]; the entries at or behind it are not read.  Values outside 1 .. L cannot be
+ *               refused by the host: the kernel clamps them into that range
+ *     ir_index  int32 [B]: window b's response; negative: the window stays dry; >= n_ir: a window without a file (fill)
+ * Dry signal of window b over its (warped) file of n' samples: dry_b[i], 0 <= i < n', is the value clip_logmel_kernel stages for file sample i
+ * in front of the noise term (the primary through the warp or read directly, fmul by gain[b], fadd of fmul(partner, mix_gain[b]): one device
+ * function, csrc/clip_dry.h, called by both kernels); dry_b[i] = 0 outside [0, n').
+ * Wet signal:  wet_b[i] = sum over k < taps of h[k] * dry_b[i - k],  0 <= i < n',  taps = clamp(ir_taps[r], 1, L), formed in fp32 as
+ *     acc = 0; for k = 0 .. taps - 1 in INCREASING order: acc = fma(h[k], dry_b[i - k], acc)            (one rounding per tap)
+ * The tail behind the file's end is cut: the wet file is as long as the dry one, so its frame count 1 + n' / hop and every fill column are
+ * what they were, and with tap 0 the direct path no onset moves: the labels are unchanged.  wet_b[i] depends on the window's sources, warps,
+ * gains, its response and i only -- not on win_start, on where a workgroup's tile begins or on the launch geometry: two overlapping windows
+ * with equal draws see the same wet waveform.  No atomics, one writer per element, the same bits from run to run.  A dry window
+ * (ir_index[b] < 0) gets dry_b bit for bit.
+ *
+ * Outputs: out fp32 [B, span], span >= (P + width - 1) * hop + n_fft / 2 with P = ceil((n_fft / 2) / hop); and three tables that the kernel
+ * writes itself: out_samp0 int64 [2 B + 1], out_win_file int32 [B], out_win_start int32 [B].  Row b of `out` holds two pseudo-files:
+ *     2 b      wet_b[o_b .. e_b),   o_b = max(0, win_start[b] - P) * hop,   e_b = min(n', (win_start[b] + width - 1) * hop + n_fft / 2)
+ *              (empty when e_b <= o_b)
+ *     2 b + 1  the unused remainder of the row (not written), which keeps out_samp0 a gap-free prefix table: out_samp0[2 b] = b * span
+ *     out_win_file[b] = 2 b,   out_win_start[b] = win_start[b] - o_b / hop
+ * A window without a valid file, with o_b > n', or with a warp outside its ranges or ir_index[b] >= n_ir gets out_win_file[b] = -1.  With
+ * these tables a plain hftt_clip_logmel over `out` (wave_i16 = 0, n_files = 2 B, total_samples = B * span, win_file = out_win_file, win_start =
+ * out_win_start, gain NULL: it is already applied) gives, bit for bit and in the fill columns too, the result of hftt_clip_logmel on a file that
+ * IS wet_b: a frame the clip shows never reads in front of o_b unless o_b = 0 (P * hop >= n_fft / 2), o_b is a multiple of hop, so
+ * 1 + (n' - o_b) / hop counts the same last frame, and a pseudo-file cut at e_b < n' still holds every sample the last shown frame reads.
+ * At o_b == n' the pseudo-file is empty and its one frame is pseudo-frame 0, in front of the P >= 1 the clip starts at: fill, as on the whole
+ * file.  With n' == 0 a window at win_start <= P shows the empty file's one frame of zeros, a later one is fill.
+ * Noise under a room is the SECOND launch's (its noise_std / seed): the microphone's, added behind the room.  It is keyed on (seed,
+ * pseudo-file 2 b, position inside the pseudo-file), not on the source file and sample: two windows of one call no longer share it.
+ *
+ * One launch: a workgroup owns a window and a tile of 2,048 wet samples, stages the dry span they need once in LDS (taps rounded up to a
+ * multiple of four, + 2,048 samples: 40 KB for the longest response) and walks the taps four at a time with eight outputs per thread in
+ * registers; the taps are read from the bank in global memory.
+ * Refused in front of the launch: null pointers (gain and absent tables excepted); a warp, mix or mix_warp table of which only a part is
+ * given; mix_warp without both of the others or missing with both; wave_i16 outside 0 / 1; n_fft != 2048; B outside 1 .. 2^30; width, hop
+ * or n_files < 1; total_samples < 0, or > 2^38 with a warp; n_ir < 1; L outside 1 .. HFTT_ROOM_MAX_TAPS; span below the bound above.
+ * --------------------------------------------------------------------------------------------- */
+#define HFTT_ROOM_MAX_TAPS 8192
+typedef struct {
+  const void* wave;                                              /* fp32 or int16 [total_samples] */
+  const int64_t* file_samp0;                                     /* [n_files + 1] */
+  const int32_t* win_file; const int32_t* win_start;             /* [B] */
+  int64_t total_samples;
+  int32_t wave_i16, n_files, B, width;
+  int32_t n_fft, hop;
+  int32_t n_ir, L;
+  const float* gain;                                             /* [B] or NULL */
+  hftt_warp_args warp;                                           /* the primaries', or all NULL */
+  hftt_clip_mix_args mix;                                        /* the partners, or all NULL */
+  hftt_warp_args mix_warp;                                       /* the partners' warps: given exactly when warp and mix are */
+  const float* ir;                                               /* [n_ir, L] */
+  const int32_t* ir_taps;                                        /* [n_ir] */
+  const int32_t* ir_index;                                       /* [B] */
+  int64_t span;
+  void* out;                                                     /* fp32 [B, span] */
+  int64_t* out_samp0;                                            /* [2 B + 1] */
+  int32_t* out_win_file; int32_t* out_win_start;                 /* [B] */
+} hftt_clip_room_desc;
+int hftt_clip_room(const hftt_clip_room_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Guarded optimizer step (csrc/guard.hip): global-norm gradient clipping, a non-finite guard and decoupled weight decay around the fused
  * Adam.  Like the note decoder and the label renderer these entry points were ADDED at ABI 8 and HFTT_ABI_VERSION stays 8: nothing that an
  * ABI-8 caller binds changed (hftt_adam_step above is untouched and remains the default step); a caller that needs them looks the symbols up.

@@ -52,3 +52,45 @@ def reference_roll(notes, n_frames, sr=SR, hop=256, note_min=21):
     for nt in notes:
         roll[int(nt['onset'] * sr / hop):int(nt['offset'] * sr / hop), nt['pitch'] - note_min] = True
     return roll
+
+
+def synth_room_bank(n, sr=SR, taps=4096, rt60=(0.15, 0.8), drr_db=(0.0, 12.0), seed=0):
+    """n synthetic room impulse responses for hftt_hip.ops.RoomBank -> (ir fp32 [n, taps], ir_taps int32 [n]).  Per response, in fp64, rounded
+    once: tap 0 is 1 (the direct path: no onset moves), a pre-delay uniform in 1 .. 10 ms of silence, and from there a tail of Gaussian noise
+    times the envelope 10^(-3 k / (rt60 sr)) (k samples behind the pre-delay: 60 dB down after rt60 seconds, rt60 uniform in its range),
+    scaled so that the direct-to-reverberant ratio 10 log10(1 / sum tail^2) is drr_db (uniform in its range).  ir_taps is where the envelope
+    has fallen by 60 dB, or `taps` if that lies behind the response; the entries behind it are zero.  The whole response is then normalised
+    to unit L2 norm, so that a wet clip keeps the level of a dry one on noise-like signals."""
+    if n < 1 or taps < 1:
+        raise ValueError('synth_room_bank: n=%r and taps=%r must be positive' % (n, taps))
+    rng = np.random.RandomState(seed)
+    ir, ir_taps = np.zeros((n, taps), np.float64), np.zeros(n, np.int32)
+    for r in range(n):
+        t60 = float(rng.uniform(rt60[0], rt60[1]))
+        drr = float(rng.uniform(drr_db[0], drr_db[1]))
+        d = int(round(float(rng.uniform(0.001, 0.010)) * sr))
+        noise = rng.standard_normal(taps)                                       # (drawn whole, whatever the pre-delay: one draw count per response)
+        end = min(taps, d + int(np.ceil(t60 * sr)))                             # the envelope is 60 dB down here
+        h = np.zeros(taps, np.float64)
+        if end > max(d, 1):
+            k = np.arange(end - max(d, 1), dtype=np.float64) + (max(d, 1) - d)
+            tail = noise[max(d, 1):end] * np.power(10.0, -3.0 * k / (t60 * sr))
+            energy = float(np.sum(tail * tail))
+            if energy > 0.0:
+                h[max(d, 1):end] = tail * np.sqrt(np.power(10.0, -drr / 10.0) / energy)
+        h[0] = 1.0
+        ir[r] = h / np.sqrt(np.sum(h * h))
+        ir_taps[r] = max(1, end)
+    return ir.astype(np.float32), ir_taps
+
+
+def align_ir(h):
+    """a measured impulse response (or an equalisation filter) as the room takes it: the sample of largest |h| moves to tap 0 (what lies in
+    front of it is dropped, zeros fill the end), and the result has unit L2 norm -> fp32, the length of h"""
+    h = np.asarray(h, np.float64)
+    if h.ndim != 1 or h.size < 1 or not np.isfinite(h).all() or not np.any(h):
+        raise ValueError('align_ir: a response is a 1-d array of finite samples, not all zero')
+    p = int(np.argmax(np.abs(h)))
+    out = np.zeros_like(h)
+    out[:h.size - p] = h[p:]
+    return (out / np.sqrt(np.sum(out * out))).astype(np.float32)

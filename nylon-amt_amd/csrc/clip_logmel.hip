@@ -8,12 +8,13 @@
 // frame with logmel_kernel's frame transform (logmel_frame.h: packed 1024-point radix-4 Stockham transform, split pass, |X|^2, sequential CSR
 // mel sum, logf), gathers the columns in an LDS tile [n_mels][RUN] and stores it along the frame axis: RUN * 4 = 64 contiguous bytes per
 // (window, mel) row.  One writer per element, no atomics, no workspace.  A partner's sample is added into the same stage[j] slot, so the LDS
-// layout, the frame transform and the tile store are the same in all four forms.  See include/hftt_hip.h for the contract.
+// layout, the frame transform and the tile store are the same in all four forms.  The staged sample in front of the noise term is clip_dry.h's
+// one device function, which clip_room_kernel (clip_room.hip) convolves.  See include/hftt_hip.h for the contract.
 #include "hftt_common.h"
 #include "hftt_host.h"
 #include "hftt_launch.h"
+#include "clip_dry.h"
 #include "logmel_frame.h"
-#include "wave_warp.h"
 #include "../../include/hftt_hip.h"
 
 namespace {
@@ -26,26 +27,15 @@ static_assert(RUN == 16 && MAX_MELS == 256, "one thread per mel row; 16 lanes st
 // 1 / sqrt(21845), rounded once: the sum of four uniform bytes has variance 4 (256^2 - 1) / 12 = 21845
 constexpr float NOISE_C = 0x1.bb688cp-8f;
 
-// The sample that enters the window product: fmul by the gain, fadd of the noise term, one rounding each.  __fmul_rn / __fadd_rn are plain
-// operators in this toolchain, which the compiler may contract into an fma: not in this function.  The noise is keyed on (file, sample), so
-// every frame and every clip sees the same noisy waveform; nstd = fmul(noise_std[b], NOISE_C).
-__device__ __forceinline__ float mix(float s, bool has_gain, float gain, bool has_noise, float nstd, uint64_t seed, uint32_t file, uint64_t i) {
+// The noise term onto a staged dry sample (clip_dry.h): one fadd of one fmul, never an fma -- __fmul_rn / __fadd_rn are plain operators in this
+// toolchain, which the compiler may contract: not in this function.  The noise is keyed on (file, sample), so every frame and every clip sees
+// the same noisy waveform; nstd = fmul(noise_std[b], NOISE_C).
+__device__ __forceinline__ float add_noise(float s, float nstd, uint64_t seed, uint32_t file, uint64_t i) {
 #pragma clang fp contract(off)
-  if (has_gain) s = s * gain;
-  if (has_noise) {
-    const uint32_t h = hftt_hash(seed, file, i);
-    const int sum = (int)(h & 0xFFu) + (int)((h >> 8) & 0xFFu) + (int)((h >> 16) & 0xFFu) + (int)(h >> 24) - 510;
-    const float nz = (float)sum * nstd;
-    s = s + nz;
-  }
-  return s;
-}
-
-// the partner's term: fadd(s, fmul(sB, gainB)), two roundings
-__device__ __forceinline__ float add_scaled(float s, float sB, float gainB) {
-#pragma clang fp contract(off)
-  const float p = sB * gainB;
-  return s + p;
+  const uint32_t h = hftt_hash(seed, file, i);
+  const int sum = (int)(h & 0xFFu) + (int)((h >> 8) & 0xFFu) + (int)((h >> 16) & 0xFFu) + (int)(h >> 24) - 510;
+  const float nz = (float)sum * nstd;
+  return s + nz;
 }
 
 // WARP: only the staging loop differs -- the window's frames are counted in the warped file and a staged sample is interpolated from the
@@ -78,19 +68,8 @@ __global__ __launch_bounds__(256) void clip_logmel_kernel(const hftt_clip_logmel
   const int ncol = g.width - c0 < RUN ? g.width - c0 : RUN;
   const int hop = g.hop;
   const int file = g.win_file[b];
-  long samp0 = 0, n = -1;                             // n < 0: no such file, every column is fill
-  if (file >= 0 && file < g.n_files) {
-    samp0 = g.file_samp0[file];
-    n = g.file_samp0[file + 1] - samp0;
-    if (samp0 < 0 || n < 0 || samp0 + n > g.total_samples) n = -1;       // a table that leaves the corpus: nothing is read there
-  }
-  warp_win w = {};
-  long np = n;                                        // samples of the file as the frames see it
-  if constexpr (WARP) {
-    w = warp_load(wa, b);
-    if (!w.ok) n = -1;
-    np = n >= 0 ? warp_len(n, w) : -1;
-  }
+  const clip_source A = clip_source_load<WARP>(g.file_samp0, g.n_files, g.total_samples, file, wa, b);
+  const long n = A.n, np = A.np;                      // n < 0: no such file, every column is fill; np: samples of the file as the frames see it
   const long nframe = n >= 0 ? 1 + np / hop : 0;
   const long t0 = (long)g.win_start[b] + c0;          // file frame of column c0
   const bool any = t0 < nframe && t0 + ncol > 0;      // (the same for every thread: the barriers below are met by all or by none)
@@ -103,10 +82,9 @@ __global__ __launch_bounds__(256) void clip_logmel_kernel(const hftt_clip_logmel
       const long i = i0 + j;
       float s = 0.f;                                  // outside [0, n): zeros, never a neighbouring file's samples
       if (i >= 0 && i < np) {
-        if constexpr (WARP) s = warp_sample(g.wave, g.wave_i16 != 0, samp0, n, np, wa.proto, w, i);
-        else s = g.wave_i16 ? (float)((const short*)g.wave)[samp0 + i] * (1.f / 32768.f) : ((const float*)g.wave)[samp0 + i];
+        s = clip_dry<WARP, false>(0.f, g.wave, g.wave_i16 != 0, A, wa.proto, i, g.gain != nullptr, gain);
         // with a partner the noise waits for the second pass below: it is added behind the partner's term
-        s = mix(s, g.gain != nullptr, gain, !MIX && g.noise_std != nullptr, nstd, g.seed, (uint32_t)file, (uint64_t)i);
+        if (!MIX && g.noise_std != nullptr) s = add_noise(s, nstd, g.seed, (uint32_t)file, (uint64_t)i);
       }
       stage[j] = s;
     }
@@ -114,20 +92,8 @@ __global__ __launch_bounds__(256) void clip_logmel_kernel(const hftt_clip_logmel
       // The partner (the same for every thread of the workgroup): its file as the primary's above, nB < 0 = it contributes nothing.  A pass
       // of its own over the slots this thread has just written (no barrier), so that the two sources' warps are not live together.
       const clip_mix& mx = clip_mix_of(mx_pack...);
-      const int fileB = mx.t.mix_file[b];
-      long sampB = 0, nB = -1;
-      if (fileB >= 0 && fileB < g.n_files) {
-        sampB = g.file_samp0[fileB];
-        nB = g.file_samp0[fileB + 1] - sampB;
-        if (sampB < 0 || nB < 0 || sampB + nB > g.total_samples) nB = -1;
-      }
-      warp_win wB = {};
-      long npB = nB;
-      if constexpr (WARP) {
-        wB = warp_load(mx.w, b);
-        if (!wB.ok) nB = -1;
-        npB = nB >= 0 ? warp_len(nB, wB) : -1;
-      }
+      const clip_source Bs = clip_source_load<WARP>(g.file_samp0, g.n_files, g.total_samples, mx.t.mix_file[b], mx.w, b);
+      const long nB = Bs.n;
       const long shiftB = ((long)mx.t.mix_start[b] - (long)g.win_start[b]) * hop;      // |.| < 2^32 * hop: no overflow
       const float gainB = mx.t.mix_gain[b];
       if (nB >= 0 || g.noise_std != nullptr) {
@@ -135,16 +101,9 @@ __global__ __launch_bounds__(256) void clip_logmel_kernel(const hftt_clip_logmel
           const long i = i0 + j;
           if (i < 0 || i >= np) continue;             // outside the primary's extent the staged zero stays
           float s = stage[j];
-          if (nB >= 0) {
-            const long iB = i + shiftB;
-            float sB = 0.f;                           // outside [0, n'_B): zeros
-            if (iB >= 0 && iB < npB) {
-              if constexpr (WARP) sB = warp_sample(g.wave, g.wave_i16 != 0, sampB, nB, npB, mx.w.proto, wB, iB);
-              else sB = g.wave_i16 ? (float)((const short*)g.wave)[sampB + iB] * (1.f / 32768.f) : ((const float*)g.wave)[sampB + iB];
-            }
-            s = add_scaled(s, sB, gainB);
-          }
-          stage[j] = mix(s, false, 1.f, g.noise_std != nullptr, nstd, g.seed, (uint32_t)file, (uint64_t)i);
+          if (nB >= 0) s = clip_dry<WARP, true>(s, g.wave, g.wave_i16 != 0, Bs, mx.w.proto, i + shiftB, true, gainB);
+          if (g.noise_std != nullptr) s = add_noise(s, nstd, g.seed, (uint32_t)file, (uint64_t)i);
+          stage[j] = s;
         }
       }
     }

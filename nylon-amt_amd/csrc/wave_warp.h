@@ -1,7 +1,7 @@
 // The warped sample (gfx950): one window's warp and the Hann-windowed sinc that reads a resident waveform at pos = j * step - delay (Q24).
-// ONE device function, called by the staging loop of clip_logmel_kernel (clip_logmel.hip: for the primary and, under clip mixing, the
-// partner) and by wave_warp_kernel (wave_warp.hip): what the log-mel sees is what hftt_wave_warp writes.  See include/hftt_hip.h for the
-// contract; every operation and its order is stated there.
+// ONE device function, called by the dry sample of the clip kernels (clip_dry.h: for the primary and, under clip mixing, the partner, in the
+// staging loops of clip_logmel_kernel and clip_room_kernel) and by wave_warp_kernel (wave_warp.hip): what the log-mel sees is what
+// hftt_wave_warp writes.  See include/hftt_hip.h for the contract; every operation and its order is stated there.
 #pragma once
 #include "hftt_common.h"
 #include "../../include/hftt_hip.h"

@@ -274,6 +274,19 @@ class LabelsMixDesc(C.Structure):
                 ('file_end_sec', C.c_void_p), ('a_frames', C.c_void_p)]
 
 
+ROOM_MAX_TAPS = 8192                        # HFTT_ROOM_MAX_TAPS
+
+
+class ClipRoomDesc(C.Structure):            # hftt_clip_room_desc: the windows' dry signal convolved with a response of the bank -> a scratch corpus
+    _fields_ = [('wave', C.c_void_p), ('file_samp0', C.c_void_p), ('win_file', C.c_void_p), ('win_start', C.c_void_p),
+                ('total_samples', C.c_int64),
+                ('wave_i16', C.c_int32), ('n_files', C.c_int32), ('B', C.c_int32), ('width', C.c_int32),
+                ('n_fft', C.c_int32), ('hop', C.c_int32), ('n_ir', C.c_int32), ('L', C.c_int32),
+                ('gain', c_f32p), ('warp', WarpArgs), ('mix', ClipMixArgs), ('mix_warp', WarpArgs),
+                ('ir', c_f32p), ('ir_taps', C.c_void_p), ('ir_index', C.c_void_p), ('span', C.c_int64),
+                ('out', C.c_void_p), ('out_samp0', C.c_void_p), ('out_win_file', C.c_void_p), ('out_win_start', C.c_void_p)]
+
+
 ADAM_MAX_GROUPS = 8                         # HFTT_ADAM_MAX_GROUPS
 
 
@@ -351,6 +364,7 @@ SIGNATURES = {
     'hftt_clip_logmel_mix': (C.c_int, [C.POINTER(ClipLogmelMixDesc), C.c_void_p]),
     'hftt_clip_logmel_mix_warp': (C.c_int, [C.POINTER(ClipLogmelMixWarpDesc), C.c_void_p]),
     'hftt_labels_render_mix': (C.c_int, [C.POINTER(LabelsMixDesc), C.c_void_p]),
+    'hftt_clip_room': (C.c_int, [C.POINTER(ClipRoomDesc), C.c_void_p]),
     'hftt_grad_norm_ws_bytes': (C.c_int64, [C.c_int64]),
     'hftt_grad_norm': (C.c_int, [c_f32p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hftt_adam_step_guarded': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32,

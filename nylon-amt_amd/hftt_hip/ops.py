@@ -10,9 +10,9 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
+from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipRoomDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
                     WARP_DELAY_MAX, WARP_STEP_MAX, WARP_STEP_MIN, WARP_TABLE_L, WARP_TABLE_LEN, WARP_ZEROS,
-                    LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, STITCH_MAX_CLIPS,
+                    LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, ROOM_MAX_TAPS, STITCH_MAX_CLIPS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
                     ATTN_Q_F16PAIR, ATTN_KV_F16PAIR, check, lib)
 
@@ -1132,7 +1132,100 @@ def audio_frames(table, hop, win_file, warp=None):
     return torch.where(ok, 1 + n // int(hop), torch.zeros_like(n)).contiguous()
 
 
-def clip_logmel(table, logmel, win_file, win_start, width, fill, gain=None, noise_std=None, seed=0, warp=None, mix=None):
+class RoomBank:
+    """The impulse responses of clip_room on one device, uploaded once: ir fp32 [n_ir, L] (1 <= L <= ROOM_MAX_TAPS; tap 0 is the direct path, so
+    that no onset moves -- corpus.synth_audio.align_ir does that to a measured response) and taps int32 [n_ir] with 1 <= taps[r] <= L (None: L
+    for every response): the entries of response r at or behind taps[r] are not read.  An equalisation filter is a response like any other."""
+
+    def __init__(self, ir, device, taps=None):
+        ir = torch.as_tensor(ir)
+        if ir.dim() != 2 or ir.shape[0] < 1 or not 1 <= ir.shape[1] <= ROOM_MAX_TAPS:
+            raise HfttError('RoomBank: ir must be [n_ir >= 1, 1 <= L <= %d], got shape %s' % (ROOM_MAX_TAPS, tuple(ir.shape)))
+        if not ir.dtype.is_floating_point or not bool(torch.isfinite(ir).all()):
+            raise HfttError('RoomBank: ir must be finite floating point, got %s' % ir.dtype)
+        self.n_ir, self.L = int(ir.shape[0]), int(ir.shape[1])
+        taps = torch.full((self.n_ir,), self.L, dtype=torch.int32) if taps is None else torch.as_tensor(taps)
+        if taps.shape != (self.n_ir,) or taps.dtype.is_floating_point or int(taps.min()) < 1 or int(taps.max()) > self.L:
+            raise HfttError('RoomBank: taps must be integers [n_ir] inside 1 .. L=%d' % self.L)
+        self.device = torch.device(device)
+        self.ir = ir.to(torch.float32).contiguous().to(self.device)
+        self.taps = taps.to(torch.int32).contiguous().to(self.device)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.ir, self.taps))
+
+
+class WetTable:
+    """what clip_room wrote, in the shape clip_logmel reads a WaveTable in: fp32 samples [B, span] as 2 B pseudo-files"""
+    dtype = 'float32'
+
+    def __init__(self, wave, file_samp0):
+        self.device, self.wave, self.file_samp0 = wave.device, wave, file_samp0
+        self.n_files, self.total_samples = file_samp0.numel() - 1, wave.numel()
+
+
+def room_span(width, hop, n_fft=2048):
+    """the samples of a scratch row that a window of `width` frames can show: (P + width - 1) * hop + n_fft / 2, P = ceil((n_fft / 2) / hop)"""
+    hop, half = int(hop), int(n_fft) // 2
+    return (-(-half // max(hop, 1)) + int(width) - 1) * hop + half
+
+
+def clip_room(table, win_file, win_start, width, bank, ir_index, hop, n_fft=2048, gain=None, warp=None, mix=None):
+    """The WET samples of B clip windows in ONE launch (hftt_clip_room): the signal clip_logmel would stage for window b -- file win_file[b] of
+    `table` (a WaveTable) under `warp` / `mix` / gain exactly as there, in front of the noise -- convolved with response ir_index[b] (int32
+    [B]) of `bank` (a RoomBank): wet[i] = sum_k h[k] dry[i - k] over the file's own extent, the tail behind its end cut.  ir_index < 0 leaves
+    the window dry (bit for bit), ir_index >= bank.n_ir makes it a window without a file.  Returns (scratch fp32 [B, span], out_samp0 int64
+    [2 B + 1], out_win_file int32 [B], out_win_start int32 [B]): row b holds the wet samples window b's frames read as pseudo-file 2 b, and a
+    plain clip_logmel over them with the two window tables gives the log-mel of the wet file.  Nothing is read back to the host."""
+    dev = table.device
+    if not isinstance(bank, RoomBank):
+        raise HfttError('clip_room: bank must be an ops.RoomBank')
+    if warp is not None and not isinstance(warp, Warp):
+        raise HfttError('clip_room: warp must be an ops.Warp')
+    if mix is not None and not isinstance(mix, Mix):
+        raise HfttError('clip_room: mix must be an ops.Mix')
+    win_file = torch.as_tensor(win_file, device=dev).to(torch.int32).contiguous()
+    win_start = torch.as_tensor(win_start, device=dev).to(torch.int32).contiguous()
+    ir_index = torch.as_tensor(ir_index, device=dev).to(torch.int32).contiguous()
+    _need_cuda(table.wave, table.file_samp0, win_file, win_start, ir_index, bank.ir, bank.taps)
+    if bank.device != dev:
+        raise HfttError('clip_room: the bank lives on %s, the corpus on %s' % (bank.device, dev))
+    if win_file.dim() != 1 or win_start.shape != win_file.shape or ir_index.shape != win_file.shape:
+        raise HfttError('clip_room: win_file, win_start and ir_index must be [B]')
+    B, width = win_file.numel(), int(width)
+    if gain is not None:
+        gain = torch.as_tensor(gain, device=dev).to(torch.float32).contiguous()
+        _need_cuda(gain)
+        if gain.shape != win_file.shape:
+            raise HfttError('clip_room: gain must be [B]')
+    span = (room_span(width, hop, n_fft) + 3) // 4 * 4 if width >= 1 and int(hop) >= 1 else 4      # (a bad request is the library's to refuse)
+    out = torch.empty((B, span), dtype=torch.float32, device=dev)
+    samp0 = torch.empty(2 * B + 1, dtype=torch.int64, device=dev)
+    ofile, ostart = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+    d = ClipRoomDesc()
+    d.wave, d.file_samp0, d.win_file, d.win_start = table.wave.data_ptr(), table.file_samp0.data_ptr(), win_file.data_ptr(), win_start.data_ptr()
+    d.total_samples, d.wave_i16, d.n_files, d.B, d.width = table.total_samples, int(table.dtype == 'int16'), table.n_files, B, width
+    d.n_fft, d.hop, d.n_ir, d.L = int(n_fft), int(hop), bank.n_ir, bank.L
+    d.gain = gain.data_ptr() if gain is not None else None
+    d.ir, d.ir_taps, d.ir_index, d.span = bank.ir.data_ptr(), bank.taps.data_ptr(), ir_index.data_ptr(), span
+    d.out, d.out_samp0, d.out_win_file, d.out_win_start = out.data_ptr(), samp0.data_ptr(), ofile.data_ptr(), ostart.data_ptr()
+    keep = []
+    if mix is not None:
+        mix._check('clip_room', B, dev)
+        d.mix.mix_file, d.mix.mix_start, d.mix.mix_gain = mix.file.data_ptr(), mix.start.data_ptr(), mix.gain.data_ptr()
+        if warp is not None or mix.warp is not None:
+            wa, wb = warp or _identity_warp(B, dev), mix.warp or _identity_warp(B, dev)
+            d.warp, ka = wa._args('clip_room', B, dev)
+            d.mix_warp, kb = wb._args('clip_room', B, dev)
+            keep += [wa, wb, ka, kb]
+    elif warp is not None:
+        d.warp, ka = warp._args('clip_room', B, dev)
+        keep.append(ka)
+    check(lib().hftt_clip_room(C.byref(d), _stream(dev)), 'clip_room')
+    return out, samp0, ofile, ostart
+
+
+def clip_logmel(table, logmel, win_file, win_start, width, fill, gain=None, noise_std=None, seed=0, warp=None, mix=None, room=None):
     """B clip windows of a waveform corpus -> spec [B, n_mels, width] fp32 in ONE launch (hftt_clip_logmel): window b shows log-mel frames
     win_start[b] .. + width of file win_file[b] of `table` (a WaveTable), each frame computed from that file's samples alone with the device
     tables of `logmel` (an ops.LogMel); frames outside the file are `fill`.  gain / noise_std: fp32 [B] device tensors or None (per-window
@@ -1140,8 +1233,18 @@ def clip_logmel(table, logmel, win_file, win_start, width, fill, gain=None, nois
     played back at each window's rate and delay (hftt_clip_logmel_warp), win_start counts frames of the warped file and the noise is keyed on
     the warped sample.  mix: an ops.Mix or None -- with one (hftt_clip_logmel_mix / _mix_warp) each window's partner is added onto the primary's
     extent: gain * primary + mix.gain * partner, then the noise; a warp on either side takes both through the warped sample (the other side
-    under the identity, which is exact).  Nothing is read back to the host."""
+    under the identity, which is exact).  room: (an ops.RoomBank, ir_index int32 [B]) or None -- with one, TWO launches and no host
+    synchronisation between them: hftt_clip_room convolves each window's dry signal (warp, gain and mix applied: both instruments stand in the
+    same room) with its response (ir_index < 0: the window stays dry) into a scratch corpus, and the plain hftt_clip_logmel reads that with
+    gain=None and the caller's noise_std / seed.  The noise is then the microphone's, behind the room, and keyed on (seed, pseudo-file 2 b,
+    position inside the scratch row), not on the source file.  Nothing is read back to the host."""
     dev = table.device
+    if room is not None:
+        if not (isinstance(room, tuple) and len(room) == 2 and isinstance(room[0], RoomBank)):
+            raise HfttError('clip_logmel: room must be (an ops.RoomBank, ir_index)')
+        _need_cuda(table.wave, table.file_samp0, logmel.window)
+        wet, samp0, ofile, ostart = clip_room(table, win_file, win_start, width, room[0], room[1], logmel.hop, logmel.n_fft, gain=gain, warp=warp, mix=mix)
+        return clip_logmel(WetTable(wet, samp0), logmel, ofile, ostart, width, fill, noise_std=noise_std, seed=seed)
     if warp is not None and not isinstance(warp, Warp):
         raise HfttError('clip_logmel: warp must be an ops.Warp')
     if mix is not None and not isinstance(mix, Mix):

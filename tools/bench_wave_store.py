@@ -17,7 +17,13 @@ call is timed with one device event on each side, after a warm-up, the stores al
 The mixed leg (clip mixing: hftt_clip_logmel_mix[_warp] + hftt_labels_render_mix): WaveClipStore.batch with mix_p 0, 0.5 and 1, without and with
 the warp above, on the same batches.  `--mix-repeats` repeats, the six stores interleaved inside each (the order rotates); a repeat's figure
 is the median of `--mix-calls` calls, the reported figure the median of the repeats, next to every repeat's.  mix_p = 0 is the un-mixed
-leg the others are read against.  Measured, no threshold."""
+leg the others are read against.  Measured, no threshold.
+
+  python tools/bench_wave_store.py --room-out profiles/clip_room.json [--room-taps 4096] [--step-ms 27.65]
+
+The room leg (reverb: hftt_clip_room + the plain hftt_clip_logmel on its scratch): WaveClipStore.batch without augmentation and with room_p = 1
+(every clip wet, a bank of 32 responses from corpus.synth_audio.synth_room_bank with its own lengths), interleaved as above, and the launches
+alone under draws made beforehand: hftt_clip_room, the clip log-mel on the source corpus and on the scratch."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'nylon-amt_amd'))
@@ -105,6 +111,50 @@ def mixed_calls(store, warped, chunks, repeats, calls, warmup):
     return {n: float(np.median(v)) for n, v in per.items()}
 
 
+def room_leg(wstore, config, dev, chunks, repeats=5, calls=60, warmup=10, taps=4096, n_ir=32):
+    """{leg: {'ms': median over the repeats, 'repeats': [...]}} for the store without and with the room (every clip wet), interleaved inside every
+    repeat (the order rotates), and 'calls': the launches alone"""
+    ir, ir_taps = SA.synth_room_bank(n_ir, config['feature']['sr'], taps=taps, seed=1)
+    bank = ops.RoomBank(ir, dev, taps=ir_taps)
+    legs = {'room_off': WaveClipStore(wstore, config, dev, wave_dtype='int16'),
+            'room_on': WaveClipStore(wstore, config, dev, wave_dtype='int16', augment=WaveAugment(seed=1, room_p=1.0, room_bank=bank))}
+    names = list(legs)
+    assert len(chunks) >= warmup + calls, 'corpus too small for %d calls' % (warmup + calls)
+    store = legs['room_on']
+    c = chunks[0]
+    file, start = store.clip_file[c], store.clip_frame[c] - store.mb
+    width = store.mb + store.T + store.mf
+    index = store.augment.draw_room(len(c))
+    wet, samp0, ofile, ostart = ops.clip_room(store.waves, file, start, width, bank, index, store.logmel.hop)
+    scratch = ops.WetTable(wet, samp0)
+    fns = {'clip_room': lambda: ops.clip_room(store.waves, file, start, width, bank, index, store.logmel.hop),
+           'clip_logmel': lambda: ops.clip_logmel(store.waves, store.logmel, file, start, width, store.fill),
+           'clip_logmel_on_scratch': lambda: ops.clip_logmel(scratch, store.logmel, ofile, ostart, width, store.fill)}
+    per, per_fn = {n: [] for n in names}, {n: [] for n in fns}
+    for r in range(repeats):
+        t, tf = {n: [] for n in names}, {n: [] for n in fns}
+        for i, c in enumerate(chunks[:warmup + calls]):
+            for n in names[r % len(names):] + names[:r % len(names)]:
+                ms, _ = timed(lambda: legs[n].batch(c))
+                if i >= warmup:
+                    t[n].append(ms)
+            for n, fn in fns.items():
+                ms, _ = timed(fn)
+                if i >= warmup:
+                    tf[n].append(ms)
+        for n in names:
+            per[n].append(float(np.median(t[n])))
+        for n in fns:
+            per_fn[n].append(float(np.median(tf[n])))
+    out = {n: {'ms': float(np.median(v)), 'repeats': v} for n, v in per.items()}
+    out['room_on']['extra_ms_over_room_off'] = out['room_on']['ms'] - out['room_off']['ms']
+    out['calls'] = {n: {'ms': float(np.median(v)), 'repeats': v} for n, v in per_fn.items()}
+    gmac = float((ir_taps[index.cpu().numpy()].astype(np.float64) * np.diff(samp0.cpu().numpy())[::2]).sum()) / 1e9
+    out['bank'] = {'n_ir': n_ir, 'L': taps, 'ir_taps_min_median_max': [int(ir_taps.min()), int(np.median(ir_taps)), int(ir_taps.max())],
+                   'clip_room_gmac_of_the_timed_call': gmac, 'scratch_bytes': wet.numel() * 4, 'bank_bytes': bank.nbytes()}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--files', type=int, default=2, help='synthetic one-minute files')
@@ -116,11 +166,33 @@ def main():
     ap.add_argument('--mix-out', default='', help='run the mixed leg alone and write it here')
     ap.add_argument('--mix-repeats', type=int, default=5)
     ap.add_argument('--mix-calls', type=int, default=60)
+    ap.add_argument('--room-out', default='', help='run the room leg alone and write it here')
+    ap.add_argument('--room-taps', type=int, default=4096)
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     config = finalize_config(prepare_config(SA.default_config()))
     notes = [SA.pluck_notes(2000 + i) for i in range(args.files)]
     waves = [SA.pluck_wave(a, device=dev) for a in notes]
+    if args.room_out:
+        wstore = assemble_wave_store([w.cpu().numpy() for w in waves], notes, config)
+        n = len(wstore['clip_file'])
+        ids = torch.randperm(n, generator=torch.Generator().manual_seed(1))
+        chunks = [ids[i:i + args.batch].to(dev) for i in range(0, n - args.batch + 1, args.batch)]
+        cin = config['input']
+        res = {'what': 'WaveClipStore.batch without and with the room (room_p = 1, every clip wet) and the launches alone: device events around each call; per repeat the median of the calls, reported the median of the repeats',
+               'device': torch.cuda.get_device_name(0), 'files': args.files, 'clips': n, 'batch': args.batch, 'window_frames': cin['margin_b'] + cin['num_frame'] + cin['margin_f'],
+               'mel_bins': config['feature']['mel_bins'], 'repeats': args.mix_repeats, 'calls': args.mix_calls, 'warmup': 10,
+               'legs': room_leg(wstore, config, dev, chunks, args.mix_repeats, args.mix_calls, 10, args.room_taps)}
+        if args.step_ms > 0.0:
+            res['benchmark_step_ms_median'] = args.step_ms
+            res['room_extra_share_of_step'] = res['legs']['room_on']['extra_ms_over_room_off'] / args.step_ms
+            res['clip_room_share_of_step'] = res['legs']['calls']['clip_room']['ms'] / args.step_ms
+        os.makedirs(os.path.dirname(os.path.abspath(args.room_out)), exist_ok=True)
+        with open(args.room_out, 'w') as fh:
+            json.dump(res, fh, indent=1)
+            fh.write('\n')
+        print(json.dumps(res))
+        return
     if args.mix_out:
         wstore = assemble_wave_store([w.cpu().numpy() for w in waves], notes, config)
         n = len(wstore['clip_file'])

@@ -10,7 +10,9 @@ instead of the label tracks (assemble_note_store, NoteClipStore) and every batch
 WAVEFORMS (int16) and the notes (assemble_wave_store, WaveClipStore): no feature pass, every batch's log-mel windows are computed on the device,
 optionally under --aug-gain-db LO HI / --aug-noise-dbfs LO HI (per-clip gain and additive noise, new for every batch) and --aug-pitch LO HI /
 --aug-detune-cents C / --aug-shift / --aug-warp-p P (per-clip pitch shift, detune and time offset: the clip is resampled and its labels move with it)
-and --aug-mix-p P / --aug-mix-gain-db LO HI (clip mixing: a second clip summed in, the labels those of the sum).  Training: the product's own step
+and --aug-mix-p P / --aug-mix-gain-db LO HI (clip mixing: a second clip summed in, the labels those of the sum) and --aug-room-p P with
+--aug-room-rt60 LO HI / --aug-room-drr-db LO HI / --aug-room-taps L or --aug-room-bank FILE.npz (reverb: the clip convolved with an impulse
+response of a synthetic or supplied bank, the labels unchanged).  Training: the product's own step
 (hftt_hip.trainer.TrainStep: forward + fused loss + backward + fused Adam) in the chosen precision mode, dropout 0.1, batch 8, until the
 time budget is spent.  The model is pickled the way m_training.py:372-373 does it (whole module, protocol 4).
 
@@ -27,7 +29,10 @@ from corpus.conv_note2label import note2label_arrays
 from corpus.make_dataset import assemble_note_store, assemble_store, assemble_wave_store
 from training.dataset import MyDataset, DeviceClipStore, NoteClipStore, WaveAugment, WaveClipStore
 from model.amt import AMT
+from hftt_hip import ops
 from evaluation.metrics import note_metrics, frame_metrics
+
+ROOM_BANK_SIZE = 32          # responses of the synthetic room bank (--aug-room-p without --aug-room-bank)
 
 
 def build_corpus(config, files, dev, n_slice=8, note_store=False, wave_store=False, augment=None):
@@ -202,6 +207,11 @@ def main():
     ap.add_argument('--aug-warp-p', type=float, default=1.0, metavar='P', help='probability that a clip is warped at all (pitch, detune, shift)')
     ap.add_argument('--aug-mix-p', type=float, default=0.0, metavar='P', help='with --wave-store: probability that a clip is summed with another clip of the corpus (the labels are those of the sum)')
     ap.add_argument('--aug-mix-gain-db', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --aug-mix-p: the partner clip\'s gain, uniform in dB (default -6 0)')
+    ap.add_argument('--aug-room-p', type=float, default=0.0, metavar='P', help='with --wave-store: probability that a clip is convolved with an impulse response of the room bank (the labels are unchanged)')
+    ap.add_argument('--aug-room-rt60', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --aug-room-p: reverberation time of the synthetic bank in seconds, uniform (default 0.15 0.8)')
+    ap.add_argument('--aug-room-drr-db', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --aug-room-p: direct-to-reverberant ratio of the synthetic bank in dB, uniform (default 0 12)')
+    ap.add_argument('--aug-room-taps', type=int, default=None, metavar='L', help='with --aug-room-p: taps of the synthetic bank (default 4096, at most 8192)')
+    ap.add_argument('--aug-room-bank', default='', metavar='FILE.npz', help='with --aug-room-p: a bank of measured responses or equalisation filters instead (arrays ir [n, L] and taps [n])')
     ap.add_argument('--out', default='gpurun_out/config5_tiny.pkl')
     ap.add_argument('--score-only', default='', help='skip training: score this pickled model')
     ap.add_argument('--init', default='', help='start from this pickled model (weights only: the optimizer state starts afresh) -- chains runs that are each bounded by the GPU call limit')
@@ -218,6 +228,12 @@ def main():
     mix_aug = args.aug_mix_p != 0.0 or args.aug_mix_gain_db is not None
     if mix_aug and not args.wave_store:
         ap.error('--aug-mix-p / --aug-mix-gain-db act on the waveform: they need --wave-store')
+    room_synth = args.aug_room_rt60 is not None or args.aug_room_drr_db is not None or args.aug_room_taps is not None
+    room_aug = args.aug_room_p != 0.0 or room_synth or bool(args.aug_room_bank)
+    if room_aug and not args.wave_store:
+        ap.error('--aug-room-p / --aug-room-rt60 / --aug-room-drr-db / --aug-room-taps / --aug-room-bank act on the waveform: they need --wave-store')
+    if room_synth and args.aug_room_bank:
+        ap.error('--aug-room-bank supplies the responses: --aug-room-rt60 / --aug-room-drr-db / --aug-room-taps describe the synthetic bank')
     if args.freeze and not args.init:
         ap.error('--freeze keeps pretrained weights fixed: it needs --init')
     groups = None
@@ -242,15 +258,26 @@ def main():
         if (args.aug_gain_db or args.aug_noise_dbfs) and not args.wave_store:
             ap.error('--aug-gain-db / --aug-noise-dbfs act on the waveform: they need --wave-store')
         augment = None
-        if args.aug_gain_db or args.aug_noise_dbfs or warp_aug or mix_aug:
+        if args.aug_gain_db or args.aug_noise_dbfs or warp_aug or mix_aug or room_aug:
+            bank = None
+            if args.aug_room_p > 0.0:
+                if args.aug_room_bank:
+                    with np.load(args.aug_room_bank) as z:
+                        bank = ops.RoomBank(z['ir'], dev, taps=z['taps'])
+                else:
+                    ir, taps = SA.synth_room_bank(ROOM_BANK_SIZE, config['feature']['sr'], taps=args.aug_room_taps or 4096, rt60=args.aug_room_rt60 or (0.15, 0.8),
+                                                  drr_db=args.aug_room_drr_db or (0.0, 12.0), seed=args.seed)
+                    bank = ops.RoomBank(ir, dev, taps=taps)
             augment = WaveAugment(gain_db=args.aug_gain_db, noise_dbfs=args.aug_noise_dbfs, seed=args.seed, pitch_semitones=args.aug_pitch,
                                   detune_cents=args.aug_detune_cents, shift=args.aug_shift, p_warp=args.aug_warp_p, mix_p=args.aug_mix_p,
-                                  mix_gain_db=args.aug_mix_gain_db or (-6.0, 0.0))
+                                  mix_gain_db=args.aug_mix_gain_db or (-6.0, 0.0), room_p=args.aug_room_p, room_bank=bank)
         clips, log['corpus'] = build_corpus(config, args.files, dev, note_store=args.note_store, wave_store=args.wave_store, augment=augment)
         if args.wave_store:
             log['augment'] = {'gain_db': args.aug_gain_db, 'noise_dbfs': args.aug_noise_dbfs, 'pitch_semitones': args.aug_pitch,
                               'detune_cents': args.aug_detune_cents, 'shift': args.aug_shift, 'p_warp': args.aug_warp_p,
-                              'mix_p': args.aug_mix_p, 'mix_gain_db': args.aug_mix_gain_db}
+                              'mix_p': args.aug_mix_p, 'mix_gain_db': args.aug_mix_gain_db, 'room_p': args.aug_room_p,
+                              'room_bank': None if augment is None or augment.room_bank is None else
+                              {'source': args.aug_room_bank or 'synth_room_bank', 'n_ir': augment.room_bank.n_ir, 'L': augment.room_bank.L}}
         # ---- training ----
         model = model.to(dev)
         saver = None
