@@ -976,6 +976,87 @@ typedef struct {
 int hftt_clip_room(const hftt_clip_room_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Clip synth (csrc/clip_synth.hip, csrc/clip_synth_fn.h): modal synthesis -- the windows of a training batch RENDERED from the note table of
+ * the label renderer above under one voice of a device-resident bank each, so that a corpus needs note lists only: no audio is collected,
+ * aligned or stored.  It writes the scratch corpus and the three tables of hftt_clip_room, under which the unchanged hftt_clip_logmel reads
+ * device-made samples as files.  One entry point ADDED at ABI 8; HFTT_ABI_VERSION stays 8 and every descriptor above keeps its layout.
+ *
+ * Inputs: the note table of hftt_labels_desc -- notes, row_ptr, n_files, n_notes, N -- and file_nsamp int64 [n_files], the length n' of each
+ * synthetic file in samples (negative: 0); the window tables win_file / win_start [B] and width, hop, n_fft with the meaning they have in
+ * hftt_clip_logmel; sr, the sample rate; lead >= 0, further frames rendered in front of each window (below); and the VOICE BANK, V voices of H
+ * partials, 1 <= H <= HFTT_SYNTH_MAX_PARTIALS, all tables built on the host and in device memory:
+ *     inc       uint32 [V, N, H]  phase increment of a partial in turns per sample, Q32 (frequency / sr * 2^32)
+ *     amp       fp32   [V, N, H]  0 switches a partial off (the host zeroes partials at or above Nyquist)
+ *     dec       fp32   [V, N, H]  >= 0: decay in log2 units per sample
+ *     vel_gain  fp32   [V, 128]   the velocity curve
+ *     rel       fp32   [V]        >= 0: additional decay per sample behind the note's offset
+ *     attack    int32  [V]        samples, >= 1          release  int32 [V]  samples, >= 0: how long a note sounds behind its offset
+ *     voice_index int32 [B]: window b's voice; outside 0 .. V - 1: a window without a file
+ * attack < 1, release < 0 and a velocity outside 0 .. 127 cannot be refused by the host: the kernel clamps them (to 1, to 0, into 0 .. 127).
+ * The kernel is a generic modal synthesizer; the instrument lives in the host function that fills the bank (corpus/synth_audio.py).
+ *
+ * The sample.  A record of pitch index p in file f has n_on = (int64)(onset_sec * sr + 0.5), n_off = (int64)(offset_sec * sr + 0.5) (fp64,
+ * the product and the sum rounded separately) and D = max(n_off - n_on, 1).  Under voice v it sounds at file sample i when
+ * 0 <= tau = i - n_on < D + release[v], and there its partial h contributes c * S(u) with, every operation in fp32 and rounded once:
+ *     u   = (float)(int32)(inc[v,p,h] * (uint32)tau) * 2^-32            the product wraps: the phase is exact at any tau; u in [-0.5, 0.5]
+ *     tf  = (float)tau,  rf = (float)max(0, tau - D)                    (exact below 2^24)
+ *     x   = min(dec[v,p,h] * tf + rel[v] * rf, 126)                     two products, one sum
+ *     ra  = (float)min(tau + 1, attack[v]) / (float)attack[v]           IEEE division
+ *     c   = ((amp[v,p,h] * vel_gain[v, velocity]) * ra) * E(-x)
+ * S(u) = sin(2 pi u) is the hardware's v_sin_f32, which takes its argument in turns; E(y) = 2^y is v_exp_f32, whose argument the clamp keeps
+ * inside [-126, 0] (no denormal result).  Both are defined once in csrc/clip_synth_fn.h; their errors against fp64 as measured on an MI355X
+ * are in profiles/clip_synth_mi355x.txt.  The sample of file f under voice v at i, 0 <= i < n', is
+ *     acc = +0;  acc = fma(c, S(u), acc)  over the file's records in TABLE order -- pitch group after pitch group, list order inside a
+ *     group -- and inside a record over h = 0 .. H - 1; a record that does not sound at i contributes no operation
+ * so a sample where nothing sounds is +0.0f.  The value depends on (f, v, i) only -- not on win_start, on lead, on where a workgroup's tile
+ * begins or on the launch geometry: S and E are evaluated per sample, there is no recurrence.  Two overlapping windows with equal voices see
+ * the same waveform, bit for bit and from run to run.
+ *
+ * Outputs: the room's convention.  out fp32 [B, span], span >= (P + lead + width - 1) * hop + n_fft / 2 with P = ceil((n_fft / 2) / hop);
+ * out_samp0 int64 [2 B + 1], out_win_file / out_win_start int32 [B].  Row b holds pseudo-file 2 b = samples [o_b, e_b) of the synthetic file,
+ *     o_b = max(0, win_start[b] - P - lead) * hop,   e_b = min(n', (win_start[b] + width - 1) * hop + n_fft / 2)     (empty when e_b <= o_b)
+ * and pseudo-file 2 b + 1, the unused remainder of the row (not written); out_samp0[2 b] = b * span, out_win_file[b] = 2 b,
+ * out_win_start[b] = win_start[b] - o_b / hop.  A window without a valid file, with voice_index[b] outside 0 .. V - 1 or with o_b > n' gets
+ * out_win_file[b] = -1.  With lead = 0 these are the tables hftt_clip_room writes, and a plain hftt_clip_logmel over `out` (wave_i16 = 0, n_files =
+ * 2 B, total_samples = B * span) gives, bit for bit and in the fill columns too, the log-mel of the whole synthetic file (the room's argument).
+ * lead exists so that a room can follow: with lead >= ceil(taps / hop), hftt_clip_room run over this scratch corpus as ITS corpus (win_file =
+ * out_win_file, win_start = out_win_start) has the full history of every wet sample the clip shows.
+ *
+ * One launch: a workgroup owns a window and a tile of 2,048 consecutive samples.  It scans the file's records, which are contiguous (row_ptr[f N]
+ * .. row_ptr[(f + 1) N]), HFTT_SYNTH_CHUNK at a time, keeps those whose sounding range meets the tile in LDS in table order (prefix sum; the
+ * pitch of a record from the file's N + 1 row pointers staged in LDS), and every thread walks the survivors with eight samples in registers; the
+ * bank rows are uniform over the workgroup and are read on the scalar unit.  More sounding records than a chunk holds are further passes.
+ * One writer per element, no atomics, no workspace, 64-bit sample indices.
+ * Refused in front of the launch: null pointers (notes excepted at n_notes == 0); n_fft != 2048; B, width, hop, n_files or V < 1; n_notes
+ * < 0; N outside 1 .. 128; H outside 1 .. HFTT_SYNTH_MAX_PARTIALS; a bank of 2^31 entries (V N H) or more; lead < 0; sr <= 0 (or
+ * not finite); span below the bound above; B above 2^30, or 2^31 workgroups and more.
+ * --------------------------------------------------------------------------------------------- */
+#define HFTT_SYNTH_MAX_PARTIALS 32
+#define HFTT_SYNTH_CHUNK 256
+typedef struct {
+  const hftt_label_note* notes;                                  /* [n_notes] (may be NULL when n_notes == 0) */
+  const int32_t* row_ptr;                                        /* [n_files * N + 1] */
+  const int64_t* file_nsamp;                                     /* [n_files] */
+  const int32_t* win_file; const int32_t* win_start;             /* [B] */
+  int32_t n_files, n_notes;
+  int32_t B, width, N;
+  int32_t n_fft, hop, lead;
+  double sr;
+  int32_t V, H;
+  const uint32_t* inc;                                           /* [V, N, H] */
+  const float* amp; const float* dec;                            /* [V, N, H] */
+  const float* vel_gain;                                         /* [V, 128] */
+  const float* rel;                                              /* [V] */
+  const int32_t* attack; const int32_t* release;                 /* [V] */
+  const int32_t* voice_index;                                    /* [B] */
+  int64_t span;
+  void* out;                                                     /* fp32 [B, span] */
+  int64_t* out_samp0;                                            /* [2 B + 1] */
+  int32_t* out_win_file; int32_t* out_win_start;                 /* [B] */
+} hftt_clip_synth_desc;
+int hftt_clip_synth(const hftt_clip_synth_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Guarded optimizer step (csrc/guard.hip): global-norm gradient clipping, a non-finite guard and decoupled weight decay around the fused
  * Adam.  Like the note decoder and the label renderer these entry points were ADDED at ABI 8 and HFTT_ABI_VERSION stays 8: nothing that an
  * ABI-8 caller binds changed (hftt_adam_step above is untouched and remains the default step); a caller that needs them looks the symbols up.

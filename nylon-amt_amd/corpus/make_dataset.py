@@ -5,7 +5,8 @@ pickles): the corpus is ONE array per tensor, each file preceded / followed by p
 its own padding -- ``margin_b`` rows first, then per file ``n_i`` rows of data followed by ``margin_f + num_frame - 1`` rows of padding;
 ``idx`` lists the first frame of every clip (every frame of every file).  The feature padding value is ``log(log_offset)`` (:105-113),
 label padding is zero.  ``assemble_note_store`` lays out the same ``feature`` and ``idx`` but keeps the NOTES of every file instead of four label
-tracks (training.dataset.NoteClipStore renders a batch's labels from them when it gathers it).  ``synth_store`` fills such a store with the
+tracks (training.dataset.NoteClipStore renders a batch's labels from them when it gathers it).  ``assemble_synth_store`` keeps the notes ALONE (training.dataset.SynthClipStore renders the
+audio too).  ``synth_store`` fills such a store with the
 synthetic recipe of SURVEY.md section 8(d) config 1."""
 import numpy as np
 
@@ -75,6 +76,25 @@ def assemble_wave_store(waves, notes_per_file, config):
     clip_file = np.repeat(np.arange(len(waves), dtype=np.int32), nf)
     clip_frame = np.concatenate([np.arange(n, dtype=np.int32) for n in nf])
     return {'waves': list(waves), 'file_nsamp': file_nsamp, 'table': table, 'clip_file': clip_file, 'clip_frame': clip_frame}
+
+
+def assemble_synth_store(notes_per_file, config, release_samples=0):
+    """assemble_wave_store without waves: the corpus of training.dataset.SynthClipStore is the note lists alone -- dict(table: the host note
+    table; file_nsamp int64 [n_files]: the length of each synthetic file, ceil(file_end_sec * sr) + release_samples (release_samples: how long
+    the longest voice sounds behind an offset, VoiceBank's largest `release`; a file without notes is release_samples of silence); clip_file
+    int32 / clip_frame int32: every frame 0 .. nf - 1 of every file, nf = max(1 + n_samp // hop, label frames), as assemble_wave_store lists them)."""
+    from hftt_hip.ops import labels_table_host
+    if int(release_samples) < 0:
+        raise ValueError('assemble_synth_store: release_samples=%r is negative' % (release_samples,))
+    table = labels_table_host(notes_per_file, config)
+    hop, sr = config['feature']['hop_sample'], config['feature']['sr']
+    file_nsamp = np.ceil(table['file_end_sec'] * sr).astype(np.int64) + int(release_samples)
+    nf = np.maximum(1 + file_nsamp // hop, table['file_nframe'].astype(np.int64))
+    if int(nf.sum()) >= 1 << 31:
+        raise ValueError('assemble_synth_store: %d clips exceed the int32 index' % int(nf.sum()))
+    clip_file = np.repeat(np.arange(len(notes_per_file), dtype=np.int32), nf)
+    clip_frame = np.concatenate([np.arange(n, dtype=np.int32) for n in nf])
+    return {'file_nsamp': file_nsamp, 'table': table, 'clip_file': clip_file, 'clip_frame': clip_frame}
 
 
 def prepare_config(config, max_value=0.0):

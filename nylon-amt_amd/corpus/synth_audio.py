@@ -94,3 +94,89 @@ def align_ir(h):
     out = np.zeros_like(h)
     out[:h.size - p] = h[p:]
     return (out / np.sqrt(np.sum(out * out))).astype(np.float32)
+
+
+def _pitch_hz(config):
+    cm = config['midi']
+    return 440.0 * np.power(2.0, (int(cm['note_min']) + np.arange(int(cm['num_note']), dtype=np.float64) - 69.0) / 12.0)
+
+
+def _inc_q32(freq, sr):
+    """phase increments in turns per sample as Q32 (uint32), 0 for a partial at or above Nyquist; and the mask of the partials below it"""
+    below = freq < 0.5 * sr
+    return np.where(below, np.round(freq / sr * 4294967296.0), 0.0).astype(np.uint64).astype(np.uint32), below
+
+
+def synth_voice_bank(n, config, seed, partials=16, inharmonicity=(1e-5, 4e-4), detune_cents=6.0, pluck_pos=(0.08, 0.45), rolloff=(0.6, 1.6),
+                     t60=(0.8, 4.0), pitch_damping=(0.3, 0.8), partial_damping=(0.02, 0.4), release_t60=(0.03, 0.25), attack_ms=(0.3, 4.0),
+                     level=(0.03, 0.12), velocity_exponent=(0.7, 1.8)):
+    """n voices of a plucked-string family for hftt_hip.ops.VoiceBank -> dict(inc uint32 [n, N, H], amp, dec fp32 [n, N, H], vel_gain fp32
+    [n, 128], rel fp32 [n], attack, release int32 [n]); N = config.midi.num_note pitches from note_min, H = partials, sr = config.feature.sr.
+    Everything is drawn and formed in fp64 and rounded once.  Per voice, each quantity uniform in its range (log-uniform where it spans decades):
+        partial k = 1 .. H of the pitch with fundamental f0:  frequency k f0 sqrt(1 + B k^2) 2^(c_k / 1200) -- B the string's inharmonicity,
+            c_k a detune uniform in +-detune_cents per partial (well under 50: the label's pitch stays the nearest one); at or above Nyquist the
+            partial is off (amp = 0)
+        amplitude  level |sin(k pi beta)| / k^rho, scaled so that the strongest partial of a pitch has `level` -- beta the pluck position
+            (the comb of a string plucked at beta of its length), rho the roll-off
+        decay      sigma_k = (sigma0 + sigma1 k^2) (f0 / 261.6 Hz)^gamma per second, sigma0 = 3 ln 10 / t60 (the fundamental of middle C is 60 dB
+            down after t60 seconds), sigma1 = partial_damping sigma0; as log2 units per sample: sigma_k log2(e) / sr
+        release    behind the offset the note falls by a further 60 dB in release_t60 seconds and is cut there; attack: a linear ramp of
+            attack_ms; velocity curve (velocity / 127)^e with e in velocity_exponent"""
+    sr = float(config['feature']['sr'])
+    H = int(partials)
+    if n < 1 or H < 1:
+        raise ValueError('synth_voice_bank: n=%r and partials=%r must be positive' % (n, partials))
+    if not 0.0 <= float(detune_cents) < 50.0:
+        raise ValueError('synth_voice_bank: detune_cents=%r outside 0 .. 50' % (detune_cents,))
+    rng = np.random.RandomState(seed)
+    f0 = _pitch_hz(config)
+    N = len(f0)
+    k = np.arange(1, H + 1, dtype=np.float64)
+    uni = lambda r: float(rng.uniform(r[0], r[1]))
+    logu = lambda r: float(np.exp(rng.uniform(np.log(r[0]), np.log(r[1]))))
+    out = {'inc': np.zeros((n, N, H), np.uint32), 'amp': np.zeros((n, N, H), np.float32), 'dec': np.zeros((n, N, H), np.float32),
+           'vel_gain': np.zeros((n, 128), np.float32), 'rel': np.zeros(n, np.float32), 'attack': np.zeros(n, np.int32), 'release': np.zeros(n, np.int32)}
+    for v in range(n):
+        B, beta, rho = logu(inharmonicity), uni(pluck_pos), uni(rolloff)
+        sigma0 = 3.0 * np.log(10.0) / logu(t60)
+        gamma, sigma1 = uni(pitch_damping), logu(partial_damping) * sigma0
+        rt60, att, lev, ve = logu(release_t60), logu(attack_ms), logu(level), uni(velocity_exponent)
+        cents = rng.uniform(-detune_cents, detune_cents, H)
+        freq = k[None, :] * f0[:, None] * np.sqrt(1.0 + B * k[None, :] ** 2) * np.power(2.0, cents[None, :] / 1200.0)
+        inc, below = _inc_q32(freq, sr)
+        a = np.abs(np.sin(k * np.pi * beta)) / np.power(k, rho)
+        a = np.where(below, a[None, :], 0.0)
+        a = lev * a / np.maximum(a.max(axis=1, keepdims=True), 1e-300)
+        sigma = (sigma0 + sigma1 * k[None, :] ** 2) * np.power(f0[:, None] / 261.6255653, gamma)
+        out['inc'][v], out['amp'][v], out['dec'][v] = inc, a, sigma * np.log2(np.e) / sr
+        out['vel_gain'][v] = np.power(np.arange(128, dtype=np.float64) / 127.0, ve)
+        out['rel'][v] = 3.0 * np.log(10.0) / rt60 * np.log2(np.e) / sr
+        out['attack'][v], out['release'][v] = max(1, int(round(att * 1e-3 * sr))), int(np.ceil(rt60 * sr))
+    return out
+
+
+def pluck_voice(config):
+    """ONE voice with pluck_wave's recipe, for continuity with the corpus every trained fixture rests on: partials 1, 1/2, 1/4 at f0, 2 f0, 3 f0
+    (off at or above Nyquist), envelope exp(-3 t) from the onset, sounding until 0.3 s behind the offset without a further decay, amplitude
+    velocity / 127 * 0.1, no attack ramp.  NOT sample-equal to pluck_wave: there the phase is sin(2 pi f t) of the ABSOLUTE time t in fp32, here it
+    runs from the note's onset sample (and the onset is rounded to a sample); the two differ by a phase per note and by pluck_wave's fp32 time."""
+    sr = float(config['feature']['sr'])
+    f0 = _pitch_hz(config)
+    freq = f0[:, None] * np.arange(1, 4, dtype=np.float64)[None, :]
+    inc, below = _inc_q32(freq, sr)
+    amp = np.where(below, 0.1 * np.array([1.0, 0.5, 0.25])[None, :], 0.0)
+    return {'inc': inc[None], 'amp': amp[None].astype(np.float32), 'dec': np.full((1,) + freq.shape, 3.0 * np.log2(np.e) / sr, np.float32),
+            'vel_gain': (np.arange(128, dtype=np.float64) / 127.0).astype(np.float32)[None], 'rel': np.zeros(1, np.float32),
+            'attack': np.ones(1, np.int32), 'release': np.full(1, int(round(0.3 * sr)), np.int32)}
+
+
+def render_file(table, bank, file, voice, nsamp, hop=256, n_fft=2048):
+    """the whole synthetic file `file` of `table` (an ops.LabelsTable) under voice `voice` of `bank` (an ops.VoiceBank), nsamp samples long ->
+    fp32 [nsamp] on the table's device: hftt_clip_synth with ONE window that covers the file, for listening and for the tests"""
+    from hftt_hip import ops
+    nsamp = int(nsamp)
+    width = max(1, -(-(nsamp - n_fft // 2) // hop) + 1)                         # (width - 1) hop + n_fft / 2 >= nsamp
+    file_nsamp = torch.zeros(table.n_files, dtype=torch.int64)
+    file_nsamp[file] = nsamp
+    out, samp0, _, _ = ops.clip_synth(table, file_nsamp.to(table.device), bank, [voice], [file], [0], width, hop, table.sr, n_fft=n_fft)
+    return out[0, :nsamp]

@@ -287,6 +287,23 @@ class ClipRoomDesc(C.Structure):            # hftt_clip_room_desc: the windows' 
                 ('out', C.c_void_p), ('out_samp0', C.c_void_p), ('out_win_file', C.c_void_p), ('out_win_start', C.c_void_p)]
 
 
+SYNTH_MAX_PARTIALS = 32                     # HFTT_SYNTH_MAX_PARTIALS
+SYNTH_CHUNK = 256                           # HFTT_SYNTH_CHUNK
+
+
+class ClipSynthDesc(C.Structure):           # hftt_clip_synth_desc: the windows rendered from the note table under a voice of the bank -> a scratch corpus
+    _fields_ = [('notes', C.c_void_p), ('row_ptr', C.c_void_p), ('file_nsamp', C.c_void_p), ('win_file', C.c_void_p), ('win_start', C.c_void_p),
+                ('n_files', C.c_int32), ('n_notes', C.c_int32),
+                ('B', C.c_int32), ('width', C.c_int32), ('N', C.c_int32),
+                ('n_fft', C.c_int32), ('hop', C.c_int32), ('lead', C.c_int32),
+                ('sr', C.c_double),
+                ('V', C.c_int32), ('H', C.c_int32),
+                ('inc', C.c_void_p), ('amp', c_f32p), ('dec', c_f32p), ('vel_gain', c_f32p), ('rel', c_f32p),
+                ('attack', C.c_void_p), ('release', C.c_void_p), ('voice_index', C.c_void_p),
+                ('span', C.c_int64),
+                ('out', C.c_void_p), ('out_samp0', C.c_void_p), ('out_win_file', C.c_void_p), ('out_win_start', C.c_void_p)]
+
+
 ADAM_MAX_GROUPS = 8                         # HFTT_ADAM_MAX_GROUPS
 
 
@@ -365,6 +382,7 @@ SIGNATURES = {
     'hftt_clip_logmel_mix_warp': (C.c_int, [C.POINTER(ClipLogmelMixWarpDesc), C.c_void_p]),
     'hftt_labels_render_mix': (C.c_int, [C.POINTER(LabelsMixDesc), C.c_void_p]),
     'hftt_clip_room': (C.c_int, [C.POINTER(ClipRoomDesc), C.c_void_p]),
+    'hftt_clip_synth': (C.c_int, [C.POINTER(ClipSynthDesc), C.c_void_p]),
     'hftt_grad_norm_ws_bytes': (C.c_int64, [C.c_int64]),
     'hftt_grad_norm': (C.c_int, [c_f32p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hftt_adam_step_guarded': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32,

@@ -10,9 +10,9 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipRoomDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
+from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipRoomDesc, ClipSynthDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
                     WARP_DELAY_MAX, WARP_STEP_MAX, WARP_STEP_MIN, WARP_TABLE_L, WARP_TABLE_LEN, WARP_ZEROS,
-                    LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, ROOM_MAX_TAPS, STITCH_MAX_CLIPS,
+                    LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, ROOM_MAX_TAPS, STITCH_MAX_CLIPS, SYNTH_MAX_PARTIALS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
                     ATTN_Q_F16PAIR, ATTN_KV_F16PAIR, check, lib)
 
@@ -1479,3 +1479,98 @@ def labels_render(table, win_file, win_start, length, form='train', duration_tol
     else:
         check(lib().hftt_labels_render(C.byref(d), _stream(dev)), 'labels_render')
     return onset, offset, (mpe if train else mpe.view(torch.bool)), velocity
+
+
+# ------------------------------------------------------------------------------------------------
+# Clip synth (hftt_clip_synth): the corpus keeps NOTES only, a batch's waveforms are rendered from them when it is gathered
+class VoiceBank:
+    """The voices of clip_synth on one device, uploaded once: V voices of H decaying partials for each of N pitches --
+        inc uint32 [V, N, H] (phase increment, turns per sample in Q32; integers inside 0 .. 2^32 - 1 of any integer dtype), amp fp32 [V, N, H]
+        (0: the partial is off), dec fp32 [V, N, H] >= 0 (log2 units per sample), vel_gain fp32 [V, 128], rel fp32 [V] >= 0 (additional decay per
+        sample behind the offset), attack int [V] >= 1 and release int [V] >= 0 (samples)
+    with 1 <= H <= SYNTH_MAX_PARTIALS.  The kernel is a generic modal synthesizer: the instrument lives in whatever fills these tables
+    (corpus.synth_audio.synth_voice_bank / pluck_voice)."""
+
+    def __init__(self, inc, amp, dec, vel_gain, rel, attack, release, device):
+        def tensor(t):                                  # (numpy's unsigned integers as int64: torch has no arithmetic on them)
+            if torch.is_tensor(t):
+                return t.cpu()
+            a = np.asarray(t)
+            return torch.from_numpy(np.ascontiguousarray(a.astype(np.int64) if a.dtype.kind in 'ui' else a))
+        inc, amp, dec, vel_gain, rel, attack, release = (tensor(t) for t in (inc, amp, dec, vel_gain, rel, attack, release))
+        if amp.dim() != 3 or min(amp.shape) < 1 or not 1 <= amp.shape[1] <= 128 or not 1 <= amp.shape[2] <= SYNTH_MAX_PARTIALS:
+            raise HfttError('VoiceBank: amp must be [V >= 1, 1 <= N <= 128, 1 <= H <= %d], got shape %s' % (SYNTH_MAX_PARTIALS, tuple(amp.shape)))
+        self.V, self.N, self.H = (int(n) for n in amp.shape)
+        if self.V * self.N * self.H >= 1 << 31:
+            raise HfttError('VoiceBank: V * N * H = %d entries exceed 2^31' % (self.V * self.N * self.H))
+        for name, t, shape in (('inc', inc, amp.shape), ('dec', dec, amp.shape), ('vel_gain', vel_gain, (self.V, 128)), ('rel', rel, (self.V,)),
+                               ('attack', attack, (self.V,)), ('release', release, (self.V,))):
+            if tuple(t.shape) != tuple(shape):
+                raise HfttError('VoiceBank: %s must have shape %s, got %s' % (name, tuple(shape), tuple(t.shape)))
+        for name, t in (('amp', amp), ('dec', dec), ('vel_gain', vel_gain), ('rel', rel)):
+            if not t.dtype.is_floating_point or not bool(torch.isfinite(t).all()):
+                raise HfttError('VoiceBank: %s must be finite floating point, got %s' % (name, t.dtype))
+        for name, t in (('dec', dec), ('rel', rel)):
+            if bool((t < 0).any()):
+                raise HfttError('VoiceBank: %s must not be negative' % name)
+        for name, t, lo, hi in (('inc', inc, 0, (1 << 32) - 1), ('attack', attack, 1, (1 << 31) - 1), ('release', release, 0, (1 << 31) - 1)):
+            if t.dtype.is_floating_point or t.dtype == torch.bool or int(t.min()) < lo or int(t.max()) > hi:
+                raise HfttError('VoiceBank: %s must be integers inside %d .. %d' % (name, lo, hi))
+        self.device = torch.device(device)
+        # (torch has no uint32 arithmetic: the increments travel as the int32 with the same bits)
+        inc = inc.to(torch.int64)
+        self.inc = torch.where(inc >= 1 << 31, inc - (1 << 32), inc).to(torch.int32).contiguous().to(self.device)
+        self.amp, self.dec, self.vel_gain, self.rel = (t.to(torch.float32).contiguous().to(self.device) for t in (amp, dec, vel_gain, rel))
+        self.attack, self.release = (t.to(torch.int32).contiguous().to(self.device) for t in (attack, release))
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.inc, self.amp, self.dec, self.vel_gain, self.rel, self.attack, self.release))
+
+
+def synth_span(width, hop, lead=0, n_fft=2048):
+    """the samples of a scratch row that a window of `width` frames with `lead` further frames in front can show:
+    (P + lead + width - 1) * hop + n_fft / 2, P = ceil((n_fft / 2) / hop)"""
+    return room_span(int(width) + int(lead), hop, n_fft)
+
+
+def clip_synth(table, file_nsamp, bank, voice_index, win_file, win_start, width, hop, sr, lead=0, n_fft=2048):
+    """The samples of B clip windows RENDERED in ONE launch (hftt_clip_synth): window b shows frames win_start[b] .. + width of the synthetic
+    file that the notes of file win_file[b] of `table` (a LabelsTable) make under voice voice_index[b] (int32 [B]) of `bank` (a VoiceBank);
+    file_nsamp int64 [n_files] (a device tensor) is each file's length in samples.  lead: further frames rendered in front of each window, so
+    that a room can follow (clip_room over the result as its corpus needs lead >= ceil(taps / hop)).  Returns what clip_room returns: (scratch
+    fp32 [B, span], out_samp0 int64 [2 B + 1], out_win_file int32 [B], out_win_start int32 [B]); a plain clip_logmel over WetTable(scratch,
+    out_samp0) with the two window tables gives the log-mel of the synthetic file.  A voice index outside 0 .. V - 1 makes a window without a
+    file.  Nothing is read back to the host; no CPU fallback."""
+    if not isinstance(table, LabelsTable):
+        raise HfttError('clip_synth: table must be an ops.LabelsTable')
+    if not isinstance(bank, VoiceBank):
+        raise HfttError('clip_synth: bank must be an ops.VoiceBank')
+    dev = table.device
+    if bank.device != dev:
+        raise HfttError('clip_synth: the bank lives on %s, the note table on %s' % (bank.device, dev))
+    if bank.N != table.N:
+        raise HfttError('clip_synth: the bank holds N=%d pitches, the note table N=%d' % (bank.N, table.N))
+    file_nsamp = torch.as_tensor(file_nsamp, device=dev).to(torch.int64).contiguous()
+    if file_nsamp.shape != (table.n_files,):
+        raise HfttError('clip_synth: file_nsamp must be [n_files=%d], got shape %s' % (table.n_files, tuple(file_nsamp.shape)))
+    win_file = torch.as_tensor(win_file, device=dev).to(torch.int32).contiguous()
+    win_start = torch.as_tensor(win_start, device=dev).to(torch.int32).contiguous()
+    voice_index = torch.as_tensor(voice_index, device=dev).to(torch.int32).contiguous()
+    if win_file.dim() != 1 or win_start.shape != win_file.shape or voice_index.shape != win_file.shape:
+        raise HfttError('clip_synth: win_file, win_start and voice_index must be [B]')
+    _need_cuda(table.notes, table.row_ptr, file_nsamp, win_file, win_start, voice_index, bank.inc)
+    B, width, lead = win_file.numel(), int(width), int(lead)
+    span = (synth_span(width, hop, lead, n_fft) + 3) // 4 * 4 if width >= 1 and int(hop) >= 1 and lead >= 0 else 4      # (a bad request is the library's to refuse)
+    out = torch.empty((B, span), dtype=torch.float32, device=dev)
+    samp0 = torch.empty(2 * B + 1, dtype=torch.int64, device=dev)
+    ofile, ostart = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+    d = ClipSynthDesc()
+    d.notes, d.row_ptr, d.file_nsamp = table.notes.data_ptr() if table.n_notes else None, table.row_ptr.data_ptr(), file_nsamp.data_ptr()
+    d.win_file, d.win_start, d.voice_index = win_file.data_ptr(), win_start.data_ptr(), voice_index.data_ptr()
+    d.n_files, d.n_notes, d.B, d.width, d.N = table.n_files, table.n_notes, B, width, table.N
+    d.n_fft, d.hop, d.lead, d.sr, d.V, d.H = int(n_fft), int(hop), lead, float(sr), bank.V, bank.H
+    d.inc, d.amp, d.dec, d.vel_gain, d.rel = (t.data_ptr() for t in (bank.inc, bank.amp, bank.dec, bank.vel_gain, bank.rel))
+    d.attack, d.release, d.span = bank.attack.data_ptr(), bank.release.data_ptr(), span
+    d.out, d.out_samp0, d.out_win_file, d.out_win_start = out.data_ptr(), samp0.data_ptr(), ofile.data_ptr(), ostart.data_ptr()
+    check(lib().hftt_clip_synth(C.byref(d), _stream(dev)), 'clip_synth')
+    return out, samp0, ofile, ostart

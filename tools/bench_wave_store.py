@@ -23,16 +23,23 @@ leg the others are read against.  Measured, no threshold.
 
 The room leg (reverb: hftt_clip_room + the plain hftt_clip_logmel on its scratch): WaveClipStore.batch without augmentation and with room_p = 1
 (every clip wet, a bank of 32 responses from corpus.synth_audio.synth_room_bank with its own lengths), interleaved as above, and the launches
-alone under draws made beforehand: hftt_clip_room, the clip log-mel on the source corpus and on the scratch."""
+alone under draws made beforehand: hftt_clip_room, the clip log-mel on the source corpus and on the scratch.
+
+  python tools/bench_wave_store.py --synth-out profiles/clip_synth.json [--synth-voices 64] [--synth-partials 16] [--step-ms 27.65]
+
+The synth leg (modal synthesis: hftt_clip_synth + the plain hftt_clip_logmel on its scratch): SynthClipStore.batch (the notes alone resident, a
+bank of plucked-string voices from corpus.synth_audio.synth_voice_bank, a voice drawn per clip) against WaveClipStore.batch on the same
+clip ids of the same corpus, interleaved as above, the launches alone under draws made beforehand (hftt_clip_synth with lead 0 and with the
+lead a 4,096-tap room needs), and the bytes both stores keep in HBM."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'nylon-amt_amd'))
 import numpy as np
 import torch
 from corpus import synth_audio as SA
-from corpus.make_dataset import assemble_note_store, assemble_wave_store, finalize_config, prepare_config
+from corpus.make_dataset import assemble_note_store, assemble_synth_store, assemble_wave_store, finalize_config, prepare_config
 from hftt_hip import ops
-from training.dataset import NoteClipStore, WaveAugment, WaveClipStore
+from training.dataset import NoteClipStore, SynthClipStore, WaveAugment, WaveClipStore
 
 
 def timed(fn):
@@ -155,6 +162,77 @@ def room_leg(wstore, config, dev, chunks, repeats=5, calls=60, warmup=10, taps=4
     return out
 
 
+def synth_leg(wstore, notes, config, dev, batch, repeats=5, calls=60, warmup=10, voices=64, partials=16):
+    """{leg: {'ms': median over the repeats, 'repeats': [...]}} for the wave store and the synth store on the same clip ids, interleaved inside
+    every repeat (the order rotates); 'calls': the launches alone; and what both stores keep resident"""
+    bank_host = SA.synth_voice_bank(voices, config, seed=1, partials=partials)
+    bank = ops.VoiceBank(device=dev, **bank_host)
+    sstore = assemble_synth_store(notes, config, release_samples=int(bank_host['release'].max()))
+    legs = {'wave_store': WaveClipStore(wstore, config, dev, wave_dtype='int16'), 'synth_store': SynthClipStore(sstore, config, dev, bank, seed=1)}
+    # The two clip lists differ: a synthetic file ends `release` behind its last offset, the recorded minute runs on.  The timed batches are
+    # drawn from the clips BOTH stores hold -- (file, frame) with frame below both files' counts -- as ids of either store, checked on the host.
+    nf_w, nf_s = np.bincount(wstore['clip_file']), np.bincount(sstore['clip_file'])
+    first_w, first_s = np.concatenate([[0], np.cumsum(nf_w)[:-1]]), np.concatenate([[0], np.cumsum(nf_s)[:-1]])
+    file = np.repeat(np.arange(len(nf_w)), np.minimum(nf_w, nf_s))
+    frame = np.concatenate([np.arange(n) for n in np.minimum(nf_w, nf_s)])
+    id_w, id_s = first_w[file] + frame, first_s[file] + frame
+    assert id_w.max() < len(wstore['clip_file']) and id_s.max() < len(sstore['clip_file'])
+    assert np.array_equal(wstore['clip_file'][id_w], sstore['clip_file'][id_s]) and np.array_equal(wstore['clip_frame'][id_w], sstore['clip_frame'][id_s])
+    order = torch.randperm(len(file), generator=torch.Generator().manual_seed(1)).numpy()
+    chunks = [order[i:i + batch] for i in range(0, len(order) - batch + 1, batch)][:warmup + calls]
+    ids = {'wave_store': lambda c: torch.from_numpy(id_w[c]).to(dev), 'synth_store': lambda c: torch.from_numpy(id_s[c]).to(dev)}
+    names = list(legs)
+    assert len(chunks) >= warmup + calls, 'corpus too small for %d calls' % (warmup + calls)
+    store = legs['synth_store']
+    c = ids['synth_store'](chunks[0])
+    file, start = store.clip_file[c], store.clip_frame[c] - store.mb
+    assert torch.equal(file, legs['wave_store'].clip_file[ids['wave_store'](chunks[0])])
+    width, hop = store.mb + store.T + store.mf, store.logmel.hop
+    voice = store.draw_voice(len(c))
+    lead = -(-4096 // hop)
+    out0, samp0, ofile, ostart = ops.clip_synth(store.table, store.file_nsamp, bank, voice, file, start, width, hop, store.sr)
+    scratch = ops.WetTable(out0, samp0)
+    fns = {'clip_synth': lambda: ops.clip_synth(store.table, store.file_nsamp, bank, voice, file, start, width, hop, store.sr),
+           'clip_synth_lead_%d' % lead: lambda: ops.clip_synth(store.table, store.file_nsamp, bank, voice, file, start, width, hop, store.sr, lead=lead),
+           'clip_logmel_on_scratch': lambda: ops.clip_logmel(scratch, store.logmel, ofile, ostart, width, store.fill),
+           'labels_render': lambda: ops.labels_render(store.table, file, store.clip_frame[c], store.T)}
+    per, per_fn = {n: [] for n in names}, {n: [] for n in fns}
+    for r in range(repeats):
+        t, tf = {n: [] for n in names}, {n: [] for n in fns}
+        for i, ch in enumerate(chunks[:warmup + calls]):
+            for n in names[r % len(names):] + names[:r % len(names)]:
+                ms, _ = timed(lambda: legs[n].batch(ids[n](ch)))
+                if i >= warmup:
+                    t[n].append(ms)
+            for n, fn in fns.items():
+                ms, _ = timed(fn)
+                if i >= warmup:
+                    tf[n].append(ms)
+        for n in names:
+            per[n].append(float(np.median(t[n])))
+        for n in fns:
+            per_fn[n].append(float(np.median(tf[n])))
+    out = {n: {'ms': float(np.median(v)), 'repeats': v} for n, v in per.items()}
+    out['synth_store']['extra_ms_over_wave_store'] = out['synth_store']['ms'] - out['wave_store']['ms']
+    out['calls'] = {n: {'ms': float(np.median(v)), 'repeats': v} for n, v in per_fn.items()}
+    # the polyphony of the timed call: records that sound, averaged over the samples its rows hold
+    tab, sr = sstore['table'], float(config['feature']['sr'])
+    lens = np.diff(samp0.cpu().numpy())[::2]
+    o = (np.maximum(0, start.cpu().numpy().astype(np.int64) - -(-1024 // hop)) * hop)
+    sounding = 0.0
+    for b in range(len(c)):
+        f, v = int(file[b]), int(voice[b])
+        rows = tab['notes'][tab['row_ptr'][f * tab['N']]:tab['row_ptr'][(f + 1) * tab['N']]]
+        on = (rows['onset_sec'] * sr + 0.5).astype(np.int64)
+        end = np.maximum((rows['offset_sec'] * sr + 0.5).astype(np.int64), on + 1) + int(bank_host['release'][v])
+        sounding += float(np.clip(np.minimum(end, o[b] + lens[b]) - np.maximum(on, o[b]), 0, None).sum())
+    out['timed_call'] = {'samples': int(lens.sum()), 'mean_sounding_records_per_sample': sounding / max(int(lens.sum()), 1), 'partials': partials,
+                         'voices': voices, 'scratch_bytes': out0.numel() * 4}
+    out['resident_bytes'] = {'wave_store': int(legs['wave_store'].resident_bytes()), 'synth_store': int(store.resident_bytes()), 'voice_bank': int(bank.nbytes()),
+                             'note_table': int(store.table.nbytes())}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--files', type=int, default=2, help='synthetic one-minute files')
@@ -168,11 +246,34 @@ def main():
     ap.add_argument('--mix-calls', type=int, default=60)
     ap.add_argument('--room-out', default='', help='run the room leg alone and write it here')
     ap.add_argument('--room-taps', type=int, default=4096)
+    ap.add_argument('--synth-out', default='', help='run the synth leg alone and write it here')
+    ap.add_argument('--synth-voices', type=int, default=64)
+    ap.add_argument('--synth-partials', type=int, default=16)
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     config = finalize_config(prepare_config(SA.default_config()))
     notes = [SA.pluck_notes(2000 + i) for i in range(args.files)]
     waves = [SA.pluck_wave(a, device=dev) for a in notes]
+    if args.synth_out:
+        wstore = assemble_wave_store([w.cpu().numpy() for w in waves], notes, config)
+        n = len(wstore['clip_file'])
+        ids = torch.randperm(n, generator=torch.Generator().manual_seed(1))
+        chunks = [ids[i:i + args.batch].to(dev) for i in range(0, n - args.batch + 1, args.batch)]
+        cin = config['input']
+        res = {'what': 'SynthClipStore.batch (notes alone resident, the audio rendered by hftt_clip_synth) against WaveClipStore.batch (int16 waveforms resident) on the same clip ids, and the launches alone: device events around each call; per repeat the median of the calls, reported the median of the repeats',
+               'device': torch.cuda.get_device_name(0), 'files': args.files, 'clips': n, 'batch': args.batch, 'window_frames': cin['margin_b'] + cin['num_frame'] + cin['margin_f'],
+               'mel_bins': config['feature']['mel_bins'], 'repeats': args.mix_repeats, 'calls': args.mix_calls, 'warmup': 10,
+               'legs': synth_leg(wstore, notes, config, dev, args.batch, args.mix_repeats, args.mix_calls, 10, args.synth_voices, args.synth_partials)}
+        if args.step_ms > 0.0:
+            res['benchmark_step_ms_median'] = args.step_ms
+            res['clip_synth_share_of_step'] = res['legs']['calls']['clip_synth']['ms'] / args.step_ms
+            res['synth_extra_share_of_step'] = res['legs']['synth_store']['extra_ms_over_wave_store'] / args.step_ms
+        os.makedirs(os.path.dirname(os.path.abspath(args.synth_out)), exist_ok=True)
+        with open(args.synth_out, 'w') as fh:
+            json.dump(res, fh, indent=1)
+            fh.write('\n')
+        print(json.dumps(res))
+        return
     if args.room_out:
         wstore = assemble_wave_store([w.cpu().numpy() for w in waves], notes, config)
         n = len(wstore['clip_file'])

@@ -16,6 +16,10 @@ response of a synthetic or supplied bank, the labels unchanged).  Training: the 
 (hftt_hip.trainer.TrainStep: forward + fused loss + backward + fused Adam) in the chosen precision mode, dropout 0.1, batch 8, until the
 time budget is spent.  The model is pickled the way m_training.py:372-373 does it (whole module, protocol 4).
 
+With --synth-store [--synth-voices V] [--synth-partials H] [--synth-seed S] the corpus keeps the NOTES alone: every batch's audio is rendered on
+the device under a plucked-string voice drawn per clip (assemble_synth_store, SynthClipStore, corpus.synth_audio.synth_voice_bank); the gain,
+noise and room options apply, warp and mix do not.
+
 Scoring (config 5): the seed-1234 minute -> log-mel -> 30 clips through AMT.transcript -> mpe2note -> note-F1 (onset, 50 ms) and frame-F1
 against the GENERATING notes, in x3, bf16 and parity mode, plus the frame-level agreement of the modes with each other.  One JSON line."""
 import argparse, json, math, os, pickle, sys, tempfile, time
@@ -26,8 +30,8 @@ import torch
 import bench
 from corpus import synth_audio as SA
 from corpus.conv_note2label import note2label_arrays
-from corpus.make_dataset import assemble_note_store, assemble_store, assemble_wave_store
-from training.dataset import MyDataset, DeviceClipStore, NoteClipStore, WaveAugment, WaveClipStore
+from corpus.make_dataset import assemble_note_store, assemble_store, assemble_synth_store, assemble_wave_store
+from training.dataset import MyDataset, DeviceClipStore, NoteClipStore, SynthClipStore, WaveAugment, WaveClipStore
 from model.amt import AMT
 from hftt_hip import ops
 from evaluation.metrics import note_metrics, frame_metrics
@@ -35,11 +39,20 @@ from evaluation.metrics import note_metrics, frame_metrics
 ROOM_BANK_SIZE = 32          # responses of the synthetic room bank (--aug-room-p without --aug-room-bank)
 
 
-def build_corpus(config, files, dev, n_slice=8, note_store=False, wave_store=False, augment=None):
+def build_corpus(config, files, dev, n_slice=8, note_store=False, wave_store=False, augment=None, synth=None):
     """`files` one-minute plucked-string files (seeds 2000..) -> HIP log-mel -> reference-recipe labels -> one MAESTRO-format store in HBM;
     note_store: features + note table in HBM instead, labels rendered per batch (a file is then as long as its label track, not cut to its
-    feature array); wave_store: waveforms (int16) + note table in HBM, no feature pass, `augment` a WaveAugment or None"""
+    feature array); wave_store: waveforms (int16) + note table in HBM, no feature pass, `augment` a WaveAugment or None;
+    synth = (voices, partials, seed): the NOTES alone in HBM and a bank of that many plucked-string voices, every batch's audio rendered on the
+    device (no waveform is made here at all)"""
     t0 = time.time()
+    if synth is not None:
+        note_lists = [SA.pluck_notes(2000 + i) for i in range(files)]
+        voices = SA.synth_voice_bank(synth[0], config, seed=synth[2], partials=synth[1])
+        store = assemble_synth_store(note_lists, config, release_samples=int(voices['release'].max()))
+        clips = SynthClipStore(store, config, dev, ops.VoiceBank(device=dev, **voices), n_slice, seed=synth[2], augment=augment)
+        return clips, {'files': files, 'samples': int(store['file_nsamp'].sum()), 'clips': len(clips), 'notes': clips.table.n_notes, 'voices': synth[0],
+                       'partials': synth[1], 'resident_bytes': clips.resident_bytes(), 'seconds_to_build': round(time.time() - t0, 1)}
     if wave_store:
         note_lists = [SA.pluck_notes(2000 + i) for i in range(files)]
         store = assemble_wave_store([SA.pluck_wave(notes, device=dev).cpu().numpy() for notes in note_lists], note_lists, config)
@@ -198,6 +211,10 @@ def main():
     ap.add_argument('--save-state-at', default='')
     ap.add_argument('--note-store', action='store_true', help='keep notes instead of label tracks in HBM and render every batch\'s labels on the device (NoteClipStore)')
     ap.add_argument('--wave-store', action='store_true', help='keep int16 waveforms and notes in HBM and compute every batch\'s log-mel windows and labels on the device (WaveClipStore)')
+    ap.add_argument('--synth-store', action='store_true', help='keep the NOTES alone in HBM and render every batch\'s audio from them on the device under a voice per clip (SynthClipStore); gain, noise and room augmentation apply')
+    ap.add_argument('--synth-voices', type=int, default=None, metavar='V', help='with --synth-store: voices of the plucked-string bank (default 64)')
+    ap.add_argument('--synth-partials', type=int, default=None, metavar='H', help='with --synth-store: partials per voice (default 16, at most 32)')
+    ap.add_argument('--synth-seed', type=int, default=None, metavar='S', help='with --synth-store: seed of the bank and of the voice draws (default: --seed)')
     ap.add_argument('--aug-gain-db', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --wave-store: per-clip gain, uniform in dB, new for every batch')
     ap.add_argument('--aug-noise-dbfs', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --wave-store: per-clip additive noise level, uniform in dB re full scale')
     ap.add_argument('--aug-pitch', type=int, nargs=2, metavar=('LO', 'HI'), default=None,
@@ -222,15 +239,22 @@ def main():
     ap.add_argument('--lr-time', type=float, default=None, help='learning rate of the time decoder and heads B (default: --lr)')
     ap.add_argument('--no-decay-1d', action='store_true', help='with --weight-decay: none on biases and LayerNorm parameters')
     args = ap.parse_args()
+    if args.synth_store and (args.wave_store or args.note_store):
+        ap.error('--synth-store, --wave-store and --note-store are exclusive: each names what the corpus keeps in HBM')
+    if not args.synth_store and any(x is not None for x in (args.synth_voices, args.synth_partials, args.synth_seed)):
+        ap.error('--synth-voices / --synth-partials / --synth-seed describe the voice bank: they need --synth-store')
+    waveform = args.wave_store or args.synth_store          # the stores with a waveform to augment
     warp_aug = args.aug_pitch is not None or args.aug_detune_cents != 0.0 or args.aug_shift or args.aug_warp_p != 1.0
+    mix_aug = args.aug_mix_p != 0.0 or args.aug_mix_gain_db is not None
+    if (warp_aug or mix_aug) and args.synth_store:
+        ap.error('--synth-store takes gain, noise and room: an augment that warps or mixes is not built there (pitch and polyphony are the note list\'s)')
     if warp_aug and not args.wave_store:
         ap.error('--aug-pitch / --aug-detune-cents / --aug-shift / --aug-warp-p act on the waveform: they need --wave-store')
-    mix_aug = args.aug_mix_p != 0.0 or args.aug_mix_gain_db is not None
     if mix_aug and not args.wave_store:
         ap.error('--aug-mix-p / --aug-mix-gain-db act on the waveform: they need --wave-store')
     room_synth = args.aug_room_rt60 is not None or args.aug_room_drr_db is not None or args.aug_room_taps is not None
     room_aug = args.aug_room_p != 0.0 or room_synth or bool(args.aug_room_bank)
-    if room_aug and not args.wave_store:
+    if room_aug and not waveform:
         ap.error('--aug-room-p / --aug-room-rt60 / --aug-room-drr-db / --aug-room-taps / --aug-room-bank act on the waveform: they need --wave-store')
     if room_synth and args.aug_room_bank:
         ap.error('--aug-room-bank supplies the responses: --aug-room-rt60 / --aug-room-drr-db / --aug-room-taps describe the synthetic bank')
@@ -255,7 +279,7 @@ def main():
             with open(args.init, 'rb') as fh:
                 model.load_state_dict(pickle.load(fh).state_dict())
             log['init'] = args.init
-        if (args.aug_gain_db or args.aug_noise_dbfs) and not args.wave_store:
+        if (args.aug_gain_db or args.aug_noise_dbfs) and not waveform:
             ap.error('--aug-gain-db / --aug-noise-dbfs act on the waveform: they need --wave-store')
         augment = None
         if args.aug_gain_db or args.aug_noise_dbfs or warp_aug or mix_aug or room_aug:
@@ -271,8 +295,9 @@ def main():
             augment = WaveAugment(gain_db=args.aug_gain_db, noise_dbfs=args.aug_noise_dbfs, seed=args.seed, pitch_semitones=args.aug_pitch,
                                   detune_cents=args.aug_detune_cents, shift=args.aug_shift, p_warp=args.aug_warp_p, mix_p=args.aug_mix_p,
                                   mix_gain_db=args.aug_mix_gain_db or (-6.0, 0.0), room_p=args.aug_room_p, room_bank=bank)
-        clips, log['corpus'] = build_corpus(config, args.files, dev, note_store=args.note_store, wave_store=args.wave_store, augment=augment)
-        if args.wave_store:
+        clips, log['corpus'] = build_corpus(config, args.files, dev, note_store=args.note_store, wave_store=args.wave_store, augment=augment,
+                                           synth=(args.synth_voices or 64, args.synth_partials or 16, args.seed if args.synth_seed is None else args.synth_seed) if args.synth_store else None)
+        if waveform:
             log['augment'] = {'gain_db': args.aug_gain_db, 'noise_dbfs': args.aug_noise_dbfs, 'pitch_semitones': args.aug_pitch,
                               'detune_cents': args.aug_detune_cents, 'shift': args.aug_shift, 'p_warp': args.aug_warp_p,
                               'mix_p': args.aug_mix_p, 'mix_gain_db': args.aug_mix_gain_db, 'room_p': args.aug_room_p,
