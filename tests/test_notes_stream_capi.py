@@ -94,8 +94,11 @@ def test_rejects_a_state_one_byte_short_and_a_null_descriptor(lib):
     assert lib.hftt_notes_stream_step(C.byref(d), None) not in (0, 2, 3)
     assert b'state_bytes=%d below' % (need - 1) in lib.hftt_last_error(), lib.hftt_last_error()
     assert lib.hftt_notes_stream_step(None, None) != 0 and b'null descriptor' in lib.hftt_last_error()
-    d = _desc(lib, cap=0, out_pitch=None, out_onset=None)                    # no room asked for: no arrays needed; refused later, by the guard
-    assert lib.hftt_notes_stream_step(C.byref(d), None) != 1 or b'null output' not in lib.hftt_last_error()
+    # no room asked for: no arrays needed.  The state is validated after the output-array rule, so a null state makes this a host-side
+    # rejection whose text shows that the rule let cap = 0 through: nothing launches on the fake pointers, with or without a device
+    d = _desc(lib, cap=0, out_pitch=None, out_onset=None, state=None)
+    assert lib.hftt_notes_stream_step(C.byref(d), None) not in (0, 2, 3)
+    assert b'state is null' in lib.hftt_last_error() and b'null output' not in lib.hftt_last_error(), lib.hftt_last_error()
 
 
 def test_state_bytes_is_per_stream_and_pitch_not_per_row(lib):
