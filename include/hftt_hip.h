@@ -1057,6 +1057,67 @@ typedef struct {
 int hftt_clip_synth(const hftt_clip_synth_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Clip synth, played (csrc/clip_synth_parts.hip): hftt_clip_synth under a per-window PERFORMANCE -- transposition, a time map (tempo and
+ * delay), a tuning offset -- and with a SECOND PART, another file's notes under its own voice and its own performance, summed onto the first:
+ * every key, tempo, tuning and pairing of a note corpus at no resident cost.  The label side is hftt_labels_render_warp / _mix, which take the
+ * same per-window shift, t_delay, t_scale and partner tables.  One entry point ADDED at ABI 8; HFTT_ABI_VERSION stays 8, every descriptor
+ * above keeps its layout, and hftt_clip_synth (its file, its kernel, its results) is untouched: the kernel here is a second copy of its walk,
+ * held to it by the identity equality below.
+ *
+ * It is the hftt_clip_synth contract -- `base` with every field as there, except that base.file_nsamp is NOT read (it may be NULL) -- with
+ * nsamp int64 [B], the length n'_A of window b's synthetic file under its map (negative: 0), and four changes per part.  A part's play is an
+ * hftt_synth_play_args: shift / t_delay / t_scale [B], all three set or all three NULL (the rule of hftt_labels_render_mix; NULL: 0, 0, 1),
+ * and tune_q31 uint32 [B] or NULL (NULL: 2^31).
+ *   Time map.  Every note time t of the part becomes t' = fmul(fadd(t, t_delay[b]), t_scale[b]) -- fp64, two roundings, never an fma: the
+ *     expression of hftt_labels_render_warp, so audio and labels are formed from the same bits of t' -- and then n_on = (int64)(t'_on * sr +
+ *     0.5), n_off likewise, D = max(n_off - n_on, 1).  t_delay = 0, t_scale = 1 gives the unmapped bits.  Decay rates, attack and release stay
+ *     per sample: a string does not know the tempo.
+ *   Transposition.  A record of table pitch p sounds with bank row p + shift[b]; a row outside 0 .. N - 1 contributes no operation (the labels
+ *     give an all-zero column there).
+ *   Tuning.  inc' = (uint32)(((uint64)inc[v, p + shift, h] * tune_q31[b]) >> 31): exact integer arithmetic, 2^31 = unison leaves inc
+ *     unchanged; the phase is u = (float)(int32)(inc' * (uint32)tau) * 2^-32 as before.  The product is NOT checked against Nyquist: the
+ *     host leaves the headroom when it fills the bank.
+ *   The second part.  part_file / part_start / part_voice int32 [B] and part_gain fp32 [B], all four set or all four NULL, with part_nsamp
+ *     int64 [B] (n'_B, the partner file's length under ITS map; given exactly when the partner tables are) and part_play.  The sample at
+ *     primary position i, 0 <= i < n'_A, is acc = +0, then the primary's records in table order exactly as in hftt_clip_synth, and then,
+ *     CARRYING THE SAME ACCUMULATOR, the partner's records in table order at partner position iB = i + (part_start[b] - win_start[b]) * hop
+ *     (int64): a partner record sounds when 0 <= iB < n'_B and 0 <= tau_B = iB - n_on_B < D_B + release[vB], with
+ *         c = (((amp * vel_gain[vB, velocity]) * part_gain[b]) * ra) * E(-x)
+ *     -- one further rounding, formed once per (record, partial) -- and everything of the voice (vel_gain, rel, attack, release, the bank
+ *     rows) the partner's vB = part_voice[b].  A part_file outside 0 .. n_files - 1 or a part_voice outside 0 .. V - 1 contributes nothing:
+ *     such a window is bit-identical to one without partner tables.  Outside [0, n'_A) nothing is rendered: the partner is added ONTO the
+ *     primary's extent, as in hftt_clip_logmel_mix.
+ * Pseudo-files, the three output tables, lead, span, invalid windows and the never-written remainder of a row are hftt_clip_synth's with
+ * n' = nsamp[b].  The value depends on (files, voices, plays, gain, part_start - win_start, i) only -- not on tile origin, lead or geometry:
+ * overlapping windows with equal draws see the same bits.  With every group NULL, or with identity values (shift 0, t_delay 0, t_scale 1,
+ * tune 2^31, part_file -1) and nsamp[b] = file_nsamp[win_file[b]], all four outputs equal hftt_clip_synth's bit for bit.
+ *
+ * One launch of hftt_clip_synth's shape (a workgroup per window and tile of 2,048 samples, eight samples per thread): one device function
+ * filters a part's records against the tile -- for the partner the tile in partner coordinates, cut to [0, n'_B) -- and walks the survivors;
+ * it runs for the primary and, under a branch uniform over the workgroup, for the partner on the same registers, re-using the survivor list
+ * and re-staging the partner file's row pointers.  The tuning product is scalar arithmetic.  One writer per element, no atomics, no workspace.
+ * Refused in front of the launch: everything hftt_clip_synth refuses except a null base.file_nsamp; null nsamp; a play or part_play map of
+ * which only a part is given; partner tables of which only a part is given; part_nsamp or part_play given without partner tables; part_nsamp
+ * missing with partner tables.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {                                                 /* how one part is played; [B] each */
+  const int32_t* shift;                                          /* semitones           } all three set, or all three NULL */
+  const double*  t_delay;                                        /* seconds             }   (the rule of hftt_labels_render_mix) */
+  const double*  t_scale;                                        /*                     } */
+  const uint32_t* tune_q31;                                      /* or NULL: 2^31 = unison */
+} hftt_synth_play_args;
+typedef struct {
+  hftt_clip_synth_desc base;                                     /* everything as in hftt_clip_synth; base.file_nsamp is NOT read */
+  const int64_t* nsamp;                                          /* [B] n'_A: length of window b's synthetic file under its map (negative: 0) */
+  hftt_synth_play_args play;                                     /* the primaries' */
+  const int32_t* part_file; const int32_t* part_start; const int32_t* part_voice;        /* [B], all four set or all four NULL */
+  const float*   part_gain;
+  const int64_t* part_nsamp;                                     /* [B] n'_B; given exactly when the partner tables are */
+  hftt_synth_play_args part_play;                                /* the partners' */
+} hftt_clip_synth_parts_desc;
+int hftt_clip_synth_parts(const hftt_clip_synth_parts_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Guarded optimizer step (csrc/guard.hip): global-norm gradient clipping, a non-finite guard and decoupled weight decay around the fused
  * Adam.  Like the note decoder and the label renderer these entry points were ADDED at ABI 8 and HFTT_ABI_VERSION stays 8: nothing that an
  * ABI-8 caller binds changed (hftt_adam_step above is untouched and remains the default step); a caller that needs them looks the symbols up.

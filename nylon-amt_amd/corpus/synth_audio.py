@@ -109,7 +109,7 @@ def _inc_q32(freq, sr):
 
 def synth_voice_bank(n, config, seed, partials=16, inharmonicity=(1e-5, 4e-4), detune_cents=6.0, pluck_pos=(0.08, 0.45), rolloff=(0.6, 1.6),
                      t60=(0.8, 4.0), pitch_damping=(0.3, 0.8), partial_damping=(0.02, 0.4), release_t60=(0.03, 0.25), attack_ms=(0.3, 4.0),
-                     level=(0.03, 0.12), velocity_exponent=(0.7, 1.8)):
+                     level=(0.03, 0.12), velocity_exponent=(0.7, 1.8), headroom_cents=0.0):
     """n voices of a plucked-string family for hftt_hip.ops.VoiceBank -> dict(inc uint32 [n, N, H], amp, dec fp32 [n, N, H], vel_gain fp32
     [n, 128], rel fp32 [n], attack, release int32 [n]); N = config.midi.num_note pitches from note_min, H = partials, sr = config.feature.sr.
     Everything is drawn and formed in fp64 and rounded once.  Per voice, each quantity uniform in its range (log-uniform where it spans decades):
@@ -121,13 +121,18 @@ def synth_voice_bank(n, config, seed, partials=16, inharmonicity=(1e-5, 4e-4), d
         decay      sigma_k = (sigma0 + sigma1 k^2) (f0 / 261.6 Hz)^gamma per second, sigma0 = 3 ln 10 / t60 (the fundamental of middle C is 60 dB
             down after t60 seconds), sigma1 = partial_damping sigma0; as log2 units per sample: sigma_k log2(e) / sr
         release    behind the offset the note falls by a further 60 dB in release_t60 seconds and is cut there; attack: a linear ramp of
-            attack_ms; velocity curve (velocity / 127)^e with e in velocity_exponent"""
+            attack_ms; velocity curve (velocity / 127)^e with e in velocity_exponent
+    headroom_cents: a partial within that margin below Nyquist is off too, so that a clip may be tuned up by as much (training.dataset.SynthPlay's
+    tune_cents) without a partial folding over: the kernel does not check the tuned increment."""
     sr = float(config['feature']['sr'])
     H = int(partials)
     if n < 1 or H < 1:
         raise ValueError('synth_voice_bank: n=%r and partials=%r must be positive' % (n, partials))
     if not 0.0 <= float(detune_cents) < 50.0:
         raise ValueError('synth_voice_bank: detune_cents=%r outside 0 .. 50' % (detune_cents,))
+    if not 0.0 <= float(headroom_cents) <= 1200.0:
+        raise ValueError('synth_voice_bank: headroom_cents=%r outside 0 .. 1200' % (headroom_cents,))
+    margin = float(np.power(2.0, float(headroom_cents) / 1200.0))
     rng = np.random.RandomState(seed)
     f0 = _pitch_hz(config)
     N = len(f0)
@@ -144,6 +149,8 @@ def synth_voice_bank(n, config, seed, partials=16, inharmonicity=(1e-5, 4e-4), d
         cents = rng.uniform(-detune_cents, detune_cents, H)
         freq = k[None, :] * f0[:, None] * np.sqrt(1.0 + B * k[None, :] ** 2) * np.power(2.0, cents[None, :] / 1200.0)
         inc, below = _inc_q32(freq, sr)
+        below = below & (freq * margin < 0.5 * sr)
+        inc = np.where(below, inc, 0).astype(np.uint32)
         a = np.abs(np.sin(k * np.pi * beta)) / np.power(k, rho)
         a = np.where(below, a[None, :], 0.0)
         a = lev * a / np.maximum(a.max(axis=1, keepdims=True), 1e-300)
@@ -170,13 +177,23 @@ def pluck_voice(config):
             'attack': np.ones(1, np.int32), 'release': np.full(1, int(round(0.3 * sr)), np.int32)}
 
 
-def render_file(table, bank, file, voice, nsamp, hop=256, n_fft=2048):
+def render_file(table, bank, file, voice, nsamp, hop=256, n_fft=2048, play=None, tune=None, part=None, file_nsamp=None):
     """the whole synthetic file `file` of `table` (an ops.LabelsTable) under voice `voice` of `bank` (an ops.VoiceBank), nsamp samples long ->
-    fp32 [nsamp] on the table's device: hftt_clip_synth with ONE window that covers the file, for listening and for the tests"""
+    fp32 [nsamp] on the table's device: hftt_clip_synth with ONE window that covers the file, for listening and for the tests.
+    play (an ops.Warp of one window), tune (one Q31 factor) and part (an ops.SynthPart of one window) play it as ops.clip_synth does
+    (hftt_clip_synth_parts); nsamp is then the PLAYED file's length, and file_nsamp int64 [n_files] gives the partner file's."""
     from hftt_hip import ops
     nsamp = int(nsamp)
     width = max(1, -(-(nsamp - n_fft // 2) // hop) + 1)                         # (width - 1) hop + n_fft / 2 >= nsamp
-    file_nsamp = torch.zeros(table.n_files, dtype=torch.int64)
-    file_nsamp[file] = nsamp
-    out, samp0, _, _ = ops.clip_synth(table, file_nsamp.to(table.device), bank, [voice], [file], [0], width, hop, table.sr, n_fft=n_fft)
+    if play is None and tune is None and part is None:
+        file_nsamp = torch.zeros(table.n_files, dtype=torch.int64)
+        file_nsamp[file] = nsamp
+        out, samp0, _, _ = ops.clip_synth(table, file_nsamp.to(table.device), bank, [voice], [file], [0], width, hop, table.sr, n_fft=n_fft)
+        return out[0, :nsamp]
+    if file_nsamp is None:
+        if part is not None:
+            raise ValueError('render_file: a part needs file_nsamp (the partner file\'s length)')
+        file_nsamp = torch.zeros(table.n_files, dtype=torch.int64)
+    out, samp0, _, _ = ops.clip_synth(table, torch.as_tensor(file_nsamp).to(table.device), bank, [voice], [file], [0], width, hop, table.sr, n_fft=n_fft,
+                                      play=play, tune=None if tune is None else [int(tune)], part=part, nsamp=[nsamp])
     return out[0, :nsamp]

@@ -304,6 +304,16 @@ class ClipSynthDesc(C.Structure):           # hftt_clip_synth_desc: the windows 
                 ('out', C.c_void_p), ('out_samp0', C.c_void_p), ('out_win_file', C.c_void_p), ('out_win_start', C.c_void_p)]
 
 
+class SynthPlayArgs(C.Structure):           # hftt_synth_play_args: how one part is played (transposition, time map, tuning), [B] each
+    _fields_ = [('shift', C.c_void_p), ('t_delay', C.c_void_p), ('t_scale', C.c_void_p), ('tune_q31', C.c_void_p)]
+
+
+class ClipSynthPartsDesc(C.Structure):      # hftt_clip_synth_parts_desc: clip synth under a per-window play, with a second part summed on
+    _fields_ = [('base', ClipSynthDesc), ('nsamp', C.c_void_p), ('play', SynthPlayArgs),
+                ('part_file', C.c_void_p), ('part_start', C.c_void_p), ('part_voice', C.c_void_p), ('part_gain', c_f32p),
+                ('part_nsamp', C.c_void_p), ('part_play', SynthPlayArgs)]
+
+
 ADAM_MAX_GROUPS = 8                         # HFTT_ADAM_MAX_GROUPS
 
 
@@ -383,6 +393,7 @@ SIGNATURES = {
     'hftt_labels_render_mix': (C.c_int, [C.POINTER(LabelsMixDesc), C.c_void_p]),
     'hftt_clip_room': (C.c_int, [C.POINTER(ClipRoomDesc), C.c_void_p]),
     'hftt_clip_synth': (C.c_int, [C.POINTER(ClipSynthDesc), C.c_void_p]),
+    'hftt_clip_synth_parts': (C.c_int, [C.POINTER(ClipSynthPartsDesc), C.c_void_p]),
     'hftt_grad_norm_ws_bytes': (C.c_int64, [C.c_int64]),
     'hftt_grad_norm': (C.c_int, [c_f32p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hftt_adam_step_guarded': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32,

@@ -10,7 +10,7 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipRoomDesc, ClipSynthDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
+from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipRoomDesc, ClipSynthDesc, ClipSynthPartsDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
                     WARP_DELAY_MAX, WARP_STEP_MAX, WARP_STEP_MIN, WARP_TABLE_L, WARP_TABLE_LEN, WARP_ZEROS,
                     LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, ROOM_MAX_TAPS, STITCH_MAX_CLIPS, SYNTH_MAX_PARTIALS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
@@ -1533,14 +1533,105 @@ def synth_span(width, hop, lead=0, n_fft=2048):
     return room_span(int(width) + int(lead), hop, n_fft)
 
 
-def clip_synth(table, file_nsamp, bank, voice_index, win_file, win_start, width, hop, sr, lead=0, n_fft=2048):
+class SynthPart:
+    """The SECOND PARTS of B windows of clip_synth as device tensors, in the manner of Mix: file int32 [B] (an index outside 0 .. n_files: the
+    window has no partner), start int32 [B] (the partner frame that column 0 shows, counted in the partner's own -- mapped -- file), voice int32
+    [B] (the partner's voice of the bank; outside 0 .. V - 1: no partner), gain fp32 [B], play: the partners' own ops.Warp or None (as
+    written), tune: the partners' tuning, uint32-valued [B] in Q31 (2^31 = unison), or None."""
+
+    def __init__(self, file, start, voice, gain, play=None, tune=None):
+        if play is not None and not isinstance(play, Warp):
+            raise HfttError('SynthPart: play must be an ops.Warp')
+        self.file = torch.as_tensor(file).to(torch.int32).contiguous()
+        dev = self.file.device
+        self.start = torch.as_tensor(start, device=dev).to(torch.int32).contiguous()
+        self.voice = torch.as_tensor(voice, device=dev).to(torch.int32).contiguous()
+        self.gain = torch.as_tensor(gain, device=dev).to(torch.float32).contiguous()
+        self.play = play
+        self.tune = None if tune is None else _tune_bits(tune, dev)
+        shapes = [t.shape for t in (self.start, self.voice, self.gain)] + ([] if self.tune is None else [self.tune.shape])
+        if self.file.dim() != 1 or any(sh != self.file.shape for sh in shapes):
+            raise HfttError('SynthPart: file, start, voice, gain and tune must be [B], got shapes %s' % ([tuple(self.file.shape)] + [tuple(sh) for sh in shapes],))
+        if play is not None and (play.step_q24.shape != self.file.shape or play.step_q24.device != dev):
+            raise HfttError('SynthPart: the play holds %d windows on %s, the partners %d on %s' % (play.step_q24.numel(), play.step_q24.device, self.file.numel(), dev))
+
+    def _check(self, what, B, dev):
+        if self.file.device != dev or self.file.numel() != B:
+            raise HfttError('%s: the part holds %d windows on %s, the request %d on %s' % (what, self.file.numel(), self.file.device, B, dev))
+
+
+def _tune_bits(tune, dev):
+    """a uint32-valued tuning table (any integer dtype, values 0 .. 2^32 - 1, or the int32 with the same bits) as int32 bits, like VoiceBank.inc"""
+    t = torch.as_tensor(tune, device=dev)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise HfttError('clip_synth: tune must be integers (Q31: 2^31 = unison), got %s' % t.dtype)
+    if t.dtype != torch.int32:
+        t = t.to(torch.int64)
+        t = torch.where(t >= 1 << 31, t - (1 << 32), t).to(torch.int32)
+    return t.contiguous()
+
+
+def tune_q31(cents):
+    """cents (a number or an array) -> the Q31 tuning factor round(2^(cents / 1200) * 2^31) as int64 numpy: what clip_synth takes as `tune`"""
+    return np.round(np.exp2(np.asarray(cents, np.float64) / 1200.0) * 2.0 ** 31).astype(np.int64)
+
+
+def synth_nsamp(table, file_nsamp, win_file, play=None):
+    """int64 [B] on the device: the length n' of each window's synthetic file under `play` (an ops.Warp or None) --
+    file_nsamp[f] + ceil(t'(file_end_sec[f]) * sr) - ceil(file_end_sec[f] * sr) with t' = (t + t_delay) * t_scale, so the release tail behind
+    the last offset keeps its length -- and 0 for a file outside the table.  What clip_synth takes as nsamp."""
+    if not isinstance(table, LabelsTable):
+        raise HfttError('synth_nsamp: table must be an ops.LabelsTable')
+    if play is not None and not isinstance(play, Warp):
+        raise HfttError('synth_nsamp: play must be an ops.Warp')
+    dev = table.device
+    file_nsamp = torch.as_tensor(file_nsamp, device=dev).to(torch.int64)
+    if file_nsamp.shape != (table.n_files,):
+        raise HfttError('synth_nsamp: file_nsamp must be [n_files=%d], got shape %s' % (table.n_files, tuple(file_nsamp.shape)))
+    f = torch.as_tensor(win_file, device=dev).long()
+    if f.dim() != 1:
+        raise HfttError('synth_nsamp: win_file must be [B], got shape %s' % (tuple(f.shape),))
+    ok = (f >= 0) & (f < table.n_files)
+    fc = f.clamp(0, table.n_files - 1)
+    n = file_nsamp[fc]
+    if play is not None:
+        if table.file_end_sec is None or table.sr is None:
+            raise HfttError('synth_nsamp: the note table carries no file_end_sec / sr: rebuild it with labels_table_host')
+        play._holds('synth_nsamp', f.numel(), dev)
+        end, sr = table.file_end_sec[fc], float(table.sr)
+        mapped = (end + play.t_delay(sr)) * play.t_scale()
+        n = n + torch.ceil(mapped * sr).long() - torch.ceil(end * sr).long()
+    return torch.where(ok, n, torch.zeros_like(n)).contiguous()
+
+
+def synth_frames(nsamp, hop):
+    """int64 [B]: the audio frame count 1 + n' / hop of each window's synthetic file (nsamp: synth_nsamp's result), 0 for an invalid window
+    (n' < 0).  What labels_render takes as a_frames next to a second part."""
+    n = torch.as_tensor(nsamp).to(torch.int64)
+    return torch.where(n >= 0, 1 + n // int(hop), torch.zeros_like(n)).contiguous()
+
+
+def clip_synth(table, file_nsamp, bank, voice_index, win_file, win_start, width, hop, sr, lead=0, n_fft=2048, play=None, tune=None, part=None, nsamp=None):
     """The samples of B clip windows RENDERED in ONE launch (hftt_clip_synth): window b shows frames win_start[b] .. + width of the synthetic
     file that the notes of file win_file[b] of `table` (a LabelsTable) make under voice voice_index[b] (int32 [B]) of `bank` (a VoiceBank);
     file_nsamp int64 [n_files] (a device tensor) is each file's length in samples.  lead: further frames rendered in front of each window, so
     that a room can follow (clip_room over the result as its corpus needs lead >= ceil(taps / hop)).  Returns what clip_room returns: (scratch
     fp32 [B, span], out_samp0 int64 [2 B + 1], out_win_file int32 [B], out_win_start int32 [B]); a plain clip_logmel over WetTable(scratch,
     out_samp0) with the two window tables gives the log-mel of the synthetic file.  A voice index outside 0 .. V - 1 makes a window without a
-    file.  Nothing is read back to the host; no CPU fallback."""
+    file.  Nothing is read back to the host; no CPU fallback.
+    With play, tune, part or nsamp the launch is hftt_clip_synth_parts: play, an ops.Warp, is how the windows are PLAYED -- shift [B] semitones
+    of transposition (an index into the bank), step_q24 the TEMPO * 2^24 and delay_q24 a delay in samples * 2^24, from which Warp derives
+    t_scale and t_delay (cut and proto are not used); tune, uint32-valued [B], the tuning in Q31 (2^31 = unison; ops.tune_q31); part, an
+    ops.SynthPart, a second part per window under its own voice and play, summed onto the first; nsamp int64 [B], the windows' file lengths
+    under their map (None: ops.synth_nsamp of file_nsamp and play).  With all four None the launch is hftt_clip_synth as it always was."""
+    launch, outs = _clip_synth_prepare(table, file_nsamp, bank, voice_index, win_file, win_start, width, hop, sr, lead, n_fft, play, tune, part, nsamp)
+    launch()
+    return outs
+
+
+def _clip_synth_prepare(table, file_nsamp, bank, voice_index, win_file, win_start, width, hop, sr, lead, n_fft, play, tune, part, nsamp):
+    """clip_synth's checks, derived tables and descriptor -> (launch, outputs): launch() enqueues the one kernel and nothing else (it keeps the
+    tensors the descriptor points to alive), so that a benchmark can time the launch without the derivations in front of it"""
     if not isinstance(table, LabelsTable):
         raise HfttError('clip_synth: table must be an ops.LabelsTable')
     if not isinstance(bank, VoiceBank):
@@ -1572,5 +1663,46 @@ def clip_synth(table, file_nsamp, bank, voice_index, win_file, win_start, width,
     d.inc, d.amp, d.dec, d.vel_gain, d.rel = (t.data_ptr() for t in (bank.inc, bank.amp, bank.dec, bank.vel_gain, bank.rel))
     d.attack, d.release, d.span = bank.attack.data_ptr(), bank.release.data_ptr(), span
     d.out, d.out_samp0, d.out_win_file, d.out_win_start = out.data_ptr(), samp0.data_ptr(), ofile.data_ptr(), ostart.data_ptr()
-    check(lib().hftt_clip_synth(C.byref(d), _stream(dev)), 'clip_synth')
-    return out, samp0, ofile, ostart
+    if play is None and tune is None and part is None and nsamp is None:
+        def launch(keep=(file_nsamp, win_file, win_start, voice_index)):
+            check(lib().hftt_clip_synth(C.byref(d), _stream(dev)), 'clip_synth')
+        return launch, (out, samp0, ofile, ostart)
+    if play is not None and not isinstance(play, Warp):
+        raise HfttError('clip_synth: play must be an ops.Warp')
+    if part is not None and not isinstance(part, SynthPart):
+        raise HfttError('clip_synth: part must be an ops.SynthPart')
+    m = ClipSynthPartsDesc()
+    m.base = d
+    nsamp = synth_nsamp(table, file_nsamp, win_file, play) if nsamp is None else torch.as_tensor(nsamp, device=dev).to(torch.int64).contiguous()
+    if nsamp.shape != win_file.shape:
+        raise HfttError('clip_synth: nsamp must be [B=%d], got shape %s' % (B, tuple(nsamp.shape)))
+    keep = [nsamp]
+    m.nsamp = nsamp.data_ptr()
+
+    def fill(args, p, t):
+        if p is not None:
+            ts = p._label_map('clip_synth', B, dev, table)
+            keep.append(ts)
+            args.shift, args.t_delay, args.t_scale = (x.data_ptr() for x in ts)
+        if t is not None:
+            t = _tune_bits(t, dev)
+            if t.shape != win_file.shape:
+                raise HfttError('clip_synth: tune must be [B=%d], got shape %s' % (B, tuple(t.shape)))
+            _need_cuda(t)
+            keep.append(t)
+            args.tune_q31 = t.data_ptr()
+    fill(m.play, play, tune)
+    if part is not None:
+        part._check('clip_synth', B, dev)
+        pn = synth_nsamp(table, file_nsamp, part.file, part.play)
+        _need_cuda(part.file, part.start, part.voice, part.gain, pn)
+        keep.append(pn)
+        m.part_file, m.part_start, m.part_voice, m.part_gain = part.file.data_ptr(), part.start.data_ptr(), part.voice.data_ptr(), part.gain.data_ptr()
+        m.part_nsamp = pn.data_ptr()
+        fill(m.part_play, part.play, part.tune)
+    _need_cuda(nsamp)
+    keep += [file_nsamp, win_file, win_start, voice_index]
+
+    def launch(keep=keep):
+        check(lib().hftt_clip_synth_parts(C.byref(m), _stream(dev)), 'clip_synth_parts')
+    return launch, (out, samp0, ofile, ostart)

@@ -30,7 +30,8 @@ alone under draws made beforehand: hftt_clip_room, the clip log-mel on the sourc
 The synth leg (modal synthesis: hftt_clip_synth + the plain hftt_clip_logmel on its scratch): SynthClipStore.batch (the notes alone resident, a
 bank of plucked-string voices from corpus.synth_audio.synth_voice_bank, a voice drawn per clip) against WaveClipStore.batch on the same
 clip ids of the same corpus, interleaved as above, the launches alone under draws made beforehand (hftt_clip_synth with lead 0 and with the
-lead a 4,096-tap room needs), and the bytes both stores keep in HBM."""
+lead a 4,096-tap room needs), the played clip synth as single launches prepared beforehand (hftt_clip_synth for comparison, then
+hftt_clip_synth_parts under an identity performance, under a drawn play and with a second part), and the bytes both stores keep in HBM."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'nylon-amt_amd'))
@@ -39,7 +40,7 @@ import torch
 from corpus import synth_audio as SA
 from corpus.make_dataset import assemble_note_store, assemble_synth_store, assemble_wave_store, finalize_config, prepare_config
 from hftt_hip import ops
-from training.dataset import NoteClipStore, SynthClipStore, WaveAugment, WaveClipStore
+from training.dataset import NoteClipStore, SynthClipStore, SynthPlay, WaveAugment, WaveClipStore, warped_frame
 
 
 def timed(fn):
@@ -162,6 +163,30 @@ def room_leg(wstore, config, dev, chunks, repeats=5, calls=60, warmup=10, taps=4
     return out
 
 
+def parts_launches(store, bank, voice, file, start, width, hop):
+    """the played clip synth on the clips of the timed call, each row ONE launch with everything in front of it prepared (ops._clip_synth_prepare):
+    hftt_clip_synth itself for comparison; hftt_clip_synth_parts under an identity performance, under a play (transposition, tempo, delay and
+    tune drawn per clip) and with a second part (another clip of the batch under a voice and a play of its own)"""
+    B, dev = file.numel(), file.device
+    play = SynthPlay(transpose=(-3, 3), tune_cents=30.0, tempo=(0.8, 1.25), shift=True, duet_p=1.0)
+    gen = torch.Generator(device=dev).manual_seed(2)
+    semis = lambda f: (-store.table.pitch_min[f.long()], store.table.N - 1 - store.table.pitch_max[f.long()])
+    warp, tune = play.draw_play(gen, B, hop, *semis(file))
+    _, _, pvoice, pgain = play.draw_duet(gen, B, len(store), bank.V)
+    pfile, pstart = file.roll(1), start.roll(1)                                 # the partner: the neighbouring clip of the batch, as dense as the primary
+    pwarp, ptune = play.draw_play(gen, B, hop, *semis(pfile))
+    part = ops.SynthPart(pfile, warped_frame(pstart + store.mb, pwarp, hop) - store.mb, pvoice, pgain, pwarp, ptune)
+    args = (store.table, store.file_nsamp, bank, voice, file)
+    ident = ops.synth_nsamp(store.table, store.file_nsamp, file)
+    mapped = ops.synth_nsamp(store.table, store.file_nsamp, file, warp)
+    wstart = warped_frame(start + store.mb, warp, hop) - store.mb
+    rows = {'clip_synth_launch': ops._clip_synth_prepare(*args, start, width, hop, store.sr, 0, 2048, None, None, None, None),
+            'clip_synth_parts_identity': ops._clip_synth_prepare(*args, start, width, hop, store.sr, 0, 2048, None, None, None, ident),
+            'clip_synth_parts_play': ops._clip_synth_prepare(*args, wstart, width, hop, store.sr, 0, 2048, warp, tune, None, mapped),
+            'clip_synth_parts_duet': ops._clip_synth_prepare(*args, wstart, width, hop, store.sr, 0, 2048, warp, tune, part, mapped)}
+    return {name: launch for name, (launch, _) in rows.items()}
+
+
 def synth_leg(wstore, notes, config, dev, batch, repeats=5, calls=60, warmup=10, voices=64, partials=16):
     """{leg: {'ms': median over the repeats, 'repeats': [...]}} for the wave store and the synth store on the same clip ids, interleaved inside
     every repeat (the order rotates); 'calls': the launches alone; and what both stores keep resident"""
@@ -194,6 +219,7 @@ def synth_leg(wstore, notes, config, dev, batch, repeats=5, calls=60, warmup=10,
     scratch = ops.WetTable(out0, samp0)
     fns = {'clip_synth': lambda: ops.clip_synth(store.table, store.file_nsamp, bank, voice, file, start, width, hop, store.sr),
            'clip_synth_lead_%d' % lead: lambda: ops.clip_synth(store.table, store.file_nsamp, bank, voice, file, start, width, hop, store.sr, lead=lead),
+           **parts_launches(store, bank, voice, file, start, width, hop),
            'clip_logmel_on_scratch': lambda: ops.clip_logmel(scratch, store.logmel, ofile, ostart, width, store.fill),
            'labels_render': lambda: ops.labels_render(store.table, file, store.clip_frame[c], store.T)}
     per, per_fn = {n: [] for n in names}, {n: [] for n in fns}

@@ -18,7 +18,9 @@ time budget is spent.  The model is pickled the way m_training.py:372-373 does i
 
 With --synth-store [--synth-voices V] [--synth-partials H] [--synth-seed S] the corpus keeps the NOTES alone: every batch's audio is rendered on
 the device under a plucked-string voice drawn per clip (assemble_synth_store, SynthClipStore, corpus.synth_audio.synth_voice_bank); the gain,
-noise and room options apply, warp and mix do not.
+noise and room options apply, warp and mix do not.  What is PLAYED varies instead: --synth-transpose LO HI, --synth-tune-cents C,
+--synth-tempo LO HI, --synth-shift, --synth-play-p P and --synth-duet-p P [--synth-duet-gain-db LO HI] (training.dataset.SynthPlay: every key,
+tuning, tempo and pairing of the note corpus, the labels rendered to match).
 
 Scoring (config 5): the seed-1234 minute -> log-mel -> 30 clips through AMT.transcript -> mpe2note -> note-F1 (onset, 50 ms) and frame-F1
 against the GENERATING notes, in x3, bf16 and parity mode, plus the frame-level agreement of the modes with each other.  One JSON line."""
@@ -31,7 +33,7 @@ import bench
 from corpus import synth_audio as SA
 from corpus.conv_note2label import note2label_arrays
 from corpus.make_dataset import assemble_note_store, assemble_store, assemble_synth_store, assemble_wave_store
-from training.dataset import MyDataset, DeviceClipStore, NoteClipStore, SynthClipStore, WaveAugment, WaveClipStore
+from training.dataset import MyDataset, DeviceClipStore, NoteClipStore, SynthClipStore, SynthPlay, WaveAugment, WaveClipStore
 from model.amt import AMT
 from hftt_hip import ops
 from evaluation.metrics import note_metrics, frame_metrics
@@ -39,18 +41,18 @@ from evaluation.metrics import note_metrics, frame_metrics
 ROOM_BANK_SIZE = 32          # responses of the synthetic room bank (--aug-room-p without --aug-room-bank)
 
 
-def build_corpus(config, files, dev, n_slice=8, note_store=False, wave_store=False, augment=None, synth=None):
+def build_corpus(config, files, dev, n_slice=8, note_store=False, wave_store=False, augment=None, synth=None, play=None):
     """`files` one-minute plucked-string files (seeds 2000..) -> HIP log-mel -> reference-recipe labels -> one MAESTRO-format store in HBM;
     note_store: features + note table in HBM instead, labels rendered per batch (a file is then as long as its label track, not cut to its
     feature array); wave_store: waveforms (int16) + note table in HBM, no feature pass, `augment` a WaveAugment or None;
     synth = (voices, partials, seed): the NOTES alone in HBM and a bank of that many plucked-string voices, every batch's audio rendered on the
-    device (no waveform is made here at all)"""
+    device (no waveform is made here at all), `play` a SynthPlay or None (its tune_cents is also the bank's Nyquist headroom)"""
     t0 = time.time()
     if synth is not None:
         note_lists = [SA.pluck_notes(2000 + i) for i in range(files)]
-        voices = SA.synth_voice_bank(synth[0], config, seed=synth[2], partials=synth[1])
+        voices = SA.synth_voice_bank(synth[0], config, seed=synth[2], partials=synth[1], headroom_cents=play.tune_cents if play is not None else 0.0)
         store = assemble_synth_store(note_lists, config, release_samples=int(voices['release'].max()))
-        clips = SynthClipStore(store, config, dev, ops.VoiceBank(device=dev, **voices), n_slice, seed=synth[2], augment=augment)
+        clips = SynthClipStore(store, config, dev, ops.VoiceBank(device=dev, **voices), n_slice, seed=synth[2], augment=augment, play=play)
         return clips, {'files': files, 'samples': int(store['file_nsamp'].sum()), 'clips': len(clips), 'notes': clips.table.n_notes, 'voices': synth[0],
                        'partials': synth[1], 'resident_bytes': clips.resident_bytes(), 'seconds_to_build': round(time.time() - t0, 1)}
     if wave_store:
@@ -222,6 +224,13 @@ def main():
     ap.add_argument('--aug-detune-cents', type=float, default=0.0, metavar='C', help='with --wave-store: per-clip detune, uniform in +-C cents (C <= 50)')
     ap.add_argument('--aug-shift', action='store_true', help='with --wave-store: per-clip time offset, uniform in [0, hop) samples')
     ap.add_argument('--aug-warp-p', type=float, default=1.0, metavar='P', help='probability that a clip is warped at all (pitch, detune, shift)')
+    ap.add_argument('--synth-transpose', type=int, nargs=2, metavar=('LO', 'HI'), default=None, help='with --synth-store: transpose each clip by a whole number of semitones uniform in LO .. HI (-11 .. 11), labels moved to match')
+    ap.add_argument('--synth-tune-cents', type=float, default=None, metavar='C', help='with --synth-store: tune each clip by an offset uniform in +-C cents (at most 50)')
+    ap.add_argument('--synth-tempo', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --synth-store: play each clip at a tempo log-uniform in LO .. HI (inside 0.5 .. 2); decays do not scale')
+    ap.add_argument('--synth-shift', action='store_true', help='with --synth-store: delay each clip by a draw from [0, hop) samples')
+    ap.add_argument('--synth-play-p', type=float, default=None, metavar='P', help='with --synth-store: probability that a clip is played under its draws at all (default 1)')
+    ap.add_argument('--synth-duet-p', type=float, default=None, metavar='P', help='with --synth-store: probability that a clip gets a second part, another clip under a voice and a play of its own (the labels are those of the sum)')
+    ap.add_argument('--synth-duet-gain-db', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --synth-duet-p: the second part\'s gain, uniform in dB (default -6 0)')
     ap.add_argument('--aug-mix-p', type=float, default=0.0, metavar='P', help='with --wave-store: probability that a clip is summed with another clip of the corpus (the labels are those of the sum)')
     ap.add_argument('--aug-mix-gain-db', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --aug-mix-p: the partner clip\'s gain, uniform in dB (default -6 0)')
     ap.add_argument('--aug-room-p', type=float, default=0.0, metavar='P', help='with --wave-store: probability that a clip is convolved with an impulse response of the room bank (the labels are unchanged)')
@@ -243,6 +252,19 @@ def main():
         ap.error('--synth-store, --wave-store and --note-store are exclusive: each names what the corpus keeps in HBM')
     if not args.synth_store and any(x is not None for x in (args.synth_voices, args.synth_partials, args.synth_seed)):
         ap.error('--synth-voices / --synth-partials / --synth-seed describe the voice bank: they need --synth-store')
+    synth_play = (args.synth_shift or any(x is not None for x in (args.synth_transpose, args.synth_tune_cents, args.synth_tempo, args.synth_play_p,
+                                                                  args.synth_duet_p, args.synth_duet_gain_db)))
+    if synth_play and not args.synth_store:
+        ap.error('--synth-transpose / --synth-tune-cents / --synth-tempo / --synth-shift / --synth-play-p / --synth-duet-p / --synth-duet-gain-db '
+                 'say how the notes are played: they need --synth-store')
+    play = None
+    if synth_play:
+        try:
+            play = SynthPlay(transpose=args.synth_transpose, tune_cents=args.synth_tune_cents or 0.0, tempo=args.synth_tempo, shift=args.synth_shift,
+                             p_play=1.0 if args.synth_play_p is None else args.synth_play_p, duet_p=args.synth_duet_p or 0.0,
+                             duet_gain_db=args.synth_duet_gain_db or (-6.0, 0.0))
+        except ops.HfttError as e:
+            ap.error(str(e))
     waveform = args.wave_store or args.synth_store          # the stores with a waveform to augment
     warp_aug = args.aug_pitch is not None or args.aug_detune_cents != 0.0 or args.aug_shift or args.aug_warp_p != 1.0
     mix_aug = args.aug_mix_p != 0.0 or args.aug_mix_gain_db is not None
@@ -296,7 +318,11 @@ def main():
                                   detune_cents=args.aug_detune_cents, shift=args.aug_shift, p_warp=args.aug_warp_p, mix_p=args.aug_mix_p,
                                   mix_gain_db=args.aug_mix_gain_db or (-6.0, 0.0), room_p=args.aug_room_p, room_bank=bank)
         clips, log['corpus'] = build_corpus(config, args.files, dev, note_store=args.note_store, wave_store=args.wave_store, augment=augment,
-                                           synth=(args.synth_voices or 64, args.synth_partials or 16, args.seed if args.synth_seed is None else args.synth_seed) if args.synth_store else None)
+                                           synth=(args.synth_voices or 64, args.synth_partials or 16, args.seed if args.synth_seed is None else args.synth_seed) if args.synth_store else None,
+                                           play=play)
+        if play is not None:
+            log['synth_play'] = {'transpose': play.transpose, 'tune_cents': play.tune_cents, 'tempo': play.tempo, 'shift': play.shift, 'p_play': play.p_play,
+                                 'duet_p': play.duet_p, 'duet_gain_db': play.duet_gain_db}
         if waveform:
             log['augment'] = {'gain_db': args.aug_gain_db, 'noise_dbfs': args.aug_noise_dbfs, 'pitch_semitones': args.aug_pitch,
                               'detune_cents': args.aug_detune_cents, 'shift': args.aug_shift, 'p_warp': args.aug_warp_p,
