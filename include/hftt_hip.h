@@ -1208,6 +1208,36 @@ int hftt_adam_step_groups(const hftt_adam_groups_desc* d, void* stream);
 int hftt_grad_norm_groups(const float* g, int64_t n, const uint8_t* quad_group, uint32_t frozen_mask, double grad_scale, double max_norm,
                           void* ws, hftt_guard_ctl* ctl, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Averaged weights inside the Adam step (csrc/guard.hip): the exponential moving average (EMA) of the parameters,
+ * torch.optim.swa_utils.get_ema_multi_avg_fn(beta): e = beta * e + (1 - beta) * p on the parameters AFTER the step, in the launch that
+ * already visits every element.  ADDED at ABI 8 like the two sections above; HFTT_ABI_VERSION stays 8 and hftt_adam_step,
+ * hftt_adam_step_guarded and hftt_adam_step_groups are untouched.
+ *
+ * hftt_adam_step_ema: ONE launch.  Per quad hftt_adam_step_groups' update, unchanged (the same constants formed the same way on the host,
+ * the same reading of `ctl`, the same frozen-quad skip, the same grid rule), then on the new p still in registers, contraction off,
+ *     y = omd * (p - e) - c;   t = e + y;   c = (t - e) - y;   e = t;          omd = (float)(1 - ema_decay)   (formed in double, rounded once)
+ * with e = ema[i] and c = ema_c[i], both loaded and stored with 16-byte accesses (44 B of traffic per element against 28).  c is the running
+ * compensation (Kahan): the plain fp32 form e += omd (p - e) stops moving once omd |p - e| < ulp(e) / 2 -- with beta = 0.9999 that is
+ * |p - e| < 6e-4 |e|, weights that jitter round a mean at the end of a decayed schedule -- while the compensated sum follows the fp64
+ * recurrence to a few ulp over thousands of calls.  ema_decay is the beta of THIS call, so a warm-up schedule costs nothing.
+ * Consequences:
+ *   - p, m, v after the call are bit-identical to the non-EMA entry point of the same configuration: hftt_adam_step (one group, no decay,
+ *     ctl NULL), hftt_adam_step_guarded (one group, ctl given), hftt_adam_step_groups.
+ *   - apply == 0: nothing is stored, ema and ema_c included.
+ *   - a frozen quad's ema and ema_c are neither loaded nor stored.
+ * a.quad_group may be NULL when a.n_groups == 1 and a.frozen[0] == 0 (one group over the whole buffer needs no map).
+ * Refused in front of the launch: what hftt_adam_step_groups refuses (but for that null map); a null descriptor; ema or ema_c null or not
+ * 16-byte aligned; ema or ema_c overlapping p, g, m, v or each other; ema_decay NaN, negative or >= 1; n % 4 != 0.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {
+  hftt_adam_groups_desc a;   /* as hftt_adam_step_groups; a.quad_group may be NULL when a.n_groups == 1 and a.frozen[0] == 0 */
+  float* ema;                /* [n] the average, 16-byte aligned */
+  float* ema_c;              /* [n] its running compensation, 16-byte aligned */
+  double ema_decay;          /* beta of THIS call, 0 <= beta < 1; omd = (float)(1 - beta), formed in double, rounded once */
+} hftt_adam_ema_desc;
+int hftt_adam_step_ema(const hftt_adam_ema_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

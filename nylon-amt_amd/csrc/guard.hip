@@ -4,7 +4,8 @@
 // tickets: every sum has one fixed order, so the record is bitwise reproducible.  Entry points and the torch definitions they restate:
 // include/hftt_hip.h.  The unguarded step (hftt_adam_step / adam_kernel) stays the default path; all three Adam kernels share one update.
 // The grouped forms (hftt_grad_norm_groups, hftt_adam_step_groups) read a per-quad group map: per-group learning rate and decay, and frozen
-// groups whose quads are neither loaded nor stored (fine-tuning).
+// groups whose quads are neither loaded nor stored (fine-tuning).  hftt_adam_step_ema is the grouped step with the exponential moving average
+// of the parameters carried in the same launch (a compensated fp32 sum); it is opt-in and shares the update with the three kernels above.
 #include "hftt_common.h"
 #include "hftt_launch.h"
 #include "../../include/hftt_hip.h"
@@ -198,12 +199,96 @@ __global__ __launch_bounds__(GN_THREADS) void adam_groups_kernel(float* __restri
   }
 }
 
-// workgroups over n elements read four at a time: the grid of all three Adam kernels (ceil((n / 4 + 1) / 256), at most GN_MAX_WGS)
+// ------------------------------------------------------------------ the averaged weights (EMA) behind the update
+// e += omd (p - e), omd = 1 - beta, on the NEW p, carried with a running compensation c (Kahan): in plain fp32 the sum stops moving once
+// omd |p - e| < ulp(e) / 2, which with beta = 0.9999 is |p - e| < 6e-4 |e| -- the end of a decayed schedule.  c holds what the last sum
+// dropped and hands it to the next.  Contraction off as in adam_update: (t - e) - y is the rounding error of t = e + y only as written.
+__device__ __forceinline__ void ema_update(float& e, float& c, float p, float omd) {
+#pragma clang fp contract(off)
+  const float y = omd * (p - e) - c;
+  const float t = e + y;
+  c = (t - e) - y;
+  e = t;
+}
+
+// adam_groups_kernel's step, then ema_update per element on the p still in registers: six 16-byte loads and five 16-byte stores per quad
+// (44 B per element against 28).  quad_group == nullptr: one group (index 0), which the host admits only unfrozen.  Skip and frozen quads as in
+// adam_groups_kernel: neither loads nor stores, ema and ema_c included.
+__global__ __launch_bounds__(GN_THREADS) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                              float* __restrict__ v, float* __restrict__ ema, float* __restrict__ ema_c, long n4,
+                                                              const uint8_t* __restrict__ quad_group, adam_group_consts c, float beta1, float beta2,
+                                                              float omb1, float omb2, float eps, float inv_sqrt_bc2, float grad_scale, float omd,
+                                                              const hftt_guard_ctl* __restrict__ ctl) {
+  if (ctl != nullptr && ctl->apply == 0u) return;          // (uniform, as in adam_guarded_kernel)
+  __shared__ float s_lr[HFTT_ADAM_MAX_GROUPS], s_d[HFTT_ADAM_MAX_GROUPS];
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < HFTT_ADAM_MAX_GROUPS; k++) { s_lr[k] = c.lr_c[k]; s_d[k] = c.d[k]; }
+  }
+  __syncthreads();
+  const float s = grad_scale * (ctl != nullptr ? ctl->coef : 1.f);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const unsigned gi = quad_group != nullptr ? quad_group[i] & (HFTT_ADAM_MAX_GROUPS - 1) : 0u;
+    if ((c.frozen_mask >> gi) & 1u) continue;
+    const float lr_c = s_lr[gi], d = s_d[gi];
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    float4 mm = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    float4 ee = reinterpret_cast<float4*>(ema)[i];
+    float4 cc = reinterpret_cast<float4*>(ema_c)[i];
+    float* pe = &pp.x; const float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x; float* ee4 = &ee.x; float* ce = &cc.x;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      adam_update<true>(pe[e], ge[e], me[e], ve[e], s, d, lr_c, beta1, beta2, omb1, omb2, eps, inv_sqrt_bc2);
+      ema_update(ee4[e], ce[e], pe[e], omd);
+    }
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(m)[i] = mm;
+    reinterpret_cast<float4*>(v)[i] = vv;
+    reinterpret_cast<float4*>(ema)[i] = ee;
+    reinterpret_cast<float4*>(ema_c)[i] = cc;
+  }
+}
+
+// workgroups over n elements read four at a time: the grid of all Adam kernels (ceil((n / 4 + 1) / 256), at most GN_MAX_WGS)
 inline int guard_grid(long n) {
   long b = (n / 4 + 1 + GN_THREADS - 1) / GN_THREADS;
   if (b < 1) b = 1;
   if (b > GN_MAX_WGS) b = GN_MAX_WGS;
   return (int)b;
+}
+
+// What hftt_adam_step_groups and hftt_adam_step_ema refuse alike (`who` names the entry point in the message), and the constants both kernels
+// take: everything that is a function of the hyper-parameters alone is formed in double and rounded once, as in hftt_adam_step_guarded.
+// map_optional: a null map stands for one unfrozen group.
+int adam_groups_host(const char* who, const hftt_adam_groups_desc& a, bool map_optional, adam_group_consts& c, float& inv_sqrt_bc2) {
+  HFTT_REQUIRE(a.p && a.g && a.m && a.v && a.n > 0 && a.step >= 1, "%s: bad arguments", who);
+  HFTT_REQUIRE((((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0, "%s: buffers must be 16-byte aligned", who);
+  HFTT_REQUIRE(a.n % 4 == 0, "%s: n=%ld must be a multiple of 4 (one map entry per quad)", who, (long)a.n);
+  HFTT_REQUIRE(a.n_groups >= 1 && a.n_groups <= HFTT_ADAM_MAX_GROUPS, "%s: n_groups=%d must be in 1..%d", who, (int)a.n_groups, HFTT_ADAM_MAX_GROUPS);
+  HFTT_REQUIRE(a.quad_group != nullptr || (map_optional && a.n_groups == 1 && a.frozen[0] == 0), "%s: the group map is null", who);
+  HFTT_REQUIRE(((uintptr_t)a.ctl & 15) == 0, "%s: ctl must be 16-byte aligned (NULL: unguarded)", who);
+  const double bc1 = 1.0 - pow(a.beta1, (double)a.step);
+  const double bc2 = 1.0 - pow(a.beta2, (double)a.step);
+  c.frozen_mask = 0u;
+  for (int k = 0; k < HFTT_ADAM_MAX_GROUPS; k++) {
+    c.lr_c[k] = 0.f; c.d[k] = 1.f;
+    if (k >= a.n_groups) continue;
+    HFTT_REQUIRE(a.weight_decay[k] >= 0.0, "%s: group %d: weight_decay must be >= 0", who, k);                  // (false for NaN too)
+    HFTT_REQUIRE(a.lr[k] * a.weight_decay[k] < 1.0, "%s: group %d: lr * weight_decay must be below 1", who, k);
+    c.lr_c[k] = (float)(a.lr[k] / bc1);
+    c.d[k] = (float)(1.0 - a.lr[k] * a.weight_decay[k]);
+    if (a.frozen[k]) c.frozen_mask |= 1u << k;
+  }
+  inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  return 0;
+}
+
+// do [a, a + bytes) and [b, b + bytes) share a byte?
+inline bool ranges_overlap(const void* a, const void* b, uint64_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
 }
 
 }  // namespace
@@ -274,27 +359,31 @@ extern "C" int hftt_grad_norm_groups(const float* g, int64_t n, const uint8_t* q
 extern "C" int hftt_adam_step_groups(const hftt_adam_groups_desc* dsc, void* stream) {
   HFTT_REQUIRE(dsc != nullptr, "adam_step_groups: null descriptor");
   const hftt_adam_groups_desc& a = *dsc;
-  HFTT_REQUIRE(a.p && a.g && a.m && a.v && a.n > 0 && a.step >= 1, "adam_step_groups: bad arguments");
-  HFTT_REQUIRE((((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0, "adam_step_groups: buffers must be 16-byte aligned");
-  HFTT_REQUIRE(a.n % 4 == 0, "adam_step_groups: n=%ld must be a multiple of 4 (one map entry per quad)", (long)a.n);
-  HFTT_REQUIRE(a.n_groups >= 1 && a.n_groups <= HFTT_ADAM_MAX_GROUPS, "adam_step_groups: n_groups=%d must be in 1..%d", (int)a.n_groups, HFTT_ADAM_MAX_GROUPS);
-  HFTT_REQUIRE(a.quad_group != nullptr, "adam_step_groups: the group map is null");
-  HFTT_REQUIRE(((uintptr_t)a.ctl & 15) == 0, "adam_step_groups: ctl must be 16-byte aligned (NULL: unguarded)");
-  // as hftt_adam_step_guarded: everything that is a function of the hyper-parameters alone is formed in double and rounded once
-  const double bc1 = 1.0 - pow(a.beta1, (double)a.step);
-  const double bc2 = 1.0 - pow(a.beta2, (double)a.step);
   adam_group_consts c;
-  c.frozen_mask = 0u;
-  for (int k = 0; k < HFTT_ADAM_MAX_GROUPS; k++) {
-    c.lr_c[k] = 0.f; c.d[k] = 1.f;
-    if (k >= a.n_groups) continue;
-    HFTT_REQUIRE(a.weight_decay[k] >= 0.0, "adam_step_groups: group %d: weight_decay must be >= 0", k);                  // (false for NaN too)
-    HFTT_REQUIRE(a.lr[k] * a.weight_decay[k] < 1.0, "adam_step_groups: group %d: lr * weight_decay must be below 1", k);
-    c.lr_c[k] = (float)(a.lr[k] / bc1);
-    c.d[k] = (float)(1.0 - a.lr[k] * a.weight_decay[k]);
-    if (a.frozen[k]) c.frozen_mask |= 1u << k;
-  }
+  float inv_sqrt_bc2;
+  if (int rc = adam_groups_host("adam_step_groups", a, false, c, inv_sqrt_bc2)) return rc;
   return hftt_launch<adam_groups_kernel>("adam_step_groups", dim3(guard_grid((long)a.n)), dim3(GN_THREADS), 0, (hipStream_t)stream, a.p, a.g, a.m, a.v,
                                          (long)(a.n / 4), a.quad_group, c, (float)a.beta1, (float)a.beta2, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2),
-                                         (float)a.eps, (float)(1.0 / sqrt(bc2)), (float)a.grad_scale, a.ctl);
+                                         (float)a.eps, inv_sqrt_bc2, (float)a.grad_scale, a.ctl);
+}
+
+extern "C" int hftt_adam_step_ema(const hftt_adam_ema_desc* dsc, void* stream) {
+  HFTT_REQUIRE(dsc != nullptr, "adam_step_ema: null descriptor");
+  const hftt_adam_groups_desc& a = dsc->a;
+  adam_group_consts c;
+  float inv_sqrt_bc2;
+  if (int rc = adam_groups_host("adam_step_ema", a, true, c, inv_sqrt_bc2)) return rc;
+  float* const ema = dsc->ema; float* const ema_c = dsc->ema_c;
+  HFTT_REQUIRE(ema != nullptr && ema_c != nullptr, "adam_step_ema: ema or ema_c is null");
+  HFTT_REQUIRE((((uintptr_t)ema | (uintptr_t)ema_c) & 15) == 0, "adam_step_ema: ema and ema_c must be 16-byte aligned");
+  const uint64_t bytes = (uint64_t)a.n * 4;
+  for (const void* q : {(const void*)a.p, (const void*)a.g, (const void*)a.m, (const void*)a.v})
+    HFTT_REQUIRE(!ranges_overlap(ema, q, bytes) && !ranges_overlap(ema_c, q, bytes), "adam_step_ema: ema and ema_c must not overlap p, g, m or v");
+  HFTT_REQUIRE(!ranges_overlap(ema, ema_c, bytes), "adam_step_ema: ema and ema_c must not overlap each other");
+  HFTT_REQUIRE(dsc->ema_decay >= 0.0 && dsc->ema_decay < 1.0, "adam_step_ema: ema_decay=%g must be in [0, 1)", dsc->ema_decay);          // (false for NaN too)
+  // 1 - beta in double, rounded once: 1.f - (float)0.9999 is 1.0001659e-4, off by 1.7e-4 relative
+  const float omd = (float)(1.0 - dsc->ema_decay);
+  return hftt_launch<adam_ema_kernel>("adam_step_ema", dim3(guard_grid((long)a.n)), dim3(GN_THREADS), 0, (hipStream_t)stream, a.p, a.g, a.m, a.v, ema, ema_c,
+                                      (long)(a.n / 4), a.quad_group, c, (float)a.beta1, (float)a.beta2, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2),
+                                      (float)a.eps, inv_sqrt_bc2, (float)a.grad_scale, omd, a.ctl);
 }

@@ -325,6 +325,10 @@ class AdamGroupsDesc(C.Structure):          # hftt_adam_groups_desc: the grouped
                 ('ctl', C.c_void_p)]
 
 
+class AdamEmaDesc(C.Structure):             # hftt_adam_ema_desc: the grouped Adam step with the averaged weights carried in the same launch
+    _fields_ = [('a', AdamGroupsDesc), ('ema', C.c_void_p), ('ema_c', C.c_void_p), ('ema_decay', C.c_double)]
+
+
 class GuardCtl(C.Structure):                # hftt_guard_ctl: 32 bytes of device memory (the host only reads it back)
     _fields_ = [('norm', C.c_float), ('coef', C.c_float), ('apply', C.c_uint32), ('skipped', C.c_uint32), ('clipped', C.c_uint32),
                 ('pad', C.c_uint32 * 3)]
@@ -400,6 +404,7 @@ SIGNATURES = {
                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     'hftt_adam_step_groups': (C.c_int, [C.POINTER(AdamGroupsDesc), C.c_void_p]),
     'hftt_grad_norm_groups': (C.c_int, [c_f32p, C.c_int64, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hftt_adam_step_ema': (C.c_int, [C.POINTER(AdamEmaDesc), C.c_void_p]),
 }
 
 _lib = None

@@ -10,7 +10,7 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (ADAM_MAX_GROUPS, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipRoomDesc, ClipSynthDesc, ClipSynthPartsDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
+from ._capi import (ADAM_MAX_GROUPS, AdamEmaDesc, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipRoomDesc, ClipSynthDesc, ClipSynthPartsDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
                     WARP_DELAY_MAX, WARP_STEP_MAX, WARP_STEP_MIN, WARP_TABLE_L, WARP_TABLE_LEN, WARP_ZEROS,
                     LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, ROOM_MAX_TAPS, STITCH_MAX_CLIPS, SYNTH_MAX_PARTIALS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
@@ -515,26 +515,49 @@ def grad_norm_groups(g, quad_group, frozen_mask, ctl, ws, grad_scale=1.0, max_no
                                       _stream(g.device)), 'grad_norm_groups')
 
 
-def adam_step_groups(p, g, m, v, step, quad_group, lr, weight_decay=None, frozen=None, ctl=None, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
-    """One launch over the flat buffers with per-group constants: lr, weight_decay (decoupled) and frozen are sequences of one value per
-    group (1..8 groups).  ctl: the guard record (None: unguarded).  Quads of a frozen group are neither read nor written."""
-    _need_cuda(p, g, m, v, quad_group, ctl)
+def _adam_groups_desc(dsc, what, p, g, m, v, step, quad_group, lr, weight_decay, frozen, ctl, beta1, beta2, eps, grad_scale, map_optional=False):
+    """fill an AdamGroupsDesc (hftt_adam_step_groups, and the `a` of hftt_adam_step_ema); quad_group None: one unfrozen group (the EMA step only)"""
     lr = [float(x) for x in lr]
     k = len(lr)
     weight_decay = [0.0] * k if weight_decay is None else [float(x) for x in weight_decay]
     frozen = [False] * k if frozen is None else [bool(x) for x in frozen]
     if len(weight_decay) != k or len(frozen) != k:
-        raise HfttError('adam_step_groups: lr, weight_decay and frozen must have one entry per group')
-    if quad_group.dtype != torch.uint8 or quad_group.numel() * 4 != p.numel() or not quad_group.is_contiguous():
-        raise HfttError('adam_step_groups: the group map must be a contiguous uint8 tensor with one entry per quad of p')
-    dsc = AdamGroupsDesc()
+        raise HfttError('%s: lr, weight_decay and frozen must have one entry per group' % what)
+    if quad_group is None:
+        if not map_optional or k != 1 or frozen[0]:
+            raise HfttError('%s: the group map may be left out only for one unfrozen group' % what)
+    elif quad_group.dtype != torch.uint8 or quad_group.numel() * 4 != p.numel() or not quad_group.is_contiguous():
+        raise HfttError('%s: the group map must be a contiguous uint8 tensor with one entry per quad of p' % what)
     dsc.p, dsc.g, dsc.m, dsc.v, dsc.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-    dsc.quad_group, dsc.n_groups, dsc.step = quad_group.data_ptr(), k, step
+    dsc.quad_group, dsc.n_groups, dsc.step = None if quad_group is None else quad_group.data_ptr(), k, step
     dsc.beta1, dsc.beta2, dsc.eps, dsc.grad_scale = beta1, beta2, eps, grad_scale
     for i in range(min(k, ADAM_MAX_GROUPS)):
         dsc.lr[i], dsc.weight_decay[i], dsc.frozen[i] = lr[i], weight_decay[i], 1 if frozen[i] else 0
     dsc.ctl = None if ctl is None else ctl.data_ptr()
+
+
+def adam_step_groups(p, g, m, v, step, quad_group, lr, weight_decay=None, frozen=None, ctl=None, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
+    """One launch over the flat buffers with per-group constants: lr, weight_decay (decoupled) and frozen are sequences of one value per
+    group (1..8 groups).  ctl: the guard record (None: unguarded).  Quads of a frozen group are neither read nor written."""
+    _need_cuda(p, g, m, v, quad_group, ctl)
+    dsc = AdamGroupsDesc()
+    _adam_groups_desc(dsc, 'adam_step_groups', p, g, m, v, step, quad_group, lr, weight_decay, frozen, ctl, beta1, beta2, eps, grad_scale)
     check(lib().hftt_adam_step_groups(C.byref(dsc), _stream(p.device)), 'adam_step_groups')
+
+
+def adam_step_ema(p, g, m, v, ema, ema_c, step, ema_decay, lr, quad_group=None, weight_decay=None, frozen=None, ctl=None, beta1=0.9, beta2=0.999,
+                  eps=1e-8, grad_scale=1.0):
+    """adam_step_groups with the averaged weights carried in the same launch: behind the update, e += (1 - ema_decay) (p - e) on the new p as
+    a compensated fp32 sum (ema: the average, ema_c: its running compensation, both fp32 of p's length).  p, m, v end bit-identical to the
+    step without the average; a skipped step and frozen quads leave ema and ema_c alone.  quad_group None: one unfrozen group (lr a
+    one-element sequence) -- with ctl None that is adam_step, with ctl adam_step_guarded."""
+    _need_cuda(p, g, m, v, ema, ema_c, quad_group, ctl)
+    if ema.numel() != p.numel() or ema_c.numel() != p.numel() or ema.dtype != torch.float32 or ema_c.dtype != torch.float32:
+        raise HfttError('adam_step_ema: ema and ema_c must be fp32 tensors of p\'s length')
+    dsc = AdamEmaDesc()
+    _adam_groups_desc(dsc.a, 'adam_step_ema', p, g, m, v, step, quad_group, lr, weight_decay, frozen, ctl, beta1, beta2, eps, grad_scale, map_optional=True)
+    dsc.ema, dsc.ema_c, dsc.ema_decay = ema.data_ptr(), ema_c.data_ptr(), float(ema_decay)
+    check(lib().hftt_adam_step_ema(C.byref(dsc), _stream(p.device)), 'adam_step_ema')
 
 
 # ------------------------------------------------------------------------------------------------

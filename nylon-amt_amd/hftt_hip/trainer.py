@@ -6,6 +6,7 @@ gradient buffer.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import weakref
 
@@ -104,9 +105,30 @@ class FusedAdam(torch.optim.Optimizer):
 
     The decision is taken on the device: ``grad_norm`` and ``clip_coef`` are 0-dim device views of the kernel's record (reading them does
     not synchronise); ``skipped_steps`` and ``clipped_steps`` are Python ints, and reading them DOES synchronise.  ``state_dict()`` carries
-    the two counters as ``hftt_guard``; a state without that key (older checkpoints, the reference's ``.dat``) loads."""
+    the two counters as ``hftt_guard``; a state without that key (older checkpoints, the reference's ``.dat``) loads.
 
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, guard=False, weight_decay=0.0, model=None):
+    Averaged weights (opt-in; ``ema_decay=None`` allocates nothing and launches exactly the kernels described above):
+
+    ``ema_decay``      the exponential moving average of the parameters, ``torch.optim.swa_utils.get_ema_multi_avg_fn(ema_decay)`` after every
+                     step, carried INSIDE the Adam launch (``hftt_adam_step_ema``: all three configurations -- plain, guarded, grouped -- go
+                     through it, the guarded norm in front as before) as a compensated fp32 sum, because the plain fp32 ``lerp_`` stops moving
+                     when the weights only jitter round a mean.  Parameters and moments keep the bits of the step without the average; a
+                     skipped step and frozen ranges leave the average alone.  Shared by all groups like ``betas``.  The average starts as a
+                     copy of the parameters at ``attach`` (right for fine-tuning from trained weights).
+    ``ema_warmup``     from scratch: the decay of call ``t`` (0-based; calls count as for ``step``, skipped ones included) is
+                     ``min(ema_decay, (1 + t) / (10 + t))``, so the random initialisation is forgotten quickly.  The decay travels in the
+                     launch descriptor: a schedule costs nothing.
+
+    ``state[p]['ema']`` and ``state[p]['ema_c']`` (the running compensation) are views into two flat buffers, like the moments, and travel
+    through ``state_dict()`` with them; ``hftt_ema = {'decay', 'warmup', 'updates'}`` rides along.  A state without them loaded into an
+    optimizer with the option restarts the average from the parameters; a state with them turns the option on.
+    ``with opt.averaged_weights():`` puts the average into the model for evaluation (contents are swapped, so every launch plan keeps its
+    addresses) and restores every bit on exit; ``step()`` inside is refused and the context does not nest.  ``opt.averaged_model()`` is a
+    CPU copy of the model that holds the average, for pickling.  Under DDP every rank applies the same update to the same bits, so the
+    averages agree without communication."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, guard=False, weight_decay=0.0, model=None,
+                 ema_decay=None, ema_warmup=False):
         """model: the module whose parameters the groups hold -- needed only where the group map is wanted before an engine has bound them
         (``frozen_stages()`` on a host without a GPU); with a bound engine the layout is the engine's."""
         if hasattr(params, 'hftt_engine'):
@@ -129,9 +151,12 @@ class FusedAdam(torch.optim.Optimizer):
             raise HfttError('FusedAdam: max_grad_norm=%r must be positive (None: no clipping)' % (max_grad_norm,))
         if not float(weight_decay) >= 0.0:
             raise HfttError('FusedAdam: weight_decay=%r must be >= 0' % (weight_decay,))
+        for d in [ema_decay] + [g.get('ema_decay') for g in params if isinstance(g, dict)]:
+            self._check_ema_decay(d)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None, capturable=False,
                                       differentiable=False, fused=None, decoupled_weight_decay=weight_decay != 0,
-                                      max_grad_norm=None if max_grad_norm is None else float(max_grad_norm), guard=bool(guard), frozen=False))
+                                      max_grad_norm=None if max_grad_norm is None else float(max_grad_norm), guard=bool(guard), frozen=False,
+                                      ema_decay=None if ema_decay is None else float(ema_decay), ema_warmup=bool(ema_warmup)))
         for g in self.param_groups:
             g['decoupled_weight_decay'] = g['weight_decay'] != 0
         self._check_shared()
@@ -142,6 +167,9 @@ class FusedAdam(torch.optim.Optimizer):
         self.exp_avg = self.exp_avg_sq = None
         self._ctl = self._ws = None               # the guarded step's device record and workspace (attach)
         self._pending_guard = None                # counters of a checkpoint loaded before any engine existed
+        self.ema = self.ema_c = None              # the averaged weights and their running compensation (attach, with ema_decay)
+        self.ema_updates = 0                      # calls the average has seen (the t of ema_warmup)
+        self._averaged = False                    # inside averaged_weights()
 
     # ---- binding to the engine's flat buffers (lazy: the engine binds at the model's first forward)
     def _params(self):
@@ -152,7 +180,7 @@ class FusedAdam(torch.optim.Optimizer):
     def _check_shared(self):
         g0 = self.param_groups[0]
         for g in self.param_groups[1:]:
-            for k in ('betas', 'eps', 'max_grad_norm', 'guard'):
+            for k in ('betas', 'eps', 'max_grad_norm', 'guard', 'ema_decay', 'ema_warmup'):
                 a, b = g0.get(k), g.get(k)
                 if (tuple(a) != tuple(b)) if k == 'betas' else (a != b):
                     raise HfttError('FusedAdam: parameter groups disagree on %s (%r against %r): it is shared by all groups' % (k, a, b))
@@ -215,7 +243,8 @@ class FusedAdam(torch.optim.Optimizer):
         return self._group_map()['stages']
 
     def attach(self, engine):
-        if self.engine is engine and self.exp_avg is not None and self.exp_avg.numel() == engine.flat_params.numel():
+        if (self.engine is engine and self.exp_avg is not None and self.exp_avg.numel() == engine.flat_params.numel()
+                and (self.ema is not None) == (self.param_groups[0].get('ema_decay') is not None)):
             return
         ps = self._params()
         bound = [p for _, p, _, _ in engine._bound]
@@ -238,6 +267,7 @@ class FusedAdam(torch.optim.Optimizer):
                 self.step_count = int(old[p]['step'])
             st['step'] = torch.tensor(float(self.step_count))
             st['exp_avg'], st['exp_avg_sq'] = m, v
+        self._attach_ema(engine, old)
         self._ctl, self._ws = ops.guard_buffers(engine.flat_params.numel(), engine.flat_params.device)
         if self._pending_guard is not None:
             self._set_guard_counts(*self._pending_guard)
@@ -246,6 +276,25 @@ class FusedAdam(torch.optim.Optimizer):
         if ctr is not None:                       # a checkpoint loaded before any engine existed: resume its dropout stream position
             engine.step_counter = int(ctr)
             self._pending_counter = None
+
+    def _attach_ema(self, engine, old):
+        """the flat average and its compensation, with per-parameter views in the state: carried over where the old state has them (every
+        parameter's, or none: a partial average restarts), else the average starts from the parameters"""
+        for st in self.state.values():
+            st.pop('ema', None); st.pop('ema_c', None)
+        if self.param_groups[0].get('ema_decay') is None:
+            self.ema = self.ema_c = None
+            return
+        self.ema = engine.flat_params.clone()
+        self.ema_c = torch.zeros_like(engine.flat_params)
+        carried = all(p in old and 'ema' in old[p] and 'ema_c' in old[p] for _, p, _, _ in engine._bound)
+        if not carried:
+            self.ema_updates = 0
+        for (name, p, o, n) in engine._bound:
+            e, c = self.ema[o:o + n].view(p.shape), self.ema_c[o:o + n].view(p.shape)
+            if carried:
+                e.copy_(old[p]['ema']); c.copy_(old[p]['ema_c'])
+            self.state[p]['ema'], self.state[p]['ema_c'] = e, c
 
     def _find_engine(self):
         if self._model is not None:
@@ -261,11 +310,15 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._averaged:
+            raise HfttError('FusedAdam.step inside averaged_weights(): the model holds the averaged weights, leave the context first')
         self.attach(self._find_engine())
         g = self.param_groups[0]
         mp = self._group_map()
         self.step_count += 1
-        if not mp['trivial']:
+        if g.get('ema_decay') is not None:
+            self._step_ema(mp, grad_scale)
+        elif not mp['trivial']:
             self._step_groups(mp, grad_scale)
         elif self._guarded(g):
             mg = g.get('max_grad_norm')
@@ -296,6 +349,85 @@ class FusedAdam(torch.optim.Optimizer):
                              lr=[float(g['lr']) for g in groups] + [0.0] * extra,
                              weight_decay=[float(g.get('weight_decay', 0)) for g in groups] + [0.0] * extra, frozen=mp['frozen'], ctl=ctl,
                              beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'], grad_scale=grad_scale)
+
+    # ---- the averaged weights: the same three configurations through the one launch that also carries the average
+    @staticmethod
+    def _check_ema_decay(d):
+        if d is not None and not 0.0 <= float(d) < 1.0:           # (false for NaN too)
+            raise HfttError('FusedAdam: ema_decay=%r must be in [0, 1) (None: no averaged weights)' % (d,))
+
+    @staticmethod
+    def ema_decay_at(ema_decay, t, warmup=False):
+        """the decay of call t (0-based): ema_decay, or with warmup min(ema_decay, (1 + t) / (10 + t))"""
+        return min(float(ema_decay), (1.0 + t) / (10.0 + t)) if warmup else float(ema_decay)
+
+    def _step_ema(self, mp, grad_scale):
+        self._check_shared()
+        groups, g0, eng = self.param_groups, self.param_groups[0], self.engine
+        self._check_ema_decay(g0['ema_decay'])
+        extra = len(mp['frozen']) - len(groups)
+        ctl = None
+        if any(self._guarded(g) for g in groups):
+            mg = g0.get('max_grad_norm')
+            max_norm = math.inf if mg is None else float(mg)
+            if mp['trivial']:
+                ops.grad_norm(eng.flat_grads, self._ctl, self._ws, grad_scale=grad_scale, max_norm=max_norm)
+            else:
+                ops.grad_norm_groups(eng.flat_grads, mp['qmap'], mp['mask'], self._ctl, self._ws, grad_scale=grad_scale, max_norm=max_norm)
+            ctl = self._ctl
+        beta = self.ema_decay_at(g0['ema_decay'], self.ema_updates, g0.get('ema_warmup', False))
+        ops.adam_step_ema(eng.flat_params, eng.flat_grads, self.exp_avg, self.exp_avg_sq, self.ema, self.ema_c, self.step_count, beta,
+                          lr=[float(g['lr']) for g in groups] + [0.0] * extra, quad_group=None if mp['trivial'] else mp['qmap'],
+                          weight_decay=[float(g.get('weight_decay', 0)) for g in groups] + [0.0] * extra, frozen=mp['frozen'], ctl=ctl,
+                          beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'], grad_scale=grad_scale)
+        self.ema_updates += 1
+
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise HfttError('FusedAdam.%s: no averaged weights (build the optimizer with ema_decay= and attach it to an engine: a step, or a '
+                            'TrainStep)' % what)
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """The model holds the averaged weights inside the context and its own, bit for bit, after it.  The CONTENTS of the flat parameter
+        buffer and of the average are swapped (launch plans and descriptors hold device addresses), and the engine is told to prepare its
+        operands again on both sides.  ``step()`` inside is refused; the context does not nest."""
+        self._need_ema('averaged_weights')
+        if self._averaged:
+            raise HfttError('FusedAdam.averaged_weights does not nest')
+        self._swap_average()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._swap_average()
+            self._averaged = False
+
+    @torch.no_grad()
+    def _swap_average(self):
+        tmp = self.engine.flat_params.clone()
+        self.engine.flat_params.copy_(self.ema)
+        self.ema.copy_(tmp)
+        self.engine._prepared_frozen = False
+
+    def averaged_model(self, model=None):
+        """A CPU deep copy of the model (``model``, or the one given to the constructor) that holds the averaged weights: what
+        ``pickle.dump(model.cpu(), fh, protocol=4)`` would write had training ended on the average.  One device-to-host copy of the
+        average; the model on the device is not touched."""
+        self._need_ema('averaged_model')
+        model = self._model if model is None else model
+        if model is None or not hasattr(model, 'hftt_state'):
+            raise HfttError('FusedAdam.averaged_model: pass the model (the optimizer was built from its parameters alone)')
+        if self._averaged:
+            raise HfttError('FusedAdam.averaged_model inside averaged_weights(): the buffers are swapped, leave the context first')
+        bound = self.engine._bound
+        if any(a is not b for a, (_, b, _, _) in zip(model.parameters(), bound)):
+            raise HfttError('FusedAdam.averaged_model: the model is not the one whose parameters the optimizer holds')
+        avg = self.ema.cpu()
+        memo = {id(p): torch.nn.Parameter(avg[o:o + n].clone().view(p.shape), requires_grad=p.requires_grad) for _, p, o, n in bound}
+        twin = type(model).__new__(type(model))
+        twin.__setstate__(model.hftt_state(memo))
+        return twin.cpu()
 
     # ---- the guarded step: options in the parameter groups, the verdict and the counters in the device record
     @staticmethod
@@ -338,16 +470,23 @@ class FusedAdam(torch.optim.Optimizer):
         return self._guard_counts()[1]
 
     def state_dict(self):
+        if self._averaged:
+            raise HfttError('FusedAdam.state_dict inside averaged_weights(): parameters and average are swapped, leave the context first')
         sd = super().state_dict()
         sd['hftt_step_counter'] = None if self.engine is None else int(self.engine.step_counter)      # dropout stream position (resume)
         skipped, clipped = self._guard_counts()
         sd['hftt_guard'] = {'skipped': skipped, 'clipped': clipped}
+        g0 = self.param_groups[0]
+        sd['hftt_ema'] = {'decay': g0.get('ema_decay'), 'warmup': bool(g0.get('ema_warmup', False)), 'updates': int(self.ema_updates)}
         return sd
 
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         ctr = state_dict.pop('hftt_step_counter', None)
         guard = state_dict.pop('hftt_guard', None)   # absent in older checkpoints and in the reference's .dat
+        ema = state_dict.pop('hftt_ema', None)       # absent in checkpoints written before the averaged weights existed
+        if self._averaged:
+            raise HfttError('FusedAdam.load_state_dict inside averaged_weights(): leave the context first')
         super().load_state_dict(state_dict)          # torch's layout: state tensors are fresh copies, param_groups restored
         steps = [int(s['step']) for s in self.state.values() if 'step' in s]
         self.step_count = max(steps) if steps else 0
@@ -358,8 +497,17 @@ class FusedAdam(torch.optim.Optimizer):
                                 '(reference: optim.Adam(model.parameters(), lr), m_training.py:146)')
             for k in ('max_grad_norm', 'guard', 'frozen'):     # a state written without the options keeps the ones this optimizer was built with
                 g.setdefault(k, self.defaults[k])
+            # the averaged weights: a state that carries no average (no option, or the option unset) leaves the option as this optimizer was
+            # built -- the average then restarts from the parameters at attach; a state that carries one brings its option along
+            if g.get('ema_decay') is None:
+                g['ema_decay'], g['ema_warmup'] = self.defaults['ema_decay'], self.defaults['ema_warmup']
+            g.setdefault('ema_warmup', False)
+            self._check_ema_decay(g['ema_decay'])
+        has_avg = bool(self.state) and all('ema' in s and 'ema_c' in s for s in self.state.values())
+        self.ema_updates = int(ema['updates']) if (ema is not None and has_avg) else 0
         self._map = None
         eng, self.engine, self.exp_avg = self.engine, None, None
+        self.ema = self.ema_c = None
         self._pending_counter = None
         self._pending_guard = None if guard is None else (int(guard['skipped']), int(guard['clipped']))
         if eng is not None:

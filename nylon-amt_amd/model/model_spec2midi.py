@@ -102,14 +102,22 @@ class Model_SPEC2MIDI(nn.Module):
             eng._prepared_frozen = False         # new parameter values: prepare again
         return r
 
-    def __getstate__(self):
+    def hftt_state(self, memo=None):
+        """The module's state without the engine.  memo None: what pickling takes (__getstate__).  memo given (copy.deepcopy's: id(parameter)
+        -> its replacement): a deep copy of the whole state in which those parameters are replaced -- a twin of the module with other weights
+        (FusedAdam.averaged_model) without a clone of the present ones."""
         state = self.__dict__.copy()
         state.pop('_hftt', None)
         state.pop('_hftt_sync', None)
         state.pop('hftt_frozen_weights', None)
+        if memo is not None:
+            return copy.deepcopy(state, memo)
         # parameters are views into the engine's flat buffer: clone them out so each pickles its own storage
         state['_modules'] = copy.deepcopy(state['_modules'])
         return state
+
+    def __getstate__(self):
+        return self.hftt_state()
 
     def _apply(self, fn, recurse=True):
         r = super()._apply(fn, recurse)

@@ -117,17 +117,18 @@ def lr_at(step, lr, warmup=0, total=0, final_frac=1.0):
 
 
 def train_loop(model, clips, dev, precision, lr, steps=0, minutes=0.0, batch=8, seed=77, warmup=0, final_frac=1.0, clip=0.0, log_every=250,
-               on_step=None, tag='', guard=False, weight_decay=0.0, groups=None):
+               on_step=None, tag='', guard=False, weight_decay=0.0, groups=None, ema=None, ema_warmup=False):
     """the product's own training step until `steps` (or the time budget); returns (TrainStep, steps done, epochs started, loss curve, seconds).
     clip > 0 / guard / weight_decay > 0 are FusedAdam's max_grad_norm / guard / weight_decay: the same TrainStep call, a guarded optimizer.
     groups: keyword arguments of hftt_hip.trainer.stage_groups (fine-tuning: frozen stages, per-stage rates, no decay on 1-D tensors); every
-    group's rate follows the schedule from its own base rate."""
+    group's rate follows the schedule from its own base rate.  ema: FusedAdam's ema_decay (the averaged weights ride in the Adam launch;
+    ts.opt.averaged_model() holds them afterwards), ema_warmup its warm-up schedule."""
     from hftt_hip.trainer import FusedAdam, TrainStep, stage_groups
     model.hftt_precision = precision
     model.train()
     params = model if not groups else stage_groups(model, **groups)
     ts = TrainStep(model, optimizer=FusedAdam(params, lr=lr, max_grad_norm=clip if clip > 0.0 else None, guard=guard, weight_decay=weight_decay,
-                                              model=model))
+                                              model=model, ema_decay=ema, ema_warmup=ema_warmup))
     group = ts.opt.param_groups[0]
     base = [g['lr'] for g in ts.opt.param_groups]
     t0, step, epoch, curve = time.time(), 0, 0, []
@@ -238,6 +239,9 @@ def main():
     ap.add_argument('--aug-room-drr-db', type=float, nargs=2, metavar=('LO', 'HI'), default=None, help='with --aug-room-p: direct-to-reverberant ratio of the synthetic bank in dB, uniform (default 0 12)')
     ap.add_argument('--aug-room-taps', type=int, default=None, metavar='L', help='with --aug-room-p: taps of the synthetic bank (default 4096, at most 8192)')
     ap.add_argument('--aug-room-bank', default='', metavar='FILE.npz', help='with --aug-room-p: a bank of measured responses or equalisation filters instead (arrays ir [n, L] and taps [n])')
+    ap.add_argument('--ema', type=float, default=None, metavar='D', help='keep the exponential moving average of the weights inside the Adam launch, FusedAdam(ema_decay=D); '
+                    'both the raw and the averaged weights are scored, and --out saves the AVERAGED model (the raw one goes next to it as *_raw.pkl)')
+    ap.add_argument('--ema-warmup', action='store_true', help='with --ema, from scratch: the decay of call t is min(D, (1 + t) / (10 + t)), FusedAdam(ema_warmup=True)')
     ap.add_argument('--out', default='gpurun_out/config5_tiny.pkl')
     ap.add_argument('--score-only', default='', help='skip training: score this pickled model')
     ap.add_argument('--init', default='', help='start from this pickled model (weights only: the optimizer state starts afresh) -- chains runs that are each bounded by the GPU call limit')
@@ -293,6 +297,9 @@ def main():
     cfg = bench.CONFIGS[args.config]
     log = {'config': args.config, 'precision': args.precision}
     pkl = args.score_only
+    raw_pkl = ''
+    if args.ema_warmup and args.ema is None:
+        ap.error('--ema-warmup shapes the decay of --ema: give --ema D')
     if not pkl:
         # ---- corpus ----
         model = bench.build_model(cfg, args.seed, 0.1, 'cpu')
@@ -339,7 +346,8 @@ def main():
                     save_state(ts, step, args.save_state % step)
         ts, step, epoch, curve, secs = train_loop(model, clips, dev, args.precision, args.lr, steps=args.steps, minutes=args.minutes, batch=args.batch,
                                                    seed=args.seed, warmup=args.warmup, final_frac=args.final_frac, clip=args.clip, on_step=saver,
-                                                   guard=args.guard, weight_decay=args.weight_decay, groups=groups)
+                                                   guard=args.guard, weight_decay=args.weight_decay, groups=groups, ema=args.ema,
+                                                   ema_warmup=args.ema_warmup)
         if curve and curve[-1][1] != curve[-1][1]:
             log['diverged_at_step'] = step
         log['training'] = {'steps': step, 'epochs_started': epoch, 'seconds': round(secs, 1), 'lr': args.lr, 'warmup': args.warmup, 'final_frac': args.final_frac,
@@ -350,6 +358,14 @@ def main():
                            'clips_per_s': round(step * args.batch / secs, 1), 'loss_curve': curve[:: max(1, len(curve) // 24)]}
         model.eval()
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        if args.ema is not None:                  # --out holds the averaged weights, the raw iterate goes next to it: both are scored below
+            log['training']['ema'] = {'decay': args.ema, 'warmup': args.ema_warmup, 'updates': ts.opt.ema_updates}
+            averaged = ts.opt.averaged_model()
+            raw_pkl = os.path.splitext(args.out)[0] + '_raw.pkl'
+            with open(raw_pkl, 'wb') as fh:
+                pickle.dump(model.cpu(), fh, protocol=4)
+            model = averaged
+            log['checkpoint_raw'] = {'path': raw_pkl, 'bytes': os.path.getsize(raw_pkl)}
         with open(args.out, 'wb') as fh:
             pickle.dump(model.cpu(), fh, protocol=4)              # m_training.py:372-373
         pkl = args.out
@@ -368,6 +384,9 @@ def main():
                        'max_abs_posterior_difference': round(float(np.abs(mpe[mode] - mpe['parity']).max()), 6)}
     log['config5'] = {'workload': '60 s synthetic plucked-string audio (seed 1234) -> HIP log-mel -> %d clips -> AMT.transcript -> mpe2note, scored against the generating notes' % res['x3']['clips'],
                       'modes': res, 'agreement_with_parity_mode': agree}
+    if raw_pkl:                                   # the averaged weights were scored above (--out); the raw iterate in the default mode beside them
+        log['config5']['weights'] = 'averaged (ema_decay %g)' % args.ema
+        log['config5_raw'] = {'weights': 'raw iterate of the last step', 'modes': {'x3': score(raw_pkl, 'x3', dev, notes, wave, config)[0]}}
     print(json.dumps(log))
 
 
