@@ -1238,6 +1238,54 @@ typedef struct {
 } hftt_adam_ema_desc;
 int hftt_adam_step_ema(const hftt_adam_ema_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Class-balanced and focal criteria inside the fused loss (csrc/loss_w.hip; training/train.py:141-153 with the criteria exchanged):
+ * hftt_loss's pass with a per-pitch positive weight and a focal modulation on the six BCE heads, and class weights, ignore_index and label
+ * smoothing on the two velocity cross-entropies.  Two entry points ADDED at ABI 8; HFTT_ABI_VERSION stays 8, hftt_loss_desc keeps its
+ * layout and hftt_loss is untouched.
+ *
+ * BCE head h (the order of prob[6]), element i, pitch j = i mod Nn, posterior p, target y in [0, 1], a = pos_weight[h][j] > 0 (NULL: 1),
+ * g = gamma[h] (0, or in [1, 4]):
+ *     lp = max(log p, -100), l1p = max(log1p(-p), -100)                  (hftt_loss's clamps)
+ *     base = -(a y lp + (1 - y) l1p)          a weighs the positive part only: BCEWithLogitsLoss(pos_weight=)'s definition
+ *     m = |y - p|^g                           the soft-label focal factor (quality focal loss; g = 0: m = 1 exactly, no pow evaluated)
+ *     term_h = (1 / n) sum_i m base
+ *     d term_h / d p = m ((p - y) - (a - 1) y (1 - p)) / max((1 - p) p, 1e-12) - base g |y - p|^(g - 1) sign(y - p)        (sign(0) = 0)
+ * d_prob[h] carries weight_A|B * grad_scale / n as in hftt_loss.
+ *
+ * Velocity side s: logits z[i, :V], label c_i, w = class_weight[s] >= 0 (NULL: 1), e = smoothing[s] in [0, 1), k = ignore_index[s];
+ * q = softmax(z_i), ok_i = (c_i != k), W_s = sum_ok w[c_i]:
+ *     term_s = [ (1 - e) sum_ok w[c_i] (-log q[c_i]) + (e / V) sum_ok sum_c w[c] (-log q[c]) ] / W_s
+ *     d term_s / d z[i, c] = ok_i [ (1 - e) w[c_i] (q[c] - [c == c_i]) + (e / V) (q[c] sum_k w[k] - w[c]) ] / W_s
+ * which is torch.nn.functional.cross_entropy(weight=, ignore_index=, label_smoothing=, reduction='mean').  ONE deliberate deviation: when
+ * W_s == 0 (every row ignored or of weight zero) torch returns NaN; here the term and its gradient are 0, so that no NaN runs through the
+ * backward into an unguarded Adam.  A label outside [0, V) that is not k is the caller's error, as in hftt_loss (it is never used as an
+ * index).
+ *
+ * loss_out[0..8] as hftt_loss (the CE terms divided by W_s), loss_out[9] = W_A, loss_out[10] = W_B: loss_out holds ELEVEN floats.
+ * Launches: a label pre-pass that sums W_s in a fixed order (no float atomics: two runs are bit-identical), the main pass, the reduce.  The
+ * pre-pass is left out (W_s = n, two launches) when no side has class weights or an ignore_index inside [0, V).  The two forms of the main
+ * pass are hftt_loss's, chosen by its predicate (each compiled with and without the class-weight registers: a call without class weights
+ * and smoothing keeps hftt_loss's register budget).
+ * Neutrality, bit for bit: a head with pos_weight NULL or all ones and gamma 0 produces hftt_loss's bits in loss_out and d_prob[h]; a side
+ * with class_weight NULL, smoothing 0 and an ignore_index outside [0, V) produces hftt_loss's bits in loss_out and d_vel[s] -- whatever the
+ * other heads and sides of the same call are given.
+ * Refused in front of the launch: a null descriptor; what hftt_loss refuses; Nn <= 0; n % Nn != 0; a gamma that is neither 0 nor in [1, 4];
+ * a smoothing outside [0, 1); ws_w NULL when the pre-pass is needed.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {
+  hftt_loss_desc base;             /* as hftt_loss, but loss_out is [11] */
+  int32_t Nn; int32_t pad;         /* pitches: the period of the pos_weight tables, n % Nn == 0 */
+  const float* pos_weight[6];      /* device [Nn] per head, NULL: 1 */
+  float gamma[6];                  /* focal exponent per head: 0, or in [1, 4] */
+  const float* class_weight[2];    /* device [V] per side, NULL: 1 */
+  float smoothing[2];              /* label smoothing per side, in [0, 1) */
+  int64_t ignore_index[2];         /* per side; outside [0, V): nothing is ignored (torch's default is -100) */
+  float* ws_w;                     /* hftt_loss_w_ws_bytes(n): the pre-pass partials; may be NULL when no pre-pass is needed */
+} hftt_loss_w_desc;
+int64_t hftt_loss_w_ws_bytes(int64_t n);
+int hftt_loss_w(const hftt_loss_w_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

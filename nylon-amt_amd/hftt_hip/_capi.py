@@ -135,6 +135,13 @@ class LossDesc(C.Structure):
                 ('loss_out', c_f32p), ('ws', c_f32p)]
 
 
+class LossWDesc(C.Structure):               # hftt_loss_w_desc: the fused loss with pos_weight / focal BCE heads and weighted / smoothed / ignoring CE sides
+    _fields_ = [('base', LossDesc), ('Nn', C.c_int32), ('pad', C.c_int32),
+                ('pos_weight', c_f32p * 6), ('gamma', C.c_float * 6),
+                ('class_weight', c_f32p * 2), ('smoothing', C.c_float * 2), ('ignore_index', C.c_int64 * 2),
+                ('ws_w', c_f32p)]
+
+
 class LogmelDesc(C.Structure):
     _fields_ = [('wave', c_f32p), ('n_samples', C.c_int64),
                 ('n_fft', C.c_int32), ('hop', C.c_int32), ('n_mels', C.c_int32), ('n_frames', C.c_int32),
@@ -375,6 +382,8 @@ SIGNATURES = {
                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     'hftt_loss_ws_bytes': (C.c_int64, [C.c_int64]),
     'hftt_loss': (C.c_int, [C.POINTER(LossDesc), C.c_void_p]),
+    'hftt_loss_w_ws_bytes': (C.c_int64, [C.c_int64]),
+    'hftt_loss_w': (C.c_int, [C.POINTER(LossWDesc), C.c_void_p]),
     'hftt_adam_step': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32,
                                  C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     'hftt_logmel': (C.c_int, [C.POINTER(LogmelDesc), C.c_void_p]),

@@ -24,7 +24,7 @@ import os
 import torch
 
 from . import _capi
-from ._capi import FoldDesc, LossDesc, PrepEntry, StripPackEntry, check, lib
+from ._capi import FoldDesc, LossDesc, LossWDesc, PrepEntry, StripPackEntry, check, lib
 from .layout import PRECISION_NPASS, Options, WeightLayout, _align, flat_offsets, model_dims, precision_modes   # noqa: F401  (PRECISION_NPASS: re-export)
 from .plan import PlanBuilder, attn_fwd8_takes   # noqa: F401  (attn_fwd8_takes: re-export)
 
@@ -421,9 +421,11 @@ class HfttEngine:
                 start = end
 
     # ------------------------------------------------------------------ fused loss (training/train.py:141-153)
-    def loss(self, B, labels, weight_A=1.0, weight_B=1.0, with_grad=True):
+    def loss(self, B, labels, weight_A=1.0, weight_B=1.0, with_grad=True, spec=None):
         """labels: (onset, offset, mpe, velocity) device tensors [B,T,N] (fp32, fp32, fp32, int64).
-        Returns a [9] device tensor (total + 8 terms); with_grad fills the 'd.*' buffers."""
+        Returns a [9] device tensor (total + 8 terms); with_grad fills the 'd.*' buffers.
+        spec: None launches hftt_loss (the reference's criteria); a hftt_hip.criteria.LossSpec launches hftt_loss_w with its options
+        (the two velocity divisors W_A, W_B then follow the nine values in the same buffer, 'loss_out'[9:11])."""
         ws = self._ws[B]
         outs = ws['outs']
         b = ws['bufs']
@@ -435,7 +437,10 @@ class HfttEngine:
         for t, dt in ((lo, torch.float32), (lf, torch.float32), (lm, torch.float32), (lv, torch.int64)):
             if t.dtype != dt or not t.is_contiguous() or t.device != self.device or t.numel() != n:
                 raise _capi.HfttError('labels must be contiguous device tensors [B,T,N] (fp32,fp32,fp32,int64)')
-        dsc = LossDesc()
+        if spec is not None and (spec.Nn != self.N or spec.V != self.V):
+            raise _capi.HfttError('loss spec built for Nn=%d, V=%d; the model has Nn=%d, V=%d' % (spec.Nn, spec.V, self.N, self.V))
+        wdsc = LossWDesc() if spec is not None else None
+        dsc = LossDesc() if spec is None else wdsc.base
         dsc.n, dsc.V = n, self.V
         for i, k in enumerate((0, 1, 2, 5, 6, 7)):
             dsc.prob[i] = outs[k].data_ptr()
@@ -449,5 +454,11 @@ class HfttEngine:
         dsc.loss_out, dsc.ws = b['loss_out'].data_ptr(), b['loss_ws'].data_ptr()
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            check(self.lib.hftt_loss(C.byref(dsc), stream), 'loss')
+            if spec is None:
+                check(self.lib.hftt_loss(C.byref(dsc), stream), 'loss')
+            else:
+                if 'loss_w_ws' not in b:
+                    b['loss_w_ws'] = torch.empty(self.lib.hftt_loss_w_ws_bytes(n) // 4, dtype=torch.float32, device=self.device)
+                spec.fill(wdsc, b['loss_w_ws'])
+                check(self.lib.hftt_loss_w(C.byref(wdsc), stream), 'loss_w')
         return b['loss_out'][:9]

@@ -521,7 +521,7 @@ class FusedAdam(torch.optim.Optimizer):
 class TrainStep:
     """One object per (model, optimizer): ``loss = step(spec, onset, offset, mpe, velocity)``."""
 
-    def __init__(self, model, lr=1e-4, weight_A=1.0, weight_B=1.0, grad_sync=None, optimizer=None):
+    def __init__(self, model, lr=1e-4, weight_A=1.0, weight_B=1.0, grad_sync=None, optimizer=None, loss_spec=None):
         self.model = model
         self.engine = model.hftt_engine()
         self.opt = optimizer if optimizer is not None else FusedAdam(model, lr=lr)
@@ -532,6 +532,7 @@ class TrainStep:
             self.opt._pending_counter = None
         self.weight_A, self.weight_B = weight_A, weight_B
         self.grad_sync = grad_sync          # callable(flat_grads) -> None (DDP all-reduce), or None
+        self.loss_spec = loss_spec          # hftt_hip.criteria.LossSpec: the fused loss with its options (hftt_loss_w); None: the reference's criteria
         self._prune = 0                     # frozen stages of the last backward (flat_grads below its border was zeroed when it changed)
 
     def forward_backward(self, spec, label_onset, label_offset, label_mpe, label_velocity):
@@ -541,7 +542,7 @@ class TrainStep:
         B = spec.shape[0]
         with torch.cuda.device(eng.device):
             eng.forward(spec, training=self.model.training, save=True)
-            loss = eng.loss(B, (label_onset, label_offset, label_mpe, label_velocity), self.weight_A, self.weight_B, with_grad=True)
+            loss = eng.loss(B, (label_onset, label_offset, label_mpe, label_velocity), self.weight_A, self.weight_B, with_grad=True, spec=self.loss_spec)
             # fine-tuning: the backward stops where nothing trainable remains (FusedAdam.frozen_stages; other optimizers: the whole backward).
             # The pruned backward does not write flat_grads below the border: zeroed once per change, so that p.grad views read zeros
             k = self.opt.frozen_stages() if hasattr(self.opt, 'frozen_stages') else 0

@@ -3,10 +3,13 @@ MI355X HIP model.  Same call signatures and return values, so ``m_training.py`` 
 
 Two execution paths, same kernels underneath:
   * fast path -- when ``optimizer`` is ``hftt_hip.trainer.FusedAdam`` (Adam defaults of m_training.py:146) and the eight
-    criteria are the reference's (6x nn.BCELoss, 2x nn.CrossEntropyLoss, mean reduction): forward plan -> fused loss kernel
-    -> backward plan -> fused Adam on the flat parameter buffer, no autograd graph, no per-step host sync;
-  * compatibility path -- any other optimizer / criterion: the model's autograd.Function + torch criteria + ``optimizer.step()``
-    exactly as training/train.py:89-160 does.
+    criteria are ones the fused loss launch computes: forward plan -> fused loss kernel -> backward plan -> fused Adam on the
+    flat parameter buffer, no autograd graph, no per-step host sync.  The criteria: the reference's (6x nn.BCELoss, 2x
+    nn.CrossEntropyLoss, mean reduction: ``hftt_loss``), or any mix of plain ``nn.BCELoss()`` / ``hftt_hip.criteria.BalancedBCELoss``
+    (per-pitch positive weight, focal gamma) on the six BCE heads and ``nn.CrossEntropyLoss(weight=, ignore_index=,
+    label_smoothing=)`` with mean reduction on the two velocity heads (``hftt_loss_w``; the ``LossSpec`` is built once per call);
+  * compatibility path -- any other optimizer / criterion (an ``nn.BCELoss(weight=)``, another reduction, another class): the
+    model's autograd.Function + torch criteria + ``optimizer.step()`` exactly as training/train.py:89-160 does.
 ``valid(metrics=True)`` -- what an unchanged ``m_training.py`` calls at its last step by default (m_training.py:64,466-470) --
 scores every batch as train.py:193-200 does (``reshape_for_mir_eval`` :9-57 on onset_B / offset_B against the onset labels, a
 degenerate metric restated as it is) through ``evaluation.metrics`` (mir_eval is absent: parity unpinned at that library boundary),
@@ -23,7 +26,6 @@ import os
 import sys
 
 import torch
-import torch.nn as nn
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _PKG not in sys.path:
@@ -31,6 +33,7 @@ if _PKG not in sys.path:
 
 from hftt_hip._capi import HfttError           # noqa: E402
 from hftt_hip.trainer import FusedAdam, TrainStep   # noqa: E402
+from hftt_hip.criteria import LossSpec, reference_criteria   # noqa: E402
 from hftt_hip import ddp                        # noqa: E402
 from evaluation.metrics import reshape_for_mir_eval, transcription_evaluate   # noqa: E402
 
@@ -41,11 +44,15 @@ except Exception:      # pragma: no cover
         return x
 
 
-def _reference_criteria(cs):
-    a = cs[:4] + cs[4:]
-    return (all(isinstance(c, nn.BCELoss) and c.reduction == 'mean' and c.weight is None for c in (a[0], a[1], a[2], a[4], a[5], a[6]))
-            and all(isinstance(c, nn.CrossEntropyLoss) and c.reduction == 'mean' and c.weight is None and c.ignore_index == -100
-                    and c.label_smoothing == 0.0 for c in (a[3], a[7])))
+def _loss_spec(model, crits, device):
+    """(fast, spec): the reference's criteria -> (True, None); criteria hftt_loss_w computes -> (True, LossSpec); others -> (False, None)"""
+    if reference_criteria(crits):
+        return True, None
+    eng = model.hftt_engine()
+    spec = LossSpec.from_criteria(crits, eng.N, eng.V, device)
+    if spec is None or spec is False:
+        return spec is None, None
+    return True, spec
 
 
 def train(model, iterator, optimizer,
@@ -56,7 +63,7 @@ def train(model, iterator, optimizer,
     model.train()
     crits = (criterion_onset_A, criterion_offset_A, criterion_mpe_A, criterion_velocity_A,
              criterion_onset_B, criterion_offset_B, criterion_mpe_B, criterion_velocity_B)
-    fast = isinstance(optimizer, FusedAdam) and _reference_criteria(crits)
+    fast, spec = _loss_spec(model, crits, device) if isinstance(optimizer, FusedAdam) else (False, None)
     rank, world = ddp.rank_world()
     sync = None
     if world > 1:
@@ -72,7 +79,7 @@ def train(model, iterator, optimizer,
         if step is None or step.model is not model or step.engine is not model.hftt_engine():
             step = TrainStep(model, weight_A=weight_A, weight_B=weight_B, optimizer=optimizer, grad_sync=sync)
             optimizer._train_step = step
-        step.weight_A, step.weight_B, step.grad_sync = weight_A, weight_B, sync
+        step.weight_A, step.weight_B, step.grad_sync, step.loss_spec = weight_A, weight_B, sync, spec
     epoch_loss = torch.zeros((), device=device, dtype=torch.float64) if fast else 0
     n = 0
     for i, (input_spec, label_onset, label_offset, label_mpe, label_velocity) in tqdm(enumerate(iterator), total=len(iterator)):
@@ -138,7 +145,7 @@ def valid(model, iterator,
     precision = recall = f1 = 0.0
     crits = (criterion_onset_A, criterion_offset_A, criterion_mpe_A, criterion_velocity_A,
              criterion_onset_B, criterion_offset_B, criterion_mpe_B, criterion_velocity_B)
-    fast = _reference_criteria(crits)
+    fast, spec = _loss_spec(model, crits, device)
     epoch_loss = torch.zeros((), device=device, dtype=torch.float64) if fast else 0
     with torch.no_grad():
         for i, (input_spec, label_onset, label_offset, label_mpe, label_velocity) in enumerate(tqdm(iterator)):
@@ -160,7 +167,7 @@ def valid(model, iterator,
                 eng = model.hftt_engine()
                 loss9 = eng.loss(input_spec.shape[0], (label_onset.float().contiguous(), label_offset.float().contiguous(),
                                                        label_mpe.float().contiguous(), label_velocity.long().contiguous()),
-                                 weight_A, weight_B, with_grad=False)
+                                 weight_A, weight_B, with_grad=False, spec=spec)
                 epoch_loss += loss9[0].double()          # one host sync per epoch (train.py:252 syncs per batch)
                 continue
             oa, fa, ma, va, _att, ob, fb, mb, vb = out

@@ -22,6 +22,12 @@ noise and room options apply, warp and mix do not.  What is PLAYED varies instea
 --synth-tempo LO HI, --synth-shift, --synth-play-p P and --synth-duet-p P [--synth-duet-gain-db LO HI] (training.dataset.SynthPlay: every key,
 tuning, tempo and pairing of the note corpus, the labels rendered to match).
 
+Criteria: --onset-pos-weight A / --offset-pos-weight A / --mpe-pos-weight A (a positive-class weight on those BCE heads, A and B alike),
+--focal-gamma G (the soft-label focal factor |y - p|^G on all six), --velocity-silence-weight W (class 0, "no note", weighs W in the
+velocity cross-entropy, the others 1) and --label-smoothing E: hftt_hip.criteria.BalancedBCELoss / nn.CrossEntropyLoss(weight=,
+label_smoothing=) inside the fused loss launch (hftt_loss_w).  All default to neutral, and with all neutral the tool builds the reference's
+criteria (hftt_loss).
+
 Scoring (config 5): the seed-1234 minute -> log-mel -> 30 clips through AMT.transcript -> mpe2note -> note-F1 (onset, 50 ms) and frame-F1
 against the GENERATING notes, in x3, bf16 and parity mode, plus the frame-level agreement of the modes with each other.  One JSON line."""
 import argparse, json, math, os, pickle, sys, tempfile, time
@@ -103,6 +109,34 @@ def scale_position_embeddings_(model, scale):
                 p.mul_(scale)
 
 
+def add_loss_arguments(ap):
+    ap.add_argument('--onset-pos-weight', type=float, default=1.0, metavar='A', help='positive-class weight of the onset BCE heads, BalancedBCELoss(pos_weight=A) (1 = nn.BCELoss)')
+    ap.add_argument('--offset-pos-weight', type=float, default=1.0, metavar='A', help='positive-class weight of the offset BCE heads')
+    ap.add_argument('--mpe-pos-weight', type=float, default=1.0, metavar='A', help='positive-class weight of the mpe BCE heads')
+    ap.add_argument('--focal-gamma', type=float, default=0.0, metavar='G', help='soft-label focal factor |y - p|^G on the six BCE heads: 0 (off), or in [1, 4]')
+    ap.add_argument('--velocity-silence-weight', type=float, default=1.0, metavar='W', help='weight of velocity class 0 ("no note") in the cross-entropy, the other classes 1')
+    ap.add_argument('--label-smoothing', type=float, default=0.0, metavar='E', help='label smoothing of the velocity cross-entropy, in [0, 1)')
+
+
+def build_criteria(args, V=128):
+    """the eight criteria of training.train.train's order (onset, offset, mpe, velocity for A, then for B) from the criterion flags; all
+    neutral: the reference's 6x nn.BCELoss() + 2x nn.CrossEntropyLoss() (training/train.py:141-153)"""
+    import torch.nn as nn
+    from hftt_hip.criteria import BalancedBCELoss
+
+    def bce(a):
+        return nn.BCELoss() if a == 1.0 and args.focal_gamma == 0.0 else BalancedBCELoss(pos_weight=a, gamma=args.focal_gamma)
+
+    def ce():
+        w = None
+        if args.velocity_silence_weight != 1.0:
+            w = torch.ones(V)
+            w[0] = args.velocity_silence_weight
+        return nn.CrossEntropyLoss(weight=w, label_smoothing=args.label_smoothing)
+    side = lambda: [bce(args.onset_pos_weight), bce(args.offset_pos_weight), bce(args.mpe_pos_weight), ce()]      # noqa: E731
+    return tuple(side() + side())
+
+
 def lr_at(step, lr, warmup=0, total=0, final_frac=1.0):
     """learning rate of optimizer step `step` (1-based): linear warm-up from lr / warmup to lr over `warmup` steps, then constant, or -- with
     `total` and `final_frac` < 1 -- a half cosine from lr down to lr * final_frac at step `total` (held there afterwards).  This schedule is
@@ -117,18 +151,25 @@ def lr_at(step, lr, warmup=0, total=0, final_frac=1.0):
 
 
 def train_loop(model, clips, dev, precision, lr, steps=0, minutes=0.0, batch=8, seed=77, warmup=0, final_frac=1.0, clip=0.0, log_every=250,
-               on_step=None, tag='', guard=False, weight_decay=0.0, groups=None, ema=None, ema_warmup=False):
+               on_step=None, tag='', guard=False, weight_decay=0.0, groups=None, ema=None, ema_warmup=False, criteria=None):
     """the product's own training step until `steps` (or the time budget); returns (TrainStep, steps done, epochs started, loss curve, seconds).
     clip > 0 / guard / weight_decay > 0 are FusedAdam's max_grad_norm / guard / weight_decay: the same TrainStep call, a guarded optimizer.
     groups: keyword arguments of hftt_hip.trainer.stage_groups (fine-tuning: frozen stages, per-stage rates, no decay on 1-D tensors); every
     group's rate follows the schedule from its own base rate.  ema: FusedAdam's ema_decay (the averaged weights ride in the Adam launch;
-    ts.opt.averaged_model() holds them afterwards), ema_warmup its warm-up schedule."""
+    ts.opt.averaged_model() holds them afterwards), ema_warmup its warm-up schedule.  criteria: the eight criteria (build_criteria); None or
+    the reference's: hftt_loss, otherwise the fused loss with their options (hftt_loss_w) -- criteria it does not compute are an error here."""
+    from hftt_hip.criteria import LossSpec
     from hftt_hip.trainer import FusedAdam, TrainStep, stage_groups
     model.hftt_precision = precision
     model.train()
     params = model if not groups else stage_groups(model, **groups)
     ts = TrainStep(model, optimizer=FusedAdam(params, lr=lr, max_grad_norm=clip if clip > 0.0 else None, guard=guard, weight_decay=weight_decay,
                                               model=model, ema_decay=ema, ema_warmup=ema_warmup))
+    if criteria is not None:
+        spec = LossSpec.from_criteria(criteria, ts.engine.N, ts.engine.V, dev)
+        if spec is False:
+            raise ops.HfttError('train_loop: these criteria are not ones the fused loss computes (hftt_hip.criteria.LossSpec.from_criteria)')
+        ts.loss_spec = spec
     group = ts.opt.param_groups[0]
     base = [g['lr'] for g in ts.opt.param_groups]
     t0, step, epoch, curve = time.time(), 0, 0, []
@@ -242,6 +283,7 @@ def main():
     ap.add_argument('--ema', type=float, default=None, metavar='D', help='keep the exponential moving average of the weights inside the Adam launch, FusedAdam(ema_decay=D); '
                     'both the raw and the averaged weights are scored, and --out saves the AVERAGED model (the raw one goes next to it as *_raw.pkl)')
     ap.add_argument('--ema-warmup', action='store_true', help='with --ema, from scratch: the decay of call t is min(D, (1 + t) / (10 + t)), FusedAdam(ema_warmup=True)')
+    add_loss_arguments(ap)
     ap.add_argument('--out', default='gpurun_out/config5_tiny.pkl')
     ap.add_argument('--score-only', default='', help='skip training: score this pickled model')
     ap.add_argument('--init', default='', help='start from this pickled model (weights only: the optimizer state starts afresh) -- chains runs that are each bounded by the GPU call limit')
@@ -284,6 +326,12 @@ def main():
         ap.error('--aug-room-p / --aug-room-rt60 / --aug-room-drr-db / --aug-room-taps / --aug-room-bank act on the waveform: they need --wave-store')
     if room_synth and args.aug_room_bank:
         ap.error('--aug-room-bank supplies the responses: --aug-room-rt60 / --aug-room-drr-db / --aug-room-taps describe the synthetic bank')
+    try:
+        criteria = build_criteria(args, V=bench.CONFIGS[args.config].n_velocity)
+    except ValueError as e:
+        ap.error(str(e))
+    if not 0.0 <= args.label_smoothing < 1.0 or args.velocity_silence_weight < 0.0:
+        ap.error('--label-smoothing is in [0, 1) and --velocity-silence-weight is not negative')
     if args.freeze and not args.init:
         ap.error('--freeze keeps pretrained weights fixed: it needs --init')
     groups = None
@@ -347,11 +395,14 @@ def main():
         ts, step, epoch, curve, secs = train_loop(model, clips, dev, args.precision, args.lr, steps=args.steps, minutes=args.minutes, batch=args.batch,
                                                    seed=args.seed, warmup=args.warmup, final_frac=args.final_frac, clip=args.clip, on_step=saver,
                                                    guard=args.guard, weight_decay=args.weight_decay, groups=groups, ema=args.ema,
-                                                   ema_warmup=args.ema_warmup)
+                                                   ema_warmup=args.ema_warmup, criteria=criteria)
         if curve and curve[-1][1] != curve[-1][1]:
             log['diverged_at_step'] = step
         log['training'] = {'steps': step, 'epochs_started': epoch, 'seconds': round(secs, 1), 'lr': args.lr, 'warmup': args.warmup, 'final_frac': args.final_frac,
                            'clip': args.clip, 'guard': args.guard, 'weight_decay': args.weight_decay,
+                           'criteria': {'onset_pos_weight': args.onset_pos_weight, 'offset_pos_weight': args.offset_pos_weight, 'mpe_pos_weight': args.mpe_pos_weight,
+                                        'focal_gamma': args.focal_gamma, 'velocity_silence_weight': args.velocity_silence_weight,
+                                        'label_smoothing': args.label_smoothing, 'fused_launch': 'hftt_loss' if ts.loss_spec is None else 'hftt_loss_w'},
                            'groups': [{k: v for k, v in g.items() if k in ('stage', 'lr', 'weight_decay', 'frozen')} for g in ts.opt.param_groups] if groups else None,
                            'frozen_stages': ts.opt.frozen_stages(),
                            'skipped_steps': ts.opt.skipped_steps, 'clipped_steps': ts.opt.clipped_steps, 'pos_scale': args.pos_scale, 'batch': args.batch, 'dropout': 0.1, 'seed': args.seed,
