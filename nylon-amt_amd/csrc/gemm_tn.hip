@@ -9,6 +9,19 @@
 // pair feeds three MFMAs (lo.hi + hi.lo + hi.hi); npass 4 (bf16 halves) is what the weight gradients use (dY is a gradient).
 // M is split over workgroups; partial tiles go to a slab workspace and a second kernel reduces them in a fixed
 // order (bitwise reproducible; no float atomics).
+// Step schedules of the x3 forms (TnCfg::SCHED).  The reference loop runs a step in series: issue the next step's loads, the step's MFMAs,
+// wait for the loads, convert and write them to LDS, barrier -- and the two waves of a SIMD do each of these at the same time, so the
+// matrix pipe idles through the convert pass.  The split loop hands each of the step's 2 * TN MFMA groups its share of the next step's 16-byte
+// slots: convert, LDS write and (with one register set) the slot's refill are interleaved with the group's MFMAs, one MFMA to eight vector
+// operations.  HFTT_TN_PIPE=0 (read on every hftt_gemm_tn call) runs the reference loop, a kernel of its own (form 100 + npass).  What makes
+// the two bit-identical, and must stay so:
+//   * the same (tile, split) map and rows_per_split, the same slab and bias-slab writes, the same reduce kernels;
+//   * every accumulator receives the same MFMAs in the same order (token blocks ascending, s = 0, 1, small terms first): only loads, converts
+//     and LDS writes move, never an MFMA;
+//   * every thread's csum adds the same rows in the same order (steps ascending, a step's dY slots ascending);
+//   * masked (form 6) elements get the same hash indices (absolute row and column, whichever order the slots are converted in);
+//   * every prefetch is an unconditional load from a clamped, in-range address, up to two steps past the split's end; slots past the end are
+//     zeroed when they are consumed, so the extra step of an odd step count still multiplies zeros.
 #include <stdlib.h>
 #include "hftt_common.h"
 #include "x3_common.h"
@@ -89,12 +102,26 @@ struct TnCfg {
   static constexpr int XL = (BMT * XSPR + 511) / 512;
   static constexpr bool Y_EXACT = (BMT * YSPR) % 512 == 0;   // every thread owns a valid slot in every load round
   static constexpr bool X_EXACT = (BMT * XSPR) % 512 == 0;
+  // Staging schedule of the main loop (header comment).  0 = the reference x3 loop: one register set, loads one step ahead, converted and
+  // written to LDS in one pass behind the step's MFMAs.  2 = two sets, loads two steps ahead, the same write pass (bf16 and parity modes).
+  // 3 / 4 = the split x3 loop with one set / two sets.  The split loop runs on the 256-wide tiles where it fits the 256 registers without
+  // scratch: every 128 x 256 form, and the 256 x 256 forms of plain npass 4.  The masked and the fp16-pair 256 x 256 forms spill under it
+  // (8 .. 124 B per lane) and keep the reference loop, with the gradient-rounding form; so do the narrow tiles, which it slowed by 1 .. 3 %
+  // (profiles/tn_pipeline_ab.txt).
+  static constexpr int SCHED = !X3M ? 2 : TN != 4 ? 0 : TM == 1 ? 4 : NPASS == 4 ? 3 : 0;
 };
 
-template <int TM, int TN, int NPASS, bool DYB, bool XB>
+// Kernel form = npass (1 .. 6, above), + TN_REF for the x3 forms under the reference schedule (HFTT_TN_PIPE=0): a kernel of its own,
+// gemm_tn_kernel<TM, TN, 100 + npass, ..>, that the default kernels are compared against bit for bit (tests/test_tn_pipeline_gpu.py).
+constexpr int TN_REF = 100;
+
+template <int TM, int TN, int FORM, bool DYB, bool XB>
 __global__ __launch_bounds__(512) void gemm_tn_kernel(const hftt_gemm_tn_desc g, const int k_tiles, const int rows_per_split,
                                                      const long nws, const long kws, const int n_tiles_total, const int n_splits) {
+  constexpr int NPASS = FORM % TN_REF;
   using Cfg = TnCfg<TM, TN, NPASS, DYB, XB>;
+  constexpr int SCHED = (FORM >= TN_REF) ? 0 : Cfg::SCHED;
+  static_assert(FORM < TN_REF || Cfg::SCHED != 0, "a reference twin exists only where the default schedule differs from it");
   constexpr bool F32 = Cfg::F32, X3M = Cfg::X3M;
   constexpr int EX = X3M ? ((NPASS == 5 || NPASS == 6) ? 4 : NPASS) : X3_BF16;         // element type of the split
   constexpr bool DYH = (NPASS == 5);
@@ -150,14 +177,28 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const hftt_gemm_tn_desc g,
   const bool ycol_ok = ycol < g.N;                  // N % 8 == 0 when dY is bf16-stored, % 4 otherwise
   const int ycol_c = ycol_ok ? ycol : g.N - YE;
 
-  auto gload = [&](int step, uint4 (&yreg)[Cfg::YL], uint4 (&xreg)[Cfg::XL]) {
+  // slots q0 <= q < q1 of a step, counted over the YL dY slots and then the XL X slots (all of them: the default)
+  constexpr int NSLOT = Cfg::YL + Cfg::XL;
+  // split loop with fp32 dY: the same addresses in fewer vector operations (they are formed between the MFMAs): wave-uniform row 0 of the
+  // split, and the clamped row inside the split as a 32-bit number times the row pitch.  (With bf16 dY the 256 x 256 form spills under it.)
+  const unsigned char* ysplit = reinterpret_cast<const unsigned char*>(g.dY) + mbeg * g.lddy * (DYB ? 2 : 4);
+  const unsigned char* xsplit = reinterpret_cast<const unsigned char*>(g.X) + mbeg * g.ldx * (XB ? 2 : 4);
+  const long ypitch = g.lddy * (DYB ? 2 : 4), xpitch = g.ldx * (XB ? 2 : 4);
+  const int row_last = (int)(mend - mbeg) - 1;
+  auto gload = [&](int step, uint4 (&yreg)[Cfg::YL], uint4 (&xreg)[Cfg::XL], int q0 = 0, int q1 = Cfg::YL + Cfg::XL) __attribute__((always_inline)) {
     const long mb = mbeg + (long)step * BMT;
     int tid_g = tid;
     asm volatile("" : "+v"(tid_g));                  // (per-slot row / column offsets formed per call: hoisted out of the step loop they spill)
 #pragma unroll
     for (int j = 0; j < Cfg::YL; j++) {
+      if (j < q0 || j >= q1) continue;
       const int i = tid_g + 512 * j;
       const int row = i / YSPR;
+      if (SCHED >= 3 && !DYB) {
+        const int r = step * BMT + row;
+        yreg[j] = *reinterpret_cast<const uint4*>(ysplit + (long)(r < row_last ? r : row_last) * ypitch + ycol_c * (DYB ? 2 : 4));
+        continue;
+      }
       const long m = mb + row;
       // unconditional load from a clamped address (a branch around the load would make hipcc wait vmcnt(0) per load); slots that
       // do not exist are zeroed when the registers are consumed (sstore) -- a select right here would wait for each load in turn
@@ -166,12 +207,18 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const hftt_gemm_tn_desc g,
     }
 #pragma unroll
     for (int j = 0; j < Cfg::XL; j++) {
+      if (Cfg::YL + j < q0 || Cfg::YL + j >= q1) continue;
       const int i = tid_g + 512 * j;
       const int row = i / XSPR, cs = i % XSPR;
       const long m = mb + row;
       const int col = k0 + cs * XE;
       const long mc = m < mend ? m : mend - 1;
       const int cc = col < g.K ? col : g.K - XE;
+      if (SCHED >= 3 && !DYB) {
+        const int r = step * BMT + row;
+        xreg[j] = *reinterpret_cast<const uint4*>(xsplit + (long)(r < row_last ? r : row_last) * xpitch + cc * (XB ? 2 : 4));
+        continue;
+      }
       xreg[j] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(g.X) + (mc * g.ldx + cc) * (XB ? 2 : 4));
     }
   };
@@ -204,11 +251,12 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const hftt_gemm_tn_desc g,
     unsigned short* base = sm16 + buf * Cfg::BUF_ELEMS + which * Cfg::Y_ELEMS;
     *reinterpret_cast<uint4*>(base + off) = u;
   };
-  auto sstore = [&](int buf, int step, const uint4 (&yreg)[Cfg::YL], const uint4 (&xreg)[Cfg::XL]) {
+  auto sstore = [&](int buf, int step, const uint4 (&yreg)[Cfg::YL], const uint4 (&xreg)[Cfg::XL], int q0 = 0, int q1 = Cfg::YL + Cfg::XL) __attribute__((always_inline)) {
     const long mb = mbeg + (long)step * BMT;
     const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
     for (int j = 0; j < Cfg::YL; j++) {
+      if (j < q0 || j >= q1) continue;
       const int i = tid + 512 * j;
       const int row = i / YSPR;
       uint4 yv = (ycol_ok && mb + row < mend) ? yreg[j] : zero4;            // slots past the split / past N count as zeros
@@ -234,6 +282,7 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const hftt_gemm_tn_desc g,
     }
 #pragma unroll
     for (int j = 0; j < Cfg::XL; j++) {
+      if (Cfg::YL + j < q0 || Cfg::YL + j >= q1) continue;
       const int i = tid + 512 * j;
       const int row = i / XSPR, cs = i % XSPR;
       const uint4 xv = (k0 + cs * XE < g.K && mb + row < mend) ? xreg[j] : zero4;
@@ -253,15 +302,17 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const hftt_gemm_tn_desc g,
   // conditional block makes hipcc's s_waitcnt insertion fall back to vmcnt(0), which drained the two-steps-ahead prefetch.
   gload(0, yregA, xregA);
   sstore(0, 0, yregA, xregA);
-  if (!X3M) gload(1, yregB, xregB);
+  if (SCHED == 2 || SCHED == 4) gload(1, yregB, xregB);
+  if (SCHED == 3) gload(1, yregA, xregA);
   __syncthreads();
   // step s computes from LDS buffer (s&1); set `cur` (stored to LDS one step ago) is refilled with step s+2, set `nxt`
   // (holding step s+1, issued one step ago) is converted into the other LDS buffer after the MFMAs
   auto body = [&](int step, uint4 (&ycur)[Cfg::YL], uint4 (&xcur)[Cfg::XL], const uint4 (&ynxt)[Cfg::YL], const uint4 (&xnxt)[Cfg::XL]) {
     const int buf = step & 1;
-    // x3: ONE staging set, loads one step ahead (three times the MFMA work per step covers the latency; two sets on top of the 128
-    // accumulator registers and the hi / lo fragments of the 256 x 256 tile spilled)
-    gload(X3M ? step + 1 : step + 2, ycur, xcur);
+    // x3 with the 256 x 256 tile: ONE staging set (two sets on top of the 128 accumulator registers and the hi / lo fragments spilled).
+    // Reference loop: its loads run one step ahead (three times the MFMA work per step covers the latency).  Split loop with one set: the
+    // set holds step + 1 since the last step and is refilled slot by slot inside the MFMA groups below.
+    if (SCHED != 3) gload(SCHED == 0 ? step + 1 : step + 2, ycur, xcur);
     __builtin_amdgcn_sched_barrier(0);      // keep the loads up here: hipcc otherwise sinks them below the MFMAs (one step of cover, not two)
     if (F32) {
       const float* Ys = sm32 + buf * Cfg::BUF_ELEMS;
@@ -317,6 +368,22 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const hftt_gemm_tn_desc g,
             }
           }
           bh = nh; bl = nl;
+          if (SCHED >= 3) {
+            // split loop: this group's share of step + 1's slots is converted and written to the other LDS buffer (last read in step - 1,
+            // and every wave has passed a barrier since); with one set the slot's registers are refilled with step + 2 at once
+            constexpr int G = 2 * TN;
+            const int q0 = (s * TN + j) * NSLOT / G, q1 = (s * TN + j + 1) * NSLOT / G;
+            sstore(buf ^ 1, step + 1, ynxt, xnxt, q0, q1);
+            if (SCHED == 3) gload(step + 2, ycur, xcur, q0, q1);
+            // one MFMA, then eight of the staging's vector operations, and so on: a wave issues in order, so arithmetic placed behind the
+            // whole MFMA group starts only when the group's last MFMA has issued, and both waves of a SIMD would convert at the same time
+            constexpr int NM = TM * ((!DYB && !DYH ? 1 : 0) + (!XB ? 1 : 0) + 1);
+#pragma unroll
+            for (int k = 0; k < NM; k++) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+            }
+          }
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -344,11 +411,11 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const hftt_gemm_tn_desc g,
           for (int j = 0; j < TN; j++) acc[i][j] = mfma32(a[i], b[j], acc[i][j]);
       }
     }
-    sstore(buf ^ 1, step + 1, ynxt, xnxt);
+    if (SCHED == 0 || SCHED == 2) sstore(buf ^ 1, step + 1, ynxt, xnxt);
     __syncthreads();
   };
   for (int step = 0; step < nsteps; step += 2) {      // an odd step count runs one extra step on zeros
-    if (X3M) {
+    if (SCHED != 2 && SCHED != 4) {
       body(step, yregA, xregA, yregA, xregA);
       body(step + 1, yregA, xregA, yregA, xregA);
     } else {
@@ -487,25 +554,29 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_small_kernel(const hftt_ge
 }
 
 template <int TM, int TN, int NPASS, bool DYB, bool XB>
-int launch_tn(const hftt_gemm_tn_desc& d, const TnPlan& p, hipStream_t st) {
+int launch_tn(const hftt_gemm_tn_desc& d, const TnPlan& p, const bool ref, hipStream_t st) {
   using Cfg = TnCfg<TM, TN, NPASS, DYB, XB>;
   const int tiles = p.n_tiles * p.k_tiles;
   dim3 grid((unsigned)(((p.splits + 7) / 8) * 8 * tiles), 1, 1);
+  if constexpr (Cfg::X3M && Cfg::SCHED != 0)
+    if (ref)
+      return hftt_launch<gemm_tn_kernel<TM, TN, TN_REF + NPASS, DYB, XB>>("gemm_tn", grid, dim3(512), Cfg::LDS_BYTES, st, d, p.k_tiles, p.rows_per_split, p.nws,
+                                                                         p.kws, tiles, p.splits);
   return hftt_launch<gemm_tn_kernel<TM, TN, NPASS, DYB, XB>>("gemm_tn", grid, dim3(512), Cfg::LDS_BYTES, st, d, p.k_tiles, p.rows_per_split, p.nws, p.kws,
                                                              tiles, p.splits);
 }
 
 // the tile the plan chose, for one form of the kernel; form 6 (HFTT_TN_DY_DROP) exists for the two 256-wide tiles only
 template <int NPASS, bool DYB, bool XB>
-int launch_tn_tile(const hftt_gemm_tn_desc& d, const TnPlan& p, hipStream_t st) {
-  if (p.tm == 2) return launch_tn<2, 4, NPASS, DYB, XB>(d, p, st);
-  if (p.tn == 4) return launch_tn<1, 4, NPASS, DYB, XB>(d, p, st);
+int launch_tn_tile(const hftt_gemm_tn_desc& d, const TnPlan& p, const bool ref, hipStream_t st) {
+  if (p.tm == 2) return launch_tn<2, 4, NPASS, DYB, XB>(d, p, ref, st);
+  if (p.tn == 4) return launch_tn<1, 4, NPASS, DYB, XB>(d, p, ref, st);
   if constexpr (NPASS == 6) {
     hftt_set_error("gemm_tn: HFTT_TN_DY_DROP covers N >= 256 and K >= 256 (got N=%d K=%d)", d.N, d.K);
     return 1;
   } else {
-    if (p.tn == 2) return launch_tn<1, 2, NPASS, DYB, XB>(d, p, st);
-    return launch_tn<1, 1, NPASS, DYB, XB>(d, p, st);
+    if (p.tn == 2) return launch_tn<1, 2, NPASS, DYB, XB>(d, p, ref, st);
+    return launch_tn<1, 1, NPASS, DYB, XB>(d, p, ref, st);
   }
 }
 
@@ -544,26 +615,28 @@ extern "C" int hftt_gemm_tn(const hftt_gemm_tn_desc* d, void* stream) {
   const TnPlan p = tn_plan(d->M, d->N, d->K);
   int rc;
   const bool dyb = d->io_flags & HFTT_TN_DY_BF16, xb = d->io_flags & HFTT_TN_X_BF16;
+  const char* pipe = getenv("HFTT_TN_PIPE");          // read on every call: one process can run both schedules (tests/test_tn_pipeline_gpu.py)
+  const bool ref = pipe && pipe[0] == '0';
   if (d->npass == 3) {
-    rc = launch_tn_tile<3, false, false>(*d, p, st);
+    rc = launch_tn_tile<3, false, false>(*d, p, ref, st);
   } else if (d->npass == 4 && (d->io_flags & HFTT_TN_DY_HI) && !dyb) {
 #ifndef HFTT_GRAD_HI_BUILD
     hftt_set_error("gemm_tn: this library was built without the gradient-rounding option (HFTT_BUILD_GRAD_HI=1 python nylon-amt_amd/build.py)");
     return 1;
 #else
-    rc = xb ? launch_tn_tile<5, false, true>(*d, p, st) : launch_tn_tile<5, false, false>(*d, p, st);
+    rc = xb ? launch_tn_tile<5, false, true>(*d, p, ref, st) : launch_tn_tile<5, false, false>(*d, p, ref, st);
 #endif
   } else if (d->npass == 4 && (d->io_flags & HFTT_TN_DY_DROP)) {
     HFTT_REQUIRE(!dyb && d->lddy == d->N && d->drop_p >= 0.f && d->drop_p < 1.f, "gemm_tn: HFTT_TN_DY_DROP takes an fp32 dY with lddy == N and 0 <= drop_p < 1");
     HFTT_REQUIRE(d->M < (1 << 24) && d->N % 4 == 0 && (((int64_t)d->M * d->N) >> 2) < (1ll << 32), "gemm_tn: HFTT_TN_DY_DROP indexes the site with 32-bit quads (M < 2^24, M * N < 2^34)");
-    rc = xb ? launch_tn_tile<6, false, true>(*d, p, st) : launch_tn_tile<6, false, false>(*d, p, st);
+    rc = xb ? launch_tn_tile<6, false, true>(*d, p, ref, st) : launch_tn_tile<6, false, false>(*d, p, ref, st);
   } else if (d->npass == 4) {
-    rc = dyb ? launch_tn_tile<4, true, false>(*d, p, st) : (xb ? launch_tn_tile<4, false, true>(*d, p, st) : launch_tn_tile<4, false, false>(*d, p, st));
+    rc = dyb ? launch_tn_tile<4, true, false>(*d, p, ref, st) : (xb ? launch_tn_tile<4, false, true>(*d, p, ref, st) : launch_tn_tile<4, false, false>(*d, p, ref, st));
   } else if (d->npass == 2) {
-    rc = launch_tn_tile<2, false, false>(*d, p, st);
+    rc = launch_tn_tile<2, false, false>(*d, p, ref, st);
   } else {
-    rc = dyb ? (xb ? launch_tn_tile<1, true, true>(*d, p, st) : launch_tn_tile<1, true, false>(*d, p, st))
-             : (xb ? launch_tn_tile<1, false, true>(*d, p, st) : launch_tn_tile<1, false, false>(*d, p, st));
+    rc = dyb ? (xb ? launch_tn_tile<1, true, true>(*d, p, ref, st) : launch_tn_tile<1, true, false>(*d, p, ref, st))
+             : (xb ? launch_tn_tile<1, false, true>(*d, p, ref, st) : launch_tn_tile<1, false, false>(*d, p, ref, st));
   }
   if (rc != 0) return rc;
   const long total = (long)d->N * d->K_out;
