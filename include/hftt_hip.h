@@ -1286,6 +1286,47 @@ typedef struct {
 int64_t hftt_loss_w_ws_bytes(int64_t n);
 int hftt_loss_w(const hftt_loss_w_desc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Streaming resampler (csrc/resample_stream.hip): hftt_resample with its state carried forward, S streams in ONE launch -- the front end of
+ * audio that arrives in pieces at any rate.  One entry point ADDED at ABI 8; HFTT_ABI_VERSION stays 8 and hftt_resample keeps its descriptor
+ * and its results.
+ *
+ * The FIR has finite support: with up, down, width, taps of the kernel table above, output o reads input samples
+ * [(o / up) * down - width, + taps) and nothing else, summed in an order that depends on o % up alone.  So output o is final once input sample
+ * (o / up) * down + width + down - 1 has arrived, and a kernel that stages the same window from a carried tail produces the bits of the
+ * whole-file kernel.  Adopted as the definition: after n_in samples a live stream owns its first up * max(0, (n_in - width) / down) outputs
+ * (capped at ceil(n_in * up / down)), a closing stream all ceil(n_in * up / down); the added latency is (width + down) / sr_in.  The host
+ * keeps the counters (they are a function of what was pushed: nothing is read back) and, per stream, the input samples from
+ * (next_output / up) * down - width on -- fewer than taps + down of them.
+ *
+ * Per call the host packs every stream's [carried tail | new samples] into `wave` (fp32, or int16 when wave_i16: converted while it is staged as
+ * (float)s * (1.0f / 32768.0f)) and uploads ONE table, tab: DEVICE int64 [HFTT_RESAMPLE_STREAM_ROWS, S], row-major, per stream
+ *   row 0 in_off     where the stream's packed input begins inside `wave`
+ *   row 1 in_first   the absolute index, in the stream's own timeline, of its first packed sample
+ *   row 2 in_end     the absolute index one past the last sample present
+ *   row 3 closing    != 0: the stream ends with this call
+ *   row 4 out_first  the first output to produce            row 5 count   how many (0: nothing to do, the workgroups return at once)
+ *   row 6 out_pos    where inside `store` output out_first goes: outputs lie at out_pos .. out_pos + count
+ *   row 7 fill       closing only: that many zeros are written behind the last output -- up to the last sample the file's final log-mel frame
+ *                    reads, so that a kernel reading the slot sees the zeros the whole-file kernel takes from its bounds test
+ * Samples in front of absolute index 0 and at or beyond in_end are zeros; for a stream that is not closing the host never asks for an output
+ * whose window reaches in_end.  Grid (max(1, ceil(max_count / 256)), S); max_count = the largest count of the table, as the host knows it.
+ * Indices derived from the table are held inside [0, wave_len) and [0, store_len): a wrong table cannot leave the two buffers.
+ * Refused in front of the launch, each with its own text: a null descriptor or operand; S outside 1..65535; up or down <= 0; taps != 2 * width
+ * + down; max_count < 0; wave_i16 outside 0..1; negative wave_len / store_len; an LDS window of 256 outputs, ((255 / up + 1) * down + taps) * 4
+ * bytes, beyond 64 KB (hftt_resample's expression).
+ * --------------------------------------------------------------------------------------------- */
+#define HFTT_RESAMPLE_STREAM_ROWS 8
+typedef struct {
+  const void* wave; int64_t wave_len;        /* packed input of all streams, fp32 or int16; its samples */
+  const float* kernel;                   /* [up, taps] */
+  const int64_t* tab;                    /* DEVICE int64 [HFTT_RESAMPLE_STREAM_ROWS, S] */
+  float* store; int64_t store_len;       /* the resampled store (all slots); its samples */
+  int64_t max_count;
+  int32_t S, up, down, width, taps, wave_i16;
+} hftt_resample_stream_desc;
+int hftt_resample_stream(const hftt_resample_stream_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,8 +14,8 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 OBJDIR = os.path.join(HERE, 'build')
 LIB = os.path.join(LIBDIR, 'libhftt_hip.so')
-SOURCES = ['capi.cpp', 'gemm_nt.hip', 'strip_gemm.hip', 'strip_gemm2.hip', 'bs_strip.hip', 'gemm_tn.hip', 'attn_fwd.hip', 'attn_fwd8.hip', 'attn_bwd.hip', 'x3_attn.hip', 'x3_attn_pl.hip', 'x3_strip.hip', 'prep.hip', 'ln_bwd.hip', 'glue.hip', 'loss.hip', 'loss_w.hip', 'logmel.hip', 'notes.hip', 'notes_stream.hip', 'labels.hip', 'guard.hip', 'clip_logmel.hip', 'wave_warp.hip', 'clip_room.hip', 'clip_synth.hip', 'clip_synth_parts.hip']
-HEADERS = [os.path.join(CSRC, 'hftt_common.h'), os.path.join(CSRC, 'hftt_host.h'), os.path.join(CSRC, 'hftt_launch.h'), os.path.join(CSRC, 'strip_internal.h'), os.path.join(CSRC, 'strip_pipe.h'), os.path.join(CSRC, 'x3_common.h'), os.path.join(CSRC, 'x3_internal.h'), os.path.join(CSRC, 'x3_attn_bwd.h'), os.path.join(CSRC, 'small_strip.h'), os.path.join(CSRC, 'block_scan.h'), os.path.join(CSRC, 'wave_warp.h'), os.path.join(CSRC, 'clip_dry.h'), os.path.join(CSRC, 'logmel_frame.h'), os.path.join(CSRC, 'clip_synth_fn.h'),
+SOURCES = ['capi.cpp', 'gemm_nt.hip', 'strip_gemm.hip', 'strip_gemm2.hip', 'bs_strip.hip', 'gemm_tn.hip', 'attn_fwd.hip', 'attn_fwd8.hip', 'attn_bwd.hip', 'x3_attn.hip', 'x3_attn_pl.hip', 'x3_strip.hip', 'prep.hip', 'ln_bwd.hip', 'glue.hip', 'loss.hip', 'loss_w.hip', 'logmel.hip', 'resample_stream.hip', 'notes.hip', 'notes_stream.hip', 'labels.hip', 'guard.hip', 'clip_logmel.hip', 'wave_warp.hip', 'clip_room.hip', 'clip_synth.hip', 'clip_synth_parts.hip']
+HEADERS = [os.path.join(CSRC, 'hftt_common.h'), os.path.join(CSRC, 'hftt_host.h'), os.path.join(CSRC, 'hftt_launch.h'), os.path.join(CSRC, 'strip_internal.h'), os.path.join(CSRC, 'strip_pipe.h'), os.path.join(CSRC, 'x3_common.h'), os.path.join(CSRC, 'x3_internal.h'), os.path.join(CSRC, 'x3_attn_bwd.h'), os.path.join(CSRC, 'small_strip.h'), os.path.join(CSRC, 'block_scan.h'), os.path.join(CSRC, 'wave_warp.h'), os.path.join(CSRC, 'clip_dry.h'), os.path.join(CSRC, 'logmel_frame.h'), os.path.join(CSRC, 'resample_fir.h'), os.path.join(CSRC, 'clip_synth_fn.h'),
            os.path.join(HERE, '..', 'include', 'hftt_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wno-unused-result']
 

@@ -5,6 +5,7 @@
 #include "hftt_common.h"
 #include "hftt_launch.h"
 #include "logmel_frame.h"
+#include "resample_fir.h"
 #include "../../include/hftt_hip.h"
 
 namespace {
@@ -50,37 +51,17 @@ __global__ __launch_bounds__(256) void logmel_kernel(const hftt_logmel_desc g) {
 // signal) is staged in LDS once -- the tap loop has no bounds test and reads the window as LDS broadcasts -- and the loop runs four
 // independent accumulators, sixteen kernel-row loads in flight per lane (the row of a lane is its own 4 x taps bytes of the [up, taps] table,
 // L2-resident: <= 300 KB at 44.1 -> 16 kHz; the round-5 loop carried one dependent FMA and one bounds-tested load per tap: 1.3 ms per minute
-// of 44.1 kHz audio).
+// of 44.1 kHz audio).  The window staging and the tap loop are resample_fir.h's, shared with resample_stream_kernel (resample_stream.hip).
 __global__ __launch_bounds__(256) void resample_kernel(const hftt_resample_desc g) {
   extern __shared__ float win[];
   const int tid = threadIdx.x;
   const long o0 = (long)blockIdx.x * 256;
   const long olast = (o0 + 255 < g.n_out ? o0 + 255 : g.n_out - 1);
-  const long f0 = o0 / g.up, f1 = olast / g.up;
-  const long sbase = f0 * g.down - g.width;
-  const int wlen = (int)(f1 - f0) * g.down + g.taps;
-  for (int i = tid; i < wlen; i += 256) {
-    const long s = sbase + i;
-    win[i] = (s >= 0 && s < g.n_in) ? g.wave[s] : 0.f;
-  }
-  __syncthreads();
+  const resample_win wn = resample_window(o0, olast, g.up, g.down, g.width, g.taps);
+  resample_stage(win, wn, tid, [&](long s) { return (s >= 0 && s < g.n_in) ? g.wave[s] : 0.f; });
   const long o = o0 + tid;
   if (o >= g.n_out) return;
-  const long f = o / g.up;
-  const int ph = (int)(o - f * g.up);
-  const float* k = g.kernel + (long)ph * g.taps;
-  const float* w = win + (int)(f - f0) * g.down;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  int t = 0;
-#pragma unroll 4
-  for (; t + 4 <= g.taps; t += 4) {
-    a0 = fmaf(w[t], k[t], a0);
-    a1 = fmaf(w[t + 1], k[t + 1], a1);
-    a2 = fmaf(w[t + 2], k[t + 2], a2);
-    a3 = fmaf(w[t + 3], k[t + 3], a3);
-  }
-  for (; t < g.taps; t++) a0 = fmaf(w[t], k[t], a0);
-  g.out[o] = (a0 + a1) + (a2 + a3);
+  g.out[o] = resample_taps(win, wn, g.kernel, o, g.up, g.down, g.taps);
 }
 
 }  // namespace

@@ -157,6 +157,15 @@ class ResampleDesc(C.Structure):
                 ('out', c_f32p), ('n_out', C.c_int64)]
 
 
+RESAMPLE_STREAM_ROWS = 8                    # HFTT_RESAMPLE_STREAM_ROWS
+
+
+class ResampleStreamDesc(C.Structure):      # hftt_resample_stream_desc: S streams' packed input, the per-stream device table, the resampled store
+    _fields_ = [('wave', C.c_void_p), ('wave_len', C.c_int64), ('kernel', c_f32p), ('tab', C.c_void_p),
+                ('store', c_f32p), ('store_len', C.c_int64), ('max_count', C.c_int64),
+                ('S', C.c_int32), ('up', C.c_int32), ('down', C.c_int32), ('width', C.c_int32), ('taps', C.c_int32), ('wave_i16', C.c_int32)]
+
+
 STITCH_MAX_CLIPS = 64                       # HFTT_STITCH_MAX_CLIPS
 NOTES_CHUNK = 256                           # HFTT_NOTES_CHUNK
 
@@ -414,6 +423,7 @@ SIGNATURES = {
     'hftt_adam_step_groups': (C.c_int, [C.POINTER(AdamGroupsDesc), C.c_void_p]),
     'hftt_grad_norm_groups': (C.c_int, [c_f32p, C.c_int64, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hftt_adam_step_ema': (C.c_int, [C.POINTER(AdamEmaDesc), C.c_void_p]),
+    'hftt_resample_stream': (C.c_int, [C.POINTER(ResampleStreamDesc), C.c_void_p]),
 }
 
 _lib = None

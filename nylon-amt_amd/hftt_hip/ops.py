@@ -10,7 +10,7 @@ import math
 import numpy as np
 import torch
 
-from ._capi import (ADAM_MAX_GROUPS, AdamEmaDesc, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipRoomDesc, ClipSynthDesc, ClipSynthPartsDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
+from ._capi import (ADAM_MAX_GROUPS, AdamEmaDesc, AdamGroupsDesc, AttnDesc, ClipLogmelDesc, ClipLogmelMixDesc, ClipLogmelMixWarpDesc, ClipLogmelWarpDesc, ClipMixArgs, ClipRoomDesc, ClipSynthDesc, ClipSynthPartsDesc, ClipWindowsDesc, FfnDesc, GemmNtDesc, GemmTnDesc, HfttError, LabelNote, LabelsDesc, LabelsMixDesc, LabelsWarpDesc, LnBwdDesc, LogmelDesc, LossDesc, NotesDesc, NotesSegDesc, NotesStreamDesc, ResampleDesc, ResampleStreamDesc, PrepEntry, StitchDesc, StripDesc, StripPackEntry, WarpArgs, WaveWarpDesc,
                     WARP_DELAY_MAX, WARP_STEP_MAX, WARP_STEP_MIN, WARP_TABLE_L, WARP_TABLE_LEN, WARP_ZEROS,
                     LABELS_STORE, LABELS_TRAIN, NOTES_CHUNK, ROOM_MAX_TAPS, STITCH_MAX_CLIPS, SYNTH_MAX_PARTIALS,
                     SL_C_BF16, SL_C_F16PAIR, SL_H_BF16, SL_PRE_BF16, SL_RELU, SL_X3_GRAD_HI, SL_RES_BF16, SL_X_BF16, SL_X3_F16, SL_X3_BF16, SL_X_DROP,
@@ -632,13 +632,18 @@ class LogMel:
         return feat
 
 
+def resample_geometry(sr_in, sr_out, lowpass_filter_width=6, rolloff=0.99):
+    """(up, down, width) of resample_kernel_table without the table: taps = 2 * width + down"""
+    g = math.gcd(int(sr_in), int(sr_out))
+    down, up = int(sr_in) // g, int(sr_out) // g
+    return up, down, math.ceil(lowpass_filter_width * down / (min(down, up) * rolloff))
+
+
 def resample_kernel_table(sr_in, sr_out, lowpass_filter_width=6, rolloff=0.99):
     """(kernel [up, taps] float64 tensor, up, down, width) of torchaudio.transforms.Resample's defaults (Hann-windowed sinc): the published
     algorithm restated (torchaudio is absent: parity unpinned at that boundary)."""
-    g = math.gcd(int(sr_in), int(sr_out))
-    down, up = int(sr_in) // g, int(sr_out) // g
+    up, down, width = resample_geometry(sr_in, sr_out, lowpass_filter_width, rolloff)
     base = min(down, up) * rolloff
-    width = math.ceil(lowpass_filter_width * down / base)
     idx = torch.arange(-width, width + down, dtype=torch.float64)[None, :] / down
     t = (torch.arange(0, -up, -1, dtype=torch.float64)[:, None] / up + idx) * base
     t = t.clamp(-lowpass_filter_width, lowpass_filter_width)
@@ -669,6 +674,306 @@ def resample(wave_mono, sr_in, sr_out):
     d.out, d.n_out = out.data_ptr(), n_out
     check(lib().hftt_resample(C.byref(d), _stream(wave.device)), 'resample')
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# the front end of audio that arrives in pieces (hftt_resample_stream; include/hftt_hip.h: streaming resampler)
+def resample_stream_plan(n_in, n_done, up, down, width, closing):
+    """What a stream that has received n_in input samples and produced n_done outputs does now -> (first output, count, first input sample
+    to retain).  Pure host arithmetic, no device.  Output o reads inputs [(o / up) * down - width, + 2 * width + down): a live stream owns its
+    first up * max(0, (n_in - width) // down) outputs (capped at ceil(n_in * up / down)), a closing one all ceil(n_in * up / down); the next
+    output's window begins at (next / up) * down - width, clamped at 0 (and at n_in: nothing is kept that has not arrived)."""
+    n_in, n_done, up, down, width = int(n_in), int(n_done), int(up), int(down), int(width)
+    total = -(-n_in * up // down)
+    ready = total if closing else min(total, up * max(0, (n_in - width) // down))
+    count = max(0, ready - n_done)
+    nxt = n_done + count
+    return n_done, count, min(n_in, max(0, (nxt // up) * down - width))
+
+
+def resample_stream_lds(up, down, width):
+    """bytes of LDS that 256 outputs' input window takes (hftt_resample's and hftt_resample_stream's expression): refused beyond 64 KB"""
+    return ((255 // int(up) + 1) * int(down) + 2 * int(width) + int(down)) * 4
+
+
+def _segments(starts, lengths, device, extra=None):
+    """flat indices of the segments starts[k] .. + lengths[k], concatenated, as a device int64 tensor (and `extra`[k] repeated over segment
+    k): one small upload and three launches, whatever the number of segments"""
+    lengths = np.asarray(lengths, np.int64)
+    total = int(lengths.sum())
+    off = np.concatenate([[0], np.cumsum(lengths)[:-1]])
+    rows = [np.asarray(starts, np.int64) - off] + ([np.asarray(extra, np.int64)] if extra is not None else [])
+    tab = torch.from_numpy(np.stack(rows + [lengths])).to(device)
+    rep = torch.repeat_interleave(tab[:-1], tab[-1], dim=1, output_size=total)
+    idx = rep[0] + torch.arange(total, device=device)
+    return (idx, rep[1]) if extra is not None else idx
+
+
+def _put_segments(flat, starts, lengths, src):
+    """flat[starts[k] .. + lengths[k]] = the k-th piece of src (the pieces concatenated): one indexed copy whatever the number of segments;
+    one or two segments are plain slice copies, without the index table"""
+    if len(starts) <= 2:
+        o = 0
+        for st, n in zip(starts, lengths):
+            flat[st:st + n].copy_(src[o:o + n])
+            o += n
+    else:
+        flat.index_copy_(0, _segments(starts, lengths, flat.device), src)
+
+
+class ResampleStream:
+    """The carried state of ``resample_stream`` for S streams at one input rate on one device: the kernel table (the _RESAMPLE_TABLES
+    cache), the per-stream counters ON THE HOST (n_in samples received, n_done outputs produced, in0 the first retained input sample: a
+    function of what was pushed, nothing is read back), the retained input tails (device, int16 or fp32, fewer than taps + down samples
+    each) and the resampled store: fp32 [S, slot_len], slot s holds stream s's samples at sr_out from absolute index base[s] (a multiple of
+    hop) on.  ``stream_logmel`` reads the store as S pseudo-files (``table``: a WetTable over the store, no copy), releases the frames that
+    are complete and slides the slots, so that a slot never holds more than n_fft + hop samples behind a push; slot_len grows to the
+    largest push seen (or is fixed by the caller with slot_len= / store=), never with the stream's age.  sr_in == sr_out: no kernel table
+    and no resample launch, the samples go into the same store unchanged."""
+
+    def __init__(self, S, sr_in, sr_out, device, n_fft=2048, hop=256, slot_len=None, store=None):
+        self.S, self.sr_in, self.sr_out = int(S), int(sr_in), int(sr_out)
+        self.n_fft, self.hop = int(n_fft), int(hop)
+        if self.S < 1 or self.sr_in < 1 or self.sr_out < 1 or self.hop < 1 or self.n_fft < 2:
+            raise HfttError('ResampleStream: S=%d streams from rate %d to rate %d (n_fft=%d, hop=%d)' % (self.S, self.sr_in, self.sr_out, self.n_fft, self.hop))
+        same = self.sr_in == self.sr_out
+        self.up, self.down, self.width = (1, 1, 0) if same else resample_geometry(self.sr_in, self.sr_out)
+        self.taps = 2 * self.width + self.down
+        if not same and resample_stream_lds(self.up, self.down, self.width) > 64 * 1024:
+            raise HfttError('ResampleStream: input rate %d -> %d: the input window of one workgroup (down = %d, taps = %d) exceeds 64 KB of LDS'
+                            % (self.sr_in, self.sr_out, self.down, self.taps))
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise HfttError('ResampleStream: a ROCm device is required (got %s); there is no CPU fallback' % self.device)
+        self.kernel = None
+        if not same:
+            key = (self.sr_in, self.sr_out, str(self.device))
+            if key not in _RESAMPLE_TABLES:
+                kern = resample_kernel_table(self.sr_in, self.sr_out)[0]
+                _RESAMPLE_TABLES[key] = (kern.float().contiguous().to(self.device), self.up, self.down, self.width)
+            self.kernel = _RESAMPLE_TABLES[key][0]
+        S = self.S
+        self.n_in, self.n_done, self.in0, self.closed = [0] * S, [0] * S, [0] * S, [False] * S
+        self.base, self.frames = [0] * S, [0] * S                 # slot position 0 in the stream's output timeline; log-mel frames released
+        self.tail = [None] * S                                    # retained input samples in0 .. n_in (device, 1-d) or None
+        self.fixed = store is not None or slot_len is not None
+        if store is not None:
+            _need_cuda(store)
+            if store.dtype != torch.float32 or store.dim() != 2 or store.shape[0] != S or not store.is_contiguous():
+                raise HfttError('ResampleStream: store must be a contiguous fp32 [S, slot_len] device tensor')
+            self.store = store
+        else:
+            self.store = torch.zeros(S, int(slot_len) if slot_len is not None else self.n_fft + 2 * self.hop, dtype=torch.float32, device=self.device)
+        self._zeros = torch.zeros(self.n_fft, dtype=torch.float32, device=self.device)
+        self._tabled = None
+
+    @property
+    def slot_len(self):
+        return self.store.shape[1]
+
+    def table(self):
+        """the store as clip_logmel reads a corpus: S pseudo-files of slot_len fp32 samples (a WetTable over the store itself)"""
+        if self._tabled is None or self._tabled.wave is not self.store:
+            samp0 = torch.arange(self.S + 1, dtype=torch.int64, device=self.device) * self.slot_len
+            self._tabled = WetTable(self.store, samp0)
+            self._tabled.device = self.device                    # as the caller named it ('cuda' and 'cuda:0' do not compare equal), as a WaveTable does
+        return self._tabled
+
+    def _room(self, need):
+        """slot_len >= need: a larger store (the old slots copied) unless the caller fixed it"""
+        if need <= self.slot_len:
+            return
+        if self.fixed:
+            raise HfttError('resample_stream: a push needs %d samples per slot, the store has slot_len=%d' % (need, self.slot_len))
+        new = torch.zeros(self.S, _align(need, 1024), dtype=torch.float32, device=self.device)
+        new[:, :self.slot_len].copy_(self.store)
+        self.store = new
+
+    def read(self, s, first, count):
+        """outputs first .. first + count of stream s as they lie in the store (a copy; they must not have been slid out)"""
+        p = first - self.base[s]
+        if p < 0 or p + count > self.slot_len:
+            raise HfttError('ResampleStream.read: outputs %d .. %d of stream %d are not in its slot (base %d)' % (first, first + count, s, self.base[s]))
+        return self.store[s, p:p + count].clone()
+
+    def fill_of(self, n_out):
+        """zeros behind the last sample of a closed file of n_out samples: up to the last sample its final frame n_out // hop reads"""
+        return (n_out // self.hop) * self.hop + self.n_fft // 2 - n_out
+
+
+def resample_stream(state, chunks, closing=None):
+    """The one call of the streaming front end: chunks[s] = new samples of stream s at state.sr_in (1-d, int16 or floating point, host or
+    device; None: nothing), closing[s]: the stream ends with this call.  Plans all streams (resample_stream_plan), uploads the per-stream
+    table in ONE copy and launches hftt_resample_stream ONCE: every stream's new outputs go behind its earlier ones in its slot of
+    state.store, a closing stream's zero tail with them.  int16 is converted by the kernel, (float)s * (1 / 32768) -- unless some stream
+    brings floating point in the same call, then the int16 pieces are converted here, to the same values.  sr_in == sr_out: no launch, one
+    indexed copy into the store.  -> [(first output, count)] per stream; nothing is read back."""
+    if not isinstance(state, ResampleStream):
+        raise HfttError('resample_stream: the first argument is an ops.ResampleStream')
+    S, dev = state.S, state.device
+    chunks = list(chunks)
+    closing = [False] * S if closing is None else [bool(c) for c in closing]
+    if len(chunks) != S or len(closing) != S:
+        raise HfttError('resample_stream: %d chunks / %d closing flags for %d streams' % (len(chunks), len(closing), S))
+    new = [None] * S
+    for s, w in enumerate(chunks):
+        if w is None:
+            continue
+        w = torch.as_tensor(w)
+        if w.dim() != 1:
+            raise HfttError('resample_stream: stream %d: samples are 1-d (mono), got shape %s' % (s, tuple(w.shape)))
+        if w.dtype != torch.int16 and not w.dtype.is_floating_point:
+            raise HfttError('resample_stream: stream %d: samples are int16 or floating point, got %s' % (s, w.dtype))
+        if w.numel() == 0:
+            continue
+        if state.closed[s]:
+            raise HfttError('resample_stream: stream %d is closed' % s)
+        new[s] = w
+    for s in range(S):
+        if closing[s] and state.closed[s]:
+            raise HfttError('resample_stream: stream %d is closed already' % s)
+    live = [s for s in range(S) if new[s] is not None or closing[s]]
+    if not live:
+        return [(state.n_done[s], 0) for s in range(S)]
+    # the pieces on the device, in one dtype: int16 only when every piece of the launch is int16
+    pieces = [t for t in new if t is not None] + [state.tail[s] for s in range(S) if state.tail[s] is not None and state.tail[s].numel()]
+    i16 = state.kernel is not None and len(pieces) > 0 and all(t.dtype == torch.int16 for t in pieces)
+
+    def conv(t):
+        if i16:
+            return t
+        return t.float() * (1.0 / 32768.0) if t.dtype == torch.int16 else t.float()
+    host = [s for s in range(S) if new[s] is not None and new[s].device.type != 'cuda']
+    if host:                                            # the host chunks travel in ONE copy
+        if len({new[s].dtype for s in host}) == 1:
+            sent = (torch.cat([new[s] for s in host]) if len(host) > 1 else new[host[0]]).to(dev)
+            o = 0
+            for s in host:
+                n = new[s].numel()
+                new[s] = sent[o:o + n]
+                o += n
+        else:
+            for s in host:
+                new[s] = new[s].to(dev)
+    # the plan of every stream
+    plan, parts, rows = [], [], np.zeros((8, S), np.int64)
+    off = 0
+    for s in range(S):
+        n_new = new[s].numel() if new[s] is not None else 0
+        state.n_in[s] += n_new
+        first, count, keep = resample_stream_plan(state.n_in[s], state.n_done[s], state.up, state.down, state.width, closing[s])
+        fill = state.fill_of(first + count) if closing[s] else 0
+        plan.append((first, count, keep, fill))
+        length = state.n_in[s] - state.in0[s]
+        if state.tail[s] is not None and state.tail[s].numel():
+            parts.append(conv(state.tail[s]))
+        if new[s] is not None:
+            parts.append(conv(new[s]))
+        rows[:, s] = (off, state.in0[s], state.n_in[s], int(closing[s]), first, count, 0, fill)
+        off += length
+    state._room(max(p[0] - state.base[s] + p[1] + p[3] for s, p in enumerate(plan)))
+    L = state.slot_len
+    for s, p in enumerate(plan):
+        rows[6, s] = s * L + p[0] - state.base[s]
+    packed = torch.cat(parts) if len(parts) > 1 else (parts[0] if parts else None)
+    max_count = max(p[1] for p in plan)
+    if state.kernel is None:
+        # equal rates: outputs are the inputs; the new samples and a closing stream's zeros in one indexed copy
+        src, starts, lens = [], [], []
+        o = 0
+        for s, (first, count, keep, fill) in enumerate(plan):
+            length = state.n_in[s] - state.in0[s]
+            if count:
+                src.append(packed[o + length - count:o + length])
+            if fill:
+                src.append(state._zeros[:fill] if fill <= state._zeros.numel() else torch.zeros(fill, device=dev))
+            if count + fill:
+                starts.append(int(rows[6, s])); lens.append(count + fill)
+            o += length
+        if src:
+            _put_segments(state.store.view(-1), starts, lens, torch.cat(src) if len(src) > 1 else src[0])
+    elif max_count > 0 or any(p[3] for p in plan):
+        if packed is None:                              # (a close of streams that hold nothing: a pointer that is only non-null)
+            packed = state._zeros[:1]
+        tab = torch.from_numpy(rows).to(dev)
+        d = ResampleStreamDesc()
+        d.wave, d.wave_len, d.kernel, d.tab = packed.data_ptr(), (packed.numel() if parts else 0), state.kernel.data_ptr(), tab.data_ptr()
+        d.store, d.store_len, d.max_count = state.store.data_ptr(), state.store.numel(), max_count
+        d.S, d.up, d.down, d.width, d.taps, d.wave_i16 = S, state.up, state.down, state.width, state.taps, int(i16)
+        check(lib().hftt_resample_stream(C.byref(d), _stream(dev)), 'resample_stream')
+    # the counters, and the tails as views of this call's packed input
+    out, o = [], 0
+    for s, (first, count, keep, fill) in enumerate(plan):
+        length = state.n_in[s] - state.in0[s]
+        state.n_done[s] = first + count
+        state.closed[s] = state.closed[s] or closing[s]
+        if state.closed[s]:                             # nothing of a closed stream is read again
+            keep = state.n_in[s]
+        state.tail[s] = packed[o + keep - state.in0[s]:o + length] if keep < state.n_in[s] else None
+        state.in0[s] = keep
+        out.append((first, count))
+        o += length
+    return out
+
+
+def stream_frames_plan(n_done, frames, closed, hop, n_fft):
+    """log-mel frames first .. end that a stream with n_done resampled samples completes: frame t once samples through t * hop + n_fft / 2
+    - 1 exist; a closed stream all 1 + n_done // hop.  -> (first, end), end >= first.  Pure host arithmetic."""
+    end = 1 + n_done // hop if closed else ((n_done - n_fft // 2) // hop + 1 if n_done >= n_fft // 2 else 0)
+    return frames, max(frames, end)
+
+
+def stream_logmel(state, logmel):
+    """The log-mel frames that the streams of `state` (an ops.ResampleStream) have completed since the last call, ALL streams in ONE
+    hftt_clip_logmel launch over the resampled store: every stream's new frames are requested as windows of HFTT_CLIP_LOGMEL_RUN = 16 frames
+    of its pseudo-file, the padding frames of a stream's last window are discarded.  Then the slots slide (one batched indexed copy): what
+    lies in front of the next frame's first sample is dropped.  -> per stream a [n, n_mels] fp32 device tensor or None."""
+    if not isinstance(state, ResampleStream):
+        raise HfttError('stream_logmel: the first argument is an ops.ResampleStream')
+    if logmel.hop != state.hop or logmel.n_fft != state.n_fft:
+        raise HfttError('stream_logmel: the LogMel has n_fft=%d, hop=%d, the stream n_fft=%d, hop=%d' % (logmel.n_fft, logmel.hop, state.n_fft, state.hop))
+    S, hop, W = state.S, state.hop, 16
+    wf, ws, spans = [], [], [None] * S
+    for s in range(S):
+        t0, t1 = stream_frames_plan(state.n_done[s], state.frames[s], state.closed[s], hop, state.n_fft)
+        if t1 > t0:
+            spans[s] = (len(wf) * W, t1 - t0)
+            for t in range(t0, t1, W):
+                wf.append(s); ws.append(t - state.base[s] // hop)
+            state.frames[s] = t1
+    out = [None] * S
+    if wf:
+        win = torch.tensor([wf, ws], dtype=torch.int32).to(state.device)
+        spec = clip_logmel(state.table(), logmel, win[0], win[1], W, 0.0)               # [B, n_mels, 16]
+        rows = spec.permute(0, 2, 1).reshape(len(wf) * W, logmel.n_mels)
+        for s in range(S):
+            if spans[s] is not None:
+                out[s] = rows[spans[s][0]:spans[s][0] + spans[s][1]]
+    resample_stream_slide(state)
+    return out
+
+
+def resample_stream_slide(state):
+    """Drop from every slot what no later frame reads: slot position 0 moves to the multiple of hop at or below the next frame's first
+    sample, frames * hop - n_fft / 2.  One batched indexed copy for all streams (the retained pieces are at most n_fft + hop samples each)."""
+    S, L, hop = state.S, state.slot_len, state.hop
+    starts, lens, shifts = [], [], []
+    for s in range(S):
+        keep = max(state.base[s], (state.frames[s] * hop - state.n_fft // 2) // hop * hop, 0)
+        shift = keep - state.base[s]
+        if shift == 0 or state.closed[s]:
+            continue
+        n = max(0, state.n_done[s] - keep)
+        if n:
+            starts.append(s * L + shift); lens.append(n); shifts.append(shift)
+        state.base[s] = keep
+    flat = state.store.view(-1)
+    if 0 < len(starts) <= 2:                            # (slice copies, the source cloned: the two ranges may overlap)
+        for st, n, sh in zip(starts, lens, shifts):
+            flat[st - sh:st - sh + n].copy_(flat[st:st + n].clone())
+    elif starts:
+        src, shift = _segments(starts, lens, state.device, extra=shifts)
+        flat.index_copy_(0, src - shift, flat.index_select(0, src))
 
 
 # ------------------------------------------------------------------------------------------------

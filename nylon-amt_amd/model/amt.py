@@ -362,10 +362,13 @@ class AMT():
 
     # ------------------------------------------------------------------ audio as it arrives -> notes as they become final
     def open_stream(self, n_streams=1, n_offset=None, output='B', thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5,
-                    mode_velocity='ignore_zero', history=None, mode_offset='shorter'):
+                    mode_velocity='ignore_zero', history=None, mode_offset='shorter', sr=None):
         """A NoteStream: ``transcript_notes`` for audio that arrives in pieces, n_streams recordings side by side on this GPU.  See NoteStream
-        for the contract.  One process, one GPU (world > 1 raises HfttError); mode_offset 'shorter' only; there is no CPU fallback."""
-        return NoteStream(self, n_streams, n_offset, output, thred_onset, thred_offset, thred_mpe, mode_velocity, history, mode_offset)
+        for the contract.  sr: the rate of the samples that ``push_wave`` will bring, of every stream of the object (None: the feature rate);
+        they are resampled on the device with their state carried forward (hftt_resample_stream).  A rate whose filter window does not fit
+        the resampler's LDS is refused here.  One process, one GPU (world > 1 raises HfttError); mode_offset 'shorter' only; there is no CPU
+        fallback."""
+        return NoteStream(self, n_streams, n_offset, output, thred_onset, thred_offset, thred_mpe, mode_velocity, history, mode_offset, sr)
 
     # ------------------------------------------------------------------ posteriorgram -> notes (amt.py:179-344)
     def mpe2note(self, a_onset=None, a_offset=None, a_mpe=None, a_velocity=None, thred_onset=0.5, thred_offset=0.5, thred_mpe=0.5,
@@ -446,7 +449,12 @@ class NoteStream():
 
         sorted(all notes returned by push... + close, key=(onset, pitch)) == amt.transcript_notes(whole_feature, same arguments)
 
-    bit for bit, for any chunking (with push_wave: whole_feature = ``wave2feature(wave, sr, on_device=True)``).  Mechanism: the frames join a
+    bit for bit, for any chunking (with push_wave: whole_feature = ``wave2feature(wave, sr, on_device=True)``, sr the rate declared at
+    ``open_stream(sr=)``: 44.1 or 48 kHz audio goes in as it comes from the sound card).  The wave side: ONE hftt_resample_stream launch per
+    push_wave takes the new samples of all streams, behind each stream's carried tail of fewer than taps + down input samples, to the feature
+    rate and into a per-stream slot of a resampled store (ops.ResampleStream); ONE hftt_clip_logmel launch over that store computes the frames
+    that became complete, all streams at once; one batched copy slides the slots.  An output sample exists (width + down) / sr seconds
+    after its instant -- 10.4 ms at 44.1 kHz, 0.5 ms at 48 kHz --, a frame n_fft / 2 samples later.  Then the frames join a
     per-stream tail; every clip whose look-ahead has arrived is cut from the tail (hftt_clip_windows, the tail as the "file", so the min_value
     padding shows only where transcript pads), the ready clips of ALL streams are packed into model calls of up to batch_size clips and
     stitched (hftt_stitch) into per-stream rings of `history` rows, and one hftt_notes_stream_step per round returns what became final with
@@ -458,9 +466,10 @@ class NoteStream():
     half holds what is undecided (an onset or offset plateau at or above its threshold that has not ended).  A stretch that outgrows it
     raises HfttError naming the stream and history=.
     Refused with HfttError: world > 1, a device that is not ROCm, mode_offset other than 'shorter' (under 'longer' / 'offset' a note may
-    wait for an offset peak anywhere later in the file), a chunk for a closed stream, samples at another rate.  No CPU fallback."""
+    wait for an offset peak anywhere later in the file), a chunk for a closed stream, samples at another rate than the declared one, a
+    declared rate whose filter window exceeds the resampler's LDS.  No CPU fallback."""
 
-    def __init__(self, amt, n_streams, n_offset, output, thred_onset, thred_offset, thred_mpe, mode_velocity, history, mode_offset):
+    def __init__(self, amt, n_streams, n_offset, output, thred_onset, thred_offset, thred_mpe, mode_velocity, history, mode_offset, sr=None):
         from hftt_hip import ops
         if amt.world > 1:
             raise HfttError('open_stream runs on one GPU (world = %d): sharded inference uses transcript / transcript_stride + mpe2note' % amt.world)
@@ -476,6 +485,15 @@ class NoteStream():
         self.amt, self.S = amt, int(n_streams)
         if self.S < 1:
             raise HfttError('open_stream: n_streams=%d must be positive' % self.S)
+        fe = amt.config['feature']
+        self.sr = int(fe['sr']) if sr is None else int(sr)
+        if self.sr < 1:
+            raise HfttError('open_stream: sr=%d must be a positive sample rate' % self.sr)
+        if self.sr != int(fe['sr']):
+            up, down, width = ops.resample_geometry(self.sr, fe['sr'])
+            if ops.resample_stream_lds(up, down, width) > 64 * 1024:
+                raise HfttError('open_stream: input rate %d -> feature rate %d: the filter window of one workgroup (down = %d, taps = %d) exceeds '
+                                '64 KB of LDS' % (self.sr, fe['sr'], down, 2 * width + down))
         cin, cm = amt.config['input'], amt.config['midi']
         T = cin['num_frame']
         if n_offset is None:                                                    # transcript (amt.py:66-118)
@@ -498,8 +516,8 @@ class NoteStream():
         self.n = [0] * self.S                                                   # frames received
         self.next = [0] * self.S                                                # start of the next clip
         self.closed = [False] * self.S
-        self.wave = [None] * self.S                                             # push_wave: the retained samples (device fp32), from sample wave0
-        self.wave0, self.n_samp, self.wave_frames = [0] * self.S, [0] * self.S, [0] * self.S
+        self.rs = None                                                          # push_wave: the ops.ResampleStream of all streams, made at the first call
+        self.is_wave = [False] * self.S                                         # the stream has been given samples
 
     # ------------------------------------------------------------------ the public calls
     def push(self, chunks):
@@ -513,17 +531,16 @@ class NoteStream():
         return out[0] if bare else out
 
     def push_wave(self, chunks, sr=None):
-        """chunks[s]: samples of stream s at the feature rate (1-d, floating point in [-1, 1) or int16; any length; None: nothing).  A frame is
-        computed (hftt_clip_logmel over the retained samples) once the samples through t * hop + n_fft / 2 - 1 have arrived; then as push."""
+        """chunks[s]: samples of stream s at the rate declared at open_stream (the feature rate by default): 1-d, or [channels, n] and then
+        downmixed per sample as wave2feature does, ``wave.float().mean(dim=0)``; floating point in [-1, 1) or int16 (value s / 32768); any
+        length; None: nothing.  sr: omitted, or the declared rate.  One hftt_resample_stream launch and one hftt_clip_logmel launch for all
+        streams; a frame is computed once the resampled samples through t * hop + n_fft / 2 - 1 exist; then as push."""
         fe = self.amt.config['feature']
-        if sr is not None and int(sr) != int(fe['sr']):
-            raise HfttError('push_wave takes samples at the feature rate %d (got %d): resample in front of the stream' % (fe['sr'], sr))
+        if sr is not None and int(sr) != self.sr:
+            raise HfttError('push_wave takes samples at the %s rate %d (got %d): the input rate of a stream object is declared at open_stream(sr=)'
+                            % ('feature' if self.sr == int(fe['sr']) else 'declared', self.sr, sr))
         chunks, bare = self._per_stream(chunks)
-        for s, w in enumerate(chunks):
-            if w is None:
-                continue
-            self._append_wave(s, w)
-            self._append(s, self._wave_frames(s, False))
+        self._wave_round([self._wave_chunk(s, w) for s, w in enumerate(chunks)], [False] * self.S)
         out = self._run([False] * self.S)
         return out[0] if bare else out
 
@@ -535,9 +552,9 @@ class NoteStream():
         for s in which:
             if self.closed[s]:
                 raise HfttError('close: stream %d is closed already' % s)
-            if self.wave[s] is not None:
-                self._append(s, self._wave_frames(s, True))
             closing[s] = True
+        if any(closing[s] and self.is_wave[s] for s in range(self.S)):
+            self._wave_round([None] * self.S, [closing[s] and self.is_wave[s] for s in range(self.S)])
         out = self._run(closing)
         return out[0] if self.S == 1 else out
 
@@ -566,23 +583,25 @@ class NoteStream():
         self.tail[s] = torch.cat([self.tail[s], x], dim=0)
         self.n[s] += x.shape[0]
 
-    def _append_wave(self, s, w):
+    def _wave_chunk(self, s, w):
+        """one stream's chunk as ops.resample_stream takes it: 1-d, int16 or floating point; [channels, n] downmixed as wave2feature does"""
+        if w is None:
+            return None
         w = torch.as_tensor(w)
-        if w.dim() != 1:
-            raise HfttError('push_wave: stream %d: samples are 1-d (mono), got shape %s' % (s, tuple(w.shape)))
-        if w.dtype == torch.int16:
-            w = w.to(self.amt.device).float() * (1.0 / 32768.0)
-        elif w.dtype.is_floating_point:
-            w = w.to(device=self.amt.device, dtype=torch.float32)
-        else:
+        if w.dtype != torch.int16 and not w.dtype.is_floating_point:
             raise HfttError('push_wave: stream %d: samples are int16 or floating point, got %s' % (s, w.dtype))
+        if w.dim() == 2:
+            w = (w.float() * (1.0 / 32768.0) if w.dtype == torch.int16 else w.float()).mean(dim=0)      # torch.mean(wave, dim=0), amt.py:56
+        elif w.dim() != 1:
+            raise HfttError('push_wave: stream %d: samples are 1-d (mono) or [channels, n], got shape %s' % (s, tuple(w.shape)))
         if w.numel() and self.closed[s]:
             raise HfttError('NoteStream: stream %d is closed' % s)
-        self.wave[s] = w if self.wave[s] is None else torch.cat([self.wave[s], w])
-        self.n_samp[s] += w.numel()
+        self.is_wave[s] = True
+        return w
 
-    def _wave_frames(self, s, last):
-        """the frames of stream s that its samples complete (last: all 1 + n / hop of the file, zeros to the right of the samples)"""
+    def _wave_round(self, chunks, closing):
+        """the samples of all streams -> the frames they complete (closing[s]: all 1 + n / hop of the file, zeros to the right of the
+        samples), appended to the feature tails: one ops.resample_stream, one ops.stream_logmel"""
         from hftt_hip import ops
         amt, fe = self.amt, self.amt.config['feature']
         hop, n_fft = fe['hop_sample'], fe['fft_bins']
@@ -590,18 +609,11 @@ class NoteStream():
             if fe['fft_bins'] != fe['window_length']:
                 raise HfttError('window_length must equal fft_bins')
             amt._logmel = ops.LogMel(amt.device, sr=fe['sr'], n_fft=n_fft, hop=hop, n_mels=fe['mel_bins'], log_offset=fe['log_offset'])
-        t0 = self.wave_frames[s]
-        t1 = 1 + self.n_samp[s] // hop if last else max(t0, (self.n_samp[s] - n_fft // 2) // hop + 1 if self.n_samp[s] >= n_fft // 2 else 0)
-        if t1 <= t0:
-            return None
-        table = ops.WaveTable([self.wave[s]], amt.device, dtype='float32')
-        spec = ops.clip_logmel(table, amt._logmel, [0], [t0 - self.wave0[s] // hop], t1 - t0, 0.0)       # [1, n_mels, t1 - t0]
-        self.wave_frames[s] = t1
-        keep = max(self.wave0[s], (t1 * hop - n_fft // 2) // hop * hop)           # a multiple of hop, n_fft / 2 samples behind the next frame
-        keep = max(keep, 0)
-        self.wave[s] = self.wave[s][keep - self.wave0[s]:]
-        self.wave0[s] = keep
-        return spec[0].T.contiguous()
+        if self.rs is None:
+            self.rs = ops.ResampleStream(self.S, self.sr, fe['sr'], amt.device, n_fft=n_fft, hop=hop)
+        ops.resample_stream(self.rs, chunks, closing)
+        for s, frames in enumerate(ops.stream_logmel(self.rs, amt._logmel)):
+            self._append(s, frames)
 
     def _roll_rows(self, s):
         """F of transcript / transcript_stride for the n frames of stream s"""
