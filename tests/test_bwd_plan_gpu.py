@@ -28,12 +28,17 @@ token embedding + the position table) stays at 40 .. 48 at any scale and the fir
 1600, so bwd_plan_emul.condition scales the fc_q of an attention that is outside to 0.8 of the table's figure.  Resulting largest |score|
 per configuration, fp64 model on the CPU (asserted below, and measured again on every attention launch's own device operands):
 x3_small 4.82, x3_256 4.43, x3_256_long 4.51, x3_256_dec3 4.30, d128_ff256 4.58, x3_256_kt34 4.54.
+
+What the conditioning leaves out is run by test_backward_plan_attention_links_unconditioned: no condition(), the input at synth_spec's own
+scale (first encoder attention at 7,434 / 11,620, first time attention at 390 / 1,280), every attn_bwd launch under the derived bound of
+tests/attn_peaked_emul.py instead of the calibrated bands.
 """
 import time
 
 import pytest
 import torch
 
+import attn_peaked_emul as AP
 import bwd_plan_emul as PE
 import util
 from test_model_gpu import DROPOUT_CASES, OTHER_CONFIGS
@@ -71,9 +76,20 @@ def _case(name):
     return _CACHE[name]
 
 
-def _engine(dev, name, precision):
+def _case_raw(name):
+    """(state dict, input, labels, seed) of a configuration with NO conditioning: fc_q as initialised, the input at synth_spec's own scale"""
+    if ('raw', name) not in _CACHE:
+        cfg, B = CONFIGS[name]
+        model = util.build_model(cfg, MODEL_SEED, dropout=P_DROP)
+        util.perturb(model, PERTURB_SEED)
+        _CACHE[('raw', name)] = (util.sd_cpu(model), O.synth_spec(B, cfg, salt=SPEC_SALT), O.synth_labels(B, cfg, salt=LABEL_SALT),
+                                 (1234 * 1000003 + 1) & 0xFFFFFFFFFFFFFFFF)
+    return _CACHE[('raw', name)]
+
+
+def _engine(dev, name, precision, sd=None):
     cfg, B = CONFIGS[name]
-    sd = _case(name)[0]
+    sd = _case(name)[0] if sd is None else sd
     model = util.build_model(cfg, MODEL_SEED, dropout=P_DROP)
     model.load_state_dict(sd)
     model = model.to(dev)
@@ -207,6 +223,76 @@ def test_backward_plan_link_by_link(dev, name, precision):
         for i, e in enumerate(ws[pname]):
             for s in PE.sites_of(e, False):
                 assert s in set(flat), '%s[%d] %s names dropout site %d, which no forward launch of this workspace has' % (pname, i, e[2], s)
+
+
+# (configuration, precision) of the unconditioned runs: the smallest configuration in both modes, and d = 256 with 256 keys (planes)
+UNCONDITIONED = [('x3_small', 'x3'), ('x3_small', 'parity'), ('x3_256_long', 'x3')]
+
+
+def attention_links(eng, ws, plan, forward, harness, tag, lines):
+    """Steps `plan` one entry at a time and holds every attention launch, on the device's own operands, to the peaked-row criterion of
+    tests/attn_peaked_emul.py (the derived element-wise bound AND e_dev <= 3 (e32 + e_x3) + 1e-6); the other links are run and not judged.
+    harness: fwd_plan_emul or bwd_plan_emul (launch_io, make_record, engine_spans).  -> [(shape, largest |score|)] in launch order"""
+    kind = 'attn_fwd' if forward else 'attn_bwd'
+    stream = torch.cuda.current_stream(eng.device).cuda_stream
+    sp = harness.engine_spans(eng, ws)
+    reached, failures = [], []
+    for i, entry in enumerate(plan):
+        rec = None
+        if entry[2] == kind:
+            I, Oo = harness.launch_io(entry, eng, ws)
+            rec = harness.make_record(entry, {k: sp.fetch(*v) for k, v in I.items()}, {}, eng, ws)
+        eng._run(ws, plan[i:i + 1], stream, outs=ws['outs'], seed=ws['seed'], p=ws['p'])
+        if rec is None:
+            continue
+        torch.cuda.synchronize()
+        got = {k: sp.fetch(*v) for k, v in Oo.items()}
+        figs, bad, lmax = AP.check_plan_launch(rec, got, forward)
+        reached.append((rec['shape'], lmax))
+        lines.append('PEAKED-PLAN %-28s plan[%d] %s %-36s %-22s planes %d drop %.2g largest |score| %-9.4g a: %s | b: %s' % (
+            tag, i, kind, (entry[3] or {}).get('kernel', '-'), 'x'.join(map(str, rec['shape'])), rec['planes'], rec.get('drop_p', 0.0), lmax,
+            ' '.join('%s %.3g' % (f, v[0]) for f, v in figs.items()), ' '.join('%s %.3g' % (f, v[1] / v[2]) for f, v in figs.items() if f != 'mx')))
+        failures += ['plan[%d] %s %s: %s' % (i, kind, (entry[3] or {}).get('kernel', '-'), b) for b in bad]
+    assert reached and not failures, '%s\n%s' % (tag, '\n'.join(failures))
+    return reached
+
+
+def first_layers_are_outside_the_table(eng, B, reached, forward, tag, lines):
+    """the first encoder self attention [B T, H, F, F] and the first time attention [B N, H, T, T] of the plan (the last such launches of a
+    backward plan) lie beyond the largest |score| the calibrated attention bands were made on"""
+    table = PE.attn_table_lmax()
+    enc = [l for s, l in reached if s[2] == s[3] == eng.F and s[0] == B * eng.T]
+    tim = [l for s, l in reached if s[2] == s[3] == eng.T and s[0] == B * eng.N]
+    assert enc and tim, reached
+    first_enc, first_time = (enc[0], tim[0]) if forward else (enc[-1], tim[-1])
+    lines.append('PEAKED-PLAN %-28s first encoder attention reaches %.4g, first time attention %.4g (table %.3f)' % (tag, first_enc, first_time, table))
+    assert first_enc > table and first_time > table, (tag, first_enc, first_time, table)
+
+
+@pytest.mark.parametrize('name,precision', UNCONDITIONED)
+def test_backward_plan_attention_links_unconditioned(dev, name, precision):
+    """bwd_plan_emul.condition NOT applied, the input at synth_spec's own scale: the first encoder and the first time attention run on the
+    scores the calibrated bands were conditioned away from.  Every attn_bwd launch of the full plan is held teacher-forced under the derived
+    bound of tests/attn_peaked_emul.py -- the plan's own sites and seeds, planes where the plan stores planes.  The other links are not
+    judged here: the conditioned runs above hold them."""
+    cfg, B = CONFIGS[name]
+    sd, x, labels, seed = _case_raw(name)
+    model, eng = _engine(dev, name, precision, sd)
+    lines = []
+    try:
+        with torch.cuda.device(eng.device):
+            eng.forward(x.to(dev), training=True, save=True)
+            eng.loss(B, tuple(t.to(dev).contiguous() for t in labels))
+            torch.cuda.synchronize()
+            ws = eng._ws[B]
+            assert ws['seed'] == seed and ws['p'] == P_DROP and ws['saved']
+            plan, _ = eng.backward_plan(B, 0)
+            eng._patch(ws, ws['p'], ws['seed'])
+            tag = '%s/%s/backward' % (name, precision)
+            reached = attention_links(eng, ws, plan, False, PE, tag, lines)
+            first_layers_are_outside_the_table(eng, B, reached, False, tag, lines)
+    finally:
+        print('\n' + '\n'.join(lines))
 
 
 def test_stepped_plans_reach_every_kernel_of_the_paper_backward(dev):

@@ -35,7 +35,8 @@ import bwd_plan_emul as PE
 import elementwise_emul as EE
 import fwd_plan_emul as FE
 import util
-from test_bwd_plan_gpu import CONFIGS, P_DROP, _case, _engine, _pairs
+from test_bwd_plan_gpu import (CONFIGS, P_DROP, UNCONDITIONED, _case, _case_raw, _engine, _pairs, attention_links,
+                               first_layers_are_outside_the_table)
 from util import O
 
 pytestmark = pytest.mark.gpu
@@ -219,6 +220,33 @@ def test_forward_plan_link_by_link(dev, name, precision, plan):
     lines = []
     try:
         _run_case(dev, name, precision, plan == 'training', lines)
+    finally:
+        print('\n' + '\n'.join(lines))
+
+
+@pytest.mark.parametrize('name,precision', UNCONDITIONED)
+def test_forward_plan_attention_links_unconditioned(dev, name, precision):
+    """test_bwd_plan_gpu.py's unconditioned run for the training forward plan: no conditioning of fc_q, the input at synth_spec's own scale,
+    every attn_fwd launch (out, the attention map where the launch writes one, row maximum, 1 / sum) held on the device's own operands under
+    the derived bound of tests/attn_peaked_emul.py; the other links are run and not judged."""
+    cfg, B = CONFIGS[name]
+    sd, x, labels, seed = _case_raw(name)
+    model, eng = _engine(dev, name, precision, sd)
+    lines = []
+    try:
+        with torch.cuda.device(eng.device):
+            ws = eng.workspace(B)
+            outs = _new_outs(eng, B, dev)
+            ws['outs'] = outs
+            _fill(ws)
+            eng.forward(x, training=True, outputs=outs, save=True)
+            torch.cuda.synchronize()
+            assert ws['p'] == P_DROP and ws['seed'] == seed and ws['saved']
+            _fill(ws)
+            eng._patch(ws, ws['p'], ws['seed'])
+            tag = '%s/%s/forward' % (name, precision)
+            reached = attention_links(eng, ws, ws['fwd'], True, FE, tag, lines)
+            first_layers_are_outside_the_table(eng, B, reached, True, tag, lines)
     finally:
         print('\n' + '\n'.join(lines))
 

@@ -159,7 +159,13 @@ GEOMS = [(5, 4, 256, 256, 64), (5, 4, 88, 256, 64), (5, 4, 88, 88, 64), (6, 4, 1
 @pytest.mark.parametrize('qk_scale', [1.0, 40.0])
 @pytest.mark.parametrize('n,H,Lq,Lk,dh', GEOMS)
 def test_attention_fwd_bwd(dev, n, H, Lq, Lk, dh, qk_scale):
-    """qk_scale 40: logits of ~1e4 with near one-hot rows (the reference's first encoder layer on raw log-mel input)."""
+    """qk_scale 40: logits of ~1e4 with near one-hot rows (the reference's first encoder layer on raw log-mel input).
+
+    What that case does NOT see: a gradient.  With randn x 40 almost every row is one-hot to 1e-200 and dq / dk are judged against gtol * nat,
+    a product of operand maxima: recomputed on the CPU for (5,4,256,256,64), (4,2,48,48,32) and (5,4,88,256,64) the allowed error is 2.9 x,
+    13.4 x and 2.8 x the largest element of the true fp64 dq, so dq = dk = 0 passes, and only 0.8 .. 1.5 % of the rows have a second
+    probability above 1e-3 (tests/test_attn_peaked_emul_bound.py restates the inputs and asserts this).  It holds the forward, dv and
+    finiteness at that magnitude; peaked rows with LIVE gradients are held by tests/test_attn_peaked_gpu.py under a derived bound."""
     ops = _ops()
     d = H * dh
     g = torch.Generator().manual_seed(Lq * 1000 + Lk + dh)

@@ -20,7 +20,11 @@ Roundings modelled (csrc/x3_common.h, gemm_tn.hip, x3_strip.hip, x3_attn_bwd.h):
         (ln_bwd.hip);
     a bf16-stored factor enters its product as its bf16 value alone (no lo half).
   * the conv + token embedding as ONE Linear(n_proc -> d) on the folded weights (the device's hftt_fold + one x3 product).
-Not modelled (2^-22 and below): the f16-pair storage of q / k / v, the fp16 pair of the FFN block's residual.
+Not modelled (2^-22 and below): the f16-pair storage of q / k / v, the fp16 pair of the FFN block's residual.  That figure is RELATIVE and
+holds for |x| >= 2^-3 only: below it the lo half is an fp16 subnormal and the stored pair is off by up to 2^-25 absolute, which in the
+attention backward (bf16 pairs formed from the stored hi + lo) is more than any relative unit on an operand element near zero --
+tests/attn_peaked_emul.py models it (chain(planes=True)) and carries it in its bound; the whole-model bound of this file is max-normalised
+per tensor and does not resolve it.
 
 Deliberately wrong variants (for the tests that prove the bound has resolution): Switches.grad_hi (the gradient operand of every GEMM-shaped
 backward product as its bf16 rounding only: HFTT_X3_GRAD_HI's arithmetic), Switches.ffn_dw_drop_lohi (the lo(dY).hi(X) pass dropped in the
